@@ -10,11 +10,16 @@ backbone backward, gradient all-reduce (N > 1), fused clip + SGD on backbone and
 Workload (BASELINE.json configs[2], the one `metric` is quoted on): ires50-MSML + 85 742-id
 PartialFC, 112x112, batch 256 per GPU, bf16 operands / f32 accumulation.  Weak scaling.
 
-Rank 0 prints ONE JSON line: images/sec over all ranks, plus
+Rank 0 prints ONE JSON line: images/sec over all ranks (`value`) and the milliseconds of one timed
+step (`ms_per_step`).  A plain run does only that: set-up, warm-up (the box probes included, unreported),
+the --steps timed steps, the line.  With --full the line also carries
+  calibration  -- what the box probes measured right before the timed region
   roofline     -- the implicit-GEMM conv kernel: algorithmic FLOP of its launches in the timed
                   region / their summed duration (HIP events on the launch stream) vs the dense
-                  bf16 MFMA peak
+                  bf16 MFMA peak (and the per-kernel-family table of that event pass)
+  modes        -- (N == 1 only) the other precision modes and BASELINE.json configurations
   cpu_baseline -- (N == 1 only) the CPU oracle's training step on a bounded sample.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -169,6 +174,13 @@ def parse():
     ap.add_argument("--emulate-world", type=int, default=1,
                     help="config 4 sizing on ONE GPU: run the head as rank 0 of an E-way class-parallel job "
                          "(classes/E local rows, batch*E gathered feature rows, collectives omitted)")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the box calibration (a plain run runs its probes as unreported warm-up) and run "
+                         "the one-stream kernel-event pass (roofline and per-kernel figures), the other precision modes "
+                         "and configurations and the CPU baseline (the --no-* switches below still drop single parts); "
+                         "off: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--no-calibration", action="store_true", help="skip the box calibration probes (MFMA loop + device copy)")
@@ -181,7 +193,10 @@ def parse():
                     help="pin this process to the first K CPUs of its affinity mask before anything touches the GPU: what ONE "
                          "rank of an 8-rank job gets on a 16-CPU box share is K = 2 (the eager step needs one Python thread "
                          "at 60-80 %% duty; DESIGN section 6)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:             # (the calibration probes still run, unreported: see main())
+        args.no_kernel_events = args.no_extra_modes = args.no_cpu_baseline = True
+    return args
 
 
 class Trainer:
@@ -439,6 +454,29 @@ def memory_table(runner, args):
         "activations_and_workspaces_peak_gb": round((torch.cuda.max_memory_allocated() - resident) / gb, 2),
     })
     return t
+
+
+DUMP_MAX_ELEMENTS = 1 << 22           # per array: 16 MiB of float32; a larger output is written as a fixed, seeded sample
+
+
+def dump_outputs(path, runner, out, args):
+    """--dump-outputs: what the last timed step computed, as float32 DIR/<name>.npy.  Training: the two losses the step
+    returns and the parameters it updated (the backbone's flat weights, this rank's head rows); inference: the embeddings.
+    Arrays over DUMP_MAX_ELEMENTS are sampled at the same seeded flat indices in every run (`<name>_sample`)."""
+    import numpy as np
+    if args.mode == "train":
+        arrays = {"loss": out[0], "seg_loss": out[1], "backbone_weights": runner.opt.flat_w,
+                  "head_weights": runner.opt_pfc.flat_w}
+    else:
+        arrays = {"embeddings": out[0]}
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMENTS,), generator=g).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_model():
@@ -860,10 +898,15 @@ def main():
     import gc
     gc.collect()
     calib = None
+    # A plain run runs the probes and the per-step clock read too, unreported: its timed region then runs under the
+    # conditions of every line before --full existed (without the probes the timed steps measured 0.4-0.6 % slower on one
+    # box, with the probes but no clock reads 0.4 %).
     if not args.no_calibration:           # every rank (the two extra steps below hold collectives); rank 0 reports
         mf, cp, ml = calibrate()
-        calib = {"mfma_tflops": round(mf, 1), "mfma_lds_tflops": round(ml, 1), "copy_tbs": round(cp, 3),
-                 "gemm_tflops": round(calibrate_gemm(), 1)}
+        gemm = calibrate_gemm()
+        if args.full:
+            calib = {"mfma_tflops": round(mf, 1), "mfma_lds_tflops": round(ml, 1), "copy_tbs": round(cp, 3),
+                     "gemm_tflops": round(gemm, 1)}
         for _ in range(2):        # the probes leave the caches and the clock in their own state: two steps of the workload again
             throttled_step()
         barrier()
@@ -880,7 +923,7 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = throttled_step()
-        if calib is not None:
+        if not args.no_calibration:
             sclk.append(_sclk_mhz())       # one sysfs read per step (~20 us of host time, the host runs ahead of the GPU)
     barrier()
     dt = time.perf_counter() - t0
@@ -890,6 +933,8 @@ def main():
         # never be reported as a pinned one)
         raise SystemExit("bench.py: --cpu-share %d but the timed region ran with %d CPUs in the affinity mask"
                          % (args.cpu_share, len(os.sched_getaffinity(0))))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runner, out, args)
     evs = step_events[-(args.steps + 1):]
     step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(len(evs) - 1))
     median_ms = step_ms[len(step_ms) // 2] if step_ms else None

@@ -1,5 +1,5 @@
 """The bench line's contract (driver + tier framing): checked on the line of the round that is committed under
-profiles/ (written by `python bench.py --steps 20 --warmup 5` on an MI355X) -- no GPU needed here."""
+profiles/ (written by `python bench.py --full --steps 20 --warmup 5` on an MI355X) -- no GPU needed here."""
 import json
 import os
 
@@ -117,3 +117,51 @@ def test_rank_environment_of_the_self_launcher():
     kept = bench.rank_env(2, {"MASTER_PORT": "29501", "OMP_NUM_THREADS": "7", "MASTER_ADDR": "10.0.0.1"}, cpus=16)
     assert (kept["MASTER_PORT"], kept["OMP_NUM_THREADS"], kept["MASTER_ADDR"]) == ("29501", "7", "10.0.0.1")
     assert 1 <= bench.usable_cpus() <= (os.cpu_count() or 1)
+
+
+def test_plain_run_measures_the_headline_only(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: no kernel-event pass, no extra modes, no CPU baseline (the
+    calibration probes run as unreported warm-up unless --no-calibration); --full turns them on again and the --no-*
+    switches still drop single parts."""
+    import sys
+    import bench
+    extras = ("no_kernel_events", "no_extra_modes", "no_cpu_baseline")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.steps == 5 and a.warmup == 2 and a.dump_outputs is None
+    assert all(getattr(a, k) for k in extras) and not a.no_calibration
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.no_cpu_baseline and a.dump_outputs == "out"
+    assert not (a.no_calibration or a.no_kernel_events or a.no_extra_modes)
+
+
+def test_dump_outputs_float32_and_seeded_sample(tmp_path):
+    """--dump-outputs on host tensors standing in for the device ones: every array float32, small ones whole, one over
+    DUMP_MAX_ELEMENTS as `<name>_sample` at the same seeded indices in every call, within the 64 MB budget."""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    n = bench.DUMP_MAX_ELEMENTS
+    big = torch.arange(n + 12345, dtype=torch.float32)
+    runner = types.SimpleNamespace(opt=types.SimpleNamespace(flat_w=torch.ones(1000)),
+                                   opt_pfc=types.SimpleNamespace(flat_w=big))
+    out = (torch.tensor(3.5), torch.tensor(0.25, dtype=torch.bfloat16))
+    args = types.SimpleNamespace(mode="train")
+    bench.dump_outputs(str(tmp_path / "a"), runner, out, args)
+    bench.dump_outputs(str(tmp_path / "b"), runner, out, args)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["backbone_weights.npy", "head_weights_sample.npy", "loss.npy", "seg_loss.npy"]
+    total = 0
+    for f in names:
+        x = np.load(tmp_path / "a" / f)
+        assert x.dtype == np.float32 and np.array_equal(x, np.load(tmp_path / "b" / f)), f
+        total += x.nbytes
+    assert total <= 64 << 20
+    s = np.load(tmp_path / "a" / "head_weights_sample.npy")
+    assert s.shape == (n,) and (np.diff(s) >= 0).all() and s.max() > n     # sorted indices over the whole array
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 3.5
+    emb = torch.randn(6, 512)
+    bench.dump_outputs(str(tmp_path / "c"), None, (emb, None), types.SimpleNamespace(mode="infer"))
+    assert np.array_equal(np.load(tmp_path / "c" / "embeddings.npy"), emb.numpy())

@@ -241,14 +241,13 @@ def test_geometric_rasters_against_pil_imagedraw():
 
 
 def test_load_occluder_sets_from_a_reference_checkout():
-    """Container-only: the loader on the reference's own folders (read at run time from the user's checkout, never
-    copied) -- shapes of the preloaded sets, and the oracle's resize against PIL on a real entry."""
+    """The loader on a checkout-shaped occluder tree: tests/golden/occluder holds the six smallest images of each of the
+    reference's four training folders (datasets/augment/occluder) -- shapes of the preloaded sets, and the oracle's resize
+    against PIL on a real entry."""
     import os
     from PIL import Image
     from msml_amd import data
-    root = "/root/reference/datasets/augment/occluder"
-    if not os.path.isdir(root):
-        pytest.skip("no reference checkout on this machine")
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "occluder")
     sets = data.load_occluder_sets(root)
     assert [k for k, _ in sets] == ["glasses", "glasses", "scarf", "object"]
     assert sets[0][1].shape[1:] == (40, 80, 4) and sets[2][1].shape[1:] == (90, 90, 4) and sets[3][1].shape[1:] == (55, 55, 4)
