@@ -541,7 +541,9 @@ int msml_conv_wgrad_bnin(const void* u, int up, const void* v, int vp, const flo
                          int stride, int pad_h, int pad_w, int accumulate, void* workspace,
                          long ws_bytes, void* stream);
 
-/* Name of the kernel the conv entry points launch for a shape (profiling labels only). */
+/* Name of the kernel the conv entry points launch for a shape (profiling labels only).  want_stats with the
+ * MSML_KERNEL_MFM bit set names the kernel of msml_conv2d_mfm (coutp = its GEMM columns, 2 x the output channels). */
+#define MSML_KERNEL_MFM 2
 const char* msml_conv2d_kernel(int c0p, int c1p, int coutp, int N, int H, int W, int P, int Q,
                                int R, int S, int stride, int pad_h, int pad_w, int transposed,
                                int in_dtype, int out_dtype, int want_stats);
@@ -616,6 +618,31 @@ int msml_probe_mfma(const void* seed, float* out, int wgs, int iters, void* stre
  * waves (two per SIMD), per round 9 ds_read_b128 fragments feed 14 MFMAs; iters even; out[wgs * 512].
  * 2 * 16 * 16 * 32 * 14 * iters FLOP per wave. */
 int msml_probe_mfma_lds(const void* seed, float* out, int wgs, int iters, void* stream);
+
+/* ---- LightCNN-29v2 FRB (backbones/frb/lightcnn.py) ------------------------------------------------ */
+
+/* mfm (lightcnn.py:25-39): filter conv with 2C outputs + torch.max(z[:, :C], z[:, C:]) in one pass; resblock
+ * (lightcnn.py:61-65) adds its input through `residual`.  wp: packed filter weight with interleaved output rows
+ * (2k = channel k, 2k + 1 = channel k + C), kop >= the tile-rounded 2 * coutp; bias f32 [2 * coutp] in the same order;
+ * out / residual NHWC [N][P][Q][coutp] (coutp = padded C; pad channels come out zero); sel u8 [N][P][Q][coutp]:
+ * 0 tie, 1 first half larger, 2 second half larger, 3 unordered.  dtype: MSML_F32 or MSML_BF16 (in = out). */
+int msml_conv2d_mfm(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out, int coutp,
+                    const void* residual, unsigned char* sel, int N, int H, int W, int P, int Q, int R, int S,
+                    int stride, int pad_h, int pad_w, int dtype, void* stream);
+
+/* Backward of the max-feature-map (torch.max(a, b), lightcnn.py:39): dz [M][czp] in the filter's natural channel
+ * order from dy [M][cp] and the selector of msml_conv2d_mfm: the larger input takes the gradient, a tie splits it
+ * 0.5 / 0.5, an unordered pair (NaN) passes it to both; channels >= 2C of dz are written zero. */
+int msml_mfm_bwd(const void* dy, const unsigned char* sel, void* dz, long M, int cp, int C, int czp, int dtype,
+                 void* stream);
+
+/* F.max_pool2d(x, 2) + F.avg_pool2d(x, 2) (lightcnn.py:211,216,221,228) on NHWC [N][H][W][cp], H and W even:
+ * y [N][H/2][W/2][cp].  A NaN wins the max, as in torch. */
+int msml_pool2_fwd(const void* x, void* y, int N, int H, int W, int cp, int dtype, void* stream);
+
+/* Its backward: dx = 0.25 dy everywhere plus dy at the window's maximum (the first in row-major order; a NaN's
+ * position if the window holds one), recomputed from x. */
+int msml_pool2_bwd(const void* dy, const void* x, void* dx, int N, int H, int W, int cp, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

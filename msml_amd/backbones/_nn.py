@@ -5,6 +5,7 @@ import torch
 import torch.nn as nn
 
 from .. import functional as Fh
+from .. import ops
 
 
 def conv(m, x0, x1=None, want_stats=False, c0=None, c1=0, tee=False):
@@ -44,7 +45,7 @@ def conv_bn(conv_m, bn_m, x0, x1=None, prelu=None, residual=None, c1=0, res_firs
         return Fh.conv_bn_eval_x3(x0, x1, conv_m, bn_m, prelu, residual, c1, res_first)
     if (not bn_m.training and not torch.is_grad_enabled() and x0.dtype == torch.bfloat16
             and conv_m.bias is None and not isinstance(conv_m, nn.ConvTranspose2d)
-            and conv_m.out_channels % 32 == 0):
+            and conv_m.out_channels % 32 == 0 and ops.cpad(conv_m.out_channels) == conv_m.out_channels):
         return Fh.conv_bn_eval(x0, x1, conv_m, bn_m, prelu, residual, c1, res_first)
     y, stats = conv(conv_m, x0, x1, want_stats=bn_m.training, c1=c1)
     return Fh.bn_act(y, stats, bn_m, prelu, residual, res_first)

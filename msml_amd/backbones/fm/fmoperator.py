@@ -29,10 +29,13 @@ class resblock_bottle(nn.Module):
         self.conv3 = nn.Conv2d(bottle_channels, out_channels, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(out_channels, eps=1e-05)
         self.prelu3 = nn.PReLU(out_channels)
+        # the one-node bottleneck (blocks.bottleneck) needs every map stored at its own width (the IResNet FM widths);
+        # the LightCNN widths (24 / 48 / 96 / 192 in 32 / 64 / 128 / 256 storage channels) run layer by layer
+        self.stored_as_is = all(ops.cpad(c_) == c_ for c_ in (in_channels, bottle_channels, out_channels))
 
     def forward(self, x):
         if self.training and x.dtype == torch.bfloat16 and torch.is_grad_enabled() and ops.BLOCK_FUNCTION \
-                and ops.BOTTLE_FUNCTION:
+                and ops.BOTTLE_FUNCTION and self.stored_as_is:
             return blocks.bottleneck(self, x)      # one autograd node, fused backward (blocks.py)
         out = conv_bn(self.conv1, self.bn1, x, prelu=self.prelu1)
         out = conv_bn(self.conv2, self.bn2, out, prelu=self.prelu2)

@@ -17,14 +17,14 @@ from .. import functional as Fh
 from .._lib import BF16, F32
 from ..headers import AMArcFace, AMCosFace, Softmax
 from .fm import FMCnn, FMNone
-from .frb import iresnet18, iresnet34, iresnet50, iresnet100
+from .frb import iresnet18, iresnet34, iresnet50, iresnet100, lightcnn29
 from .osb import unet
 
 __all__ = ["MSML"]
 
 
 class MSML(nn.Module):
-    frb_type_list = ("iresnet18", "iresnet34", "iresnet50", "iresnet100")
+    frb_type_list = ("lightcnn", "iresnet18", "iresnet34", "iresnet50", "iresnet100")
     osb_type_list = ("unet",)
     head_type_list = ("Softmax", "AMArcFace", "AMCosFace")
 
@@ -35,14 +35,22 @@ class MSML(nn.Module):
                  use_osb: bool = True, peer_params: dict = None):
         super().__init__()
         assert len(fm_layers) == 4
-        if "iresnet" not in frb_type:
-            raise ValueError("FRB type error (msml_amd builds the IResNet FRB only)")
+        # shapes per FRB family (msml.py:47-58)
+        self.lightcnn = "lightcnn" in frb_type
+        if self.lightcnn:
+            self.input_size, self.gray = 128, True
+            self.heights = (64, 32, 16, 8)
+            self.f_channels = (48, 96, 192, 128)
+            self.dim_feature = 256
+        elif "iresnet" in frb_type:
+            self.input_size, self.gray = 112, False
+            self.heights = (56, 28, 14, 7)
+            self.f_channels = (64, 128, 256, 512)
+            self.dim_feature = 512
+        else:
+            raise ValueError("FRB type error")
         if "unet" not in osb_type:
             raise ValueError("OSB type error")
-        self.input_size, self.gray = 112, False
-        self.heights = (56, 28, 14, 7)
-        self.f_channels = (64, 128, 256, 512)
-        self.dim_feature = 512
         self.s_channels = (18, 18, 18, 18)
         peer_params = dict(peer_params or {})
         peer_params["header_type"] = header_type
@@ -58,8 +66,10 @@ class MSML(nn.Module):
                 raise ValueError("FM Operators type error")
         self.fm_ops = fm_ops          # plain list, like the reference (registered under frb)
         ctor = None
+        if self.lightcnn:
+            ctor = lightcnn29
         for key, fn in (("100", iresnet100), ("18", iresnet18), ("34", iresnet34), ("50", iresnet50)):
-            if key in frb_type:
+            if ctor is None and key in frb_type:
                 ctor = fn
                 break
         if ctor is None:
@@ -91,6 +101,11 @@ class MSML(nn.Module):
     def forward(self, x, label=None, ori=None):
         if not x.is_cuda:
             raise RuntimeError("msml_amd.MSML runs on an MI355X only (no CPU path); got a CPU tensor")
+        if self.lightcnn and self.fp16 and not self.training and not torch.is_grad_enabled() \
+                and self.eval_precision not in ("bf16",):
+            raise NotImplementedError("msml_amd: split-bf16 (%r) inference is not built for the LightCNN FRB; use "
+                                      "fp16=False (exact f32, what the reference evaluates with) or "
+                                      "eval_precision='bf16'" % (self.eval_precision,))
         from .. import ops
         if (self.fp16 and not self.training and not torch.is_grad_enabled() and self.eval_precision == "bf16x3"
                 and x.shape[0] > self.x3_chunk):
@@ -119,6 +134,8 @@ class MSML(nn.Module):
         xh = Fh.RawImage(x.float(), x3=x3) if self.fp16 else Fh.to_nhwc(x, F32)
         if ori is not None:
             ori = Fh.RawImage(ori.float()) if self.fp16 else Fh.to_nhwc(ori, F32)
+        if self.lightcnn:
+            return self._forward_lightcnn(x, xh, label, ori)
         side = ops.OSB_STREAM
         if not self.use_osb:                      # msml.py:159-161: no masks (FMNone stages only)
             feature, kd = self.frb(xh, (None, None, None, None), ori)
@@ -151,4 +168,38 @@ class MSML(nn.Module):
                 return feature, final_seg, kd
             final_cls = self.classification(feature, label) + kd
             return final_cls, final_seg, kd
+        return feature, final_seg
+
+    def _forward_lightcnn(self, x, xh, label, ori):
+        """_forward for the LightCNN FRB: its mfm stem unfolds the raw gray image itself (msml_stem_im2col, 5x5 -> 32
+        patches), the OSB takes the stem input it takes for IResNet (xh)."""
+        from .. import ops
+        dtype = BF16 if self.fp16 else F32
+        if not self.use_osb:
+            feature, kd = self.frb(x, (None, None, None, None), ori, dtype=dtype)
+            if self.training:
+                if label is None:
+                    return feature, None, kd
+                return self.classification(feature, label) + kd, None, kd
+            return feature, None
+        side = ops.OSB_STREAM
+        if side is None:
+            seg_list = self.osb(xh)
+            osb_done = None
+        else:
+            main = torch.cuda.current_stream()
+            side.wait_stream(main)
+            xh.record_stream(side)
+            with torch.cuda.stream(side):
+                seg_list = self.osb(xh)
+                osb_done = side.record_event()
+            for t_ in seg_list:
+                t_.record_stream(main)
+        final_seg = seg_list[4]
+        segs = [seg_list[3], seg_list[2], seg_list[1], seg_list[0]]
+        feature, kd = self.frb(x, segs, ori, wait_segs=osb_done, dtype=dtype)
+        if self.training:
+            if label is None:
+                return feature, final_seg, kd
+            return self.classification(feature, label) + kd, final_seg, kd
         return feature, final_seg

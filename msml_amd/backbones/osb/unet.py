@@ -44,9 +44,10 @@ class Unet(nn.Module):
     def __init__(self, block, layers, groups=1, num_classes=2, kernel_size=7, dap_k=3, gray=True,
                  input_size=128):
         super().__init__()
-        if gray or input_size != 112 or dap_k != 3 or num_classes != 2:
-            raise NotImplementedError("msml_amd: OSB is built for RGB 112x112, 2 classes, DAP k=3")
-        self.conv1 = nn.Conv2d(3, 64, kernel_size=3, stride=2, padding=1, bias=False)
+        if (gray, input_size) not in ((False, 112), (True, 128)) or dap_k != 3 or num_classes != 2:
+            raise NotImplementedError("msml_amd: OSB is built for RGB 112x112 (IResNet FRB) and gray 128x128 "
+                                      "(LightCNN FRB), 2 classes, DAP k=3")
+        self.conv1 = nn.Conv2d(1 if gray else 3, 64, kernel_size=3, stride=2, padding=1, bias=False)
         self.bn1 = nn.BatchNorm2d(64, eps=1e-05)
         self.prelu = nn.PReLU(64)
         self.layer1 = make_layer(block, 64, 64, layers[0], 2)
@@ -61,8 +62,9 @@ class Unet(nn.Module):
         self.gcm3 = _GlobalConvModule(128, s, ks)
         self.gcm4 = _GlobalConvModule(64, s, ks)
         self.gcm5 = _GlobalConvModule(64, s, ks)
-        self.deconv1 = nn.ConvTranspose2d(num_classes * 4, s, kernel_size=3, stride=2, padding=1,
-                                          bias=False)
+        # (unet.py:141-146: 4x4 on the 4x4 map of a 128 input, 3x3 on the 4x4 map of a 112 input -> 8x8 / 7x7)
+        self.deconv1 = nn.ConvTranspose2d(num_classes * 4, s, kernel_size=4 if input_size == 128 else 3, stride=2,
+                                          padding=1, bias=False)
         self.deconv2 = nn.ConvTranspose2d(2 * s, s, kernel_size=4, stride=2, padding=1, bias=False)
         self.deconv3 = nn.ConvTranspose2d(2 * s, s, kernel_size=4, stride=2, padding=1, bias=False)
         self.deconv4 = nn.ConvTranspose2d(2 * s, s, kernel_size=4, stride=2, padding=1, bias=False)

@@ -37,6 +37,10 @@ struct ConvArgs {
   float* stats;     // [tiles_m][2][coutp] partial (sum, sumsq) or null
   int stats_acc;    // accumulator mode (common.h): stats is double[MSML_ACC_ROWS][2][coutp]
   long M;
+  // MFM epilogue (msml_conv2d_mfm): GEMM columns 2k / 2k+1 are the pair (k, k + C) of the max-feature-map; the
+  // output has coutp / 2 channels, `sel` one selector byte per output element, `residual` is added after the max
+  const void* residual;
+  unsigned char* sel;
 };
 
 template <typename T>
@@ -109,7 +113,7 @@ __device__ __forceinline__ void mma_step(const u32x4* __restrict__ As, const u32
   }
 }
 
-template <typename TIN, typename TOUT, int BM, int BN, int WGM, int WGN>
+template <typename TIN, typename TOUT, int BM, int BN, int WGM, int WGN, bool MFM = false>
 __global__ void __launch_bounds__(256) k_conv_igemm(const ConvArgs p) {
   constexpr int CH = Elem<TIN>::CH, CPR = Elem<TIN>::CPR;
   constexpr int RPT = 256 / CPR;            // rows covered per pass of the 256 threads
@@ -256,6 +260,41 @@ __global__ void __launch_bounds__(256) k_conv_igemm(const ConvArgs p) {
   // ---------------- epilogue: bias, store, optional per-channel (sum, sumsq) partials -------
   const int h = lane >> 5, c32 = lane & 31;
   TOUT* outp = reinterpret_cast<TOUT*>(p.out);
+  if constexpr (MFM) {
+    // max-feature-map (backbones/frb/lightcnn.py:36-39): the pair partners sit in lanes c32 and c32 ^ 1 of the same
+    // accumulator register; the even lane writes max(a, b) (+ residual) and the selector (0 tie, 1 a, 2 b, 3 unordered)
+    const int coutp_o = p.coutp >> 1;
+    const TOUT* res = reinterpret_cast<const TOUT*>(p.residual);
+#pragma unroll
+    for (int j = 0; j < TN; j++) {
+      const int col = n0 + brow0 + j * 32 + c32;
+      const bool cok = col < p.coutp && !(c32 & 1);
+      const float bv = (p.bias && col < p.coutp) ? p.bias[col] : 0.f;
+#pragma unroll
+      for (int i = 0; i < TM; i++) {
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+          const int row = arow0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+          const long m = m0 + row;
+          const float a = acc[i][j][e] + bv;
+          const float b = __shfl_xor(a, 1, 64);
+          if (m < p.M && cok) {
+            float y;
+            unsigned char sv;
+            if (a > b) { y = a; sv = 1; }
+            else if (a < b) { y = b; sv = 2; }
+            else if (a == b) { y = a; sv = 0; }
+            else { y = (a != a) ? a : b; sv = 3; }          // NaN wins, as torch.max(a, b)
+            const long idx = m * coutp_o + (col >> 1);
+            if (res) y += load1<TOUT>(res + idx);
+            store1<TOUT>(outp + idx, y);
+            p.sel[idx] = sv;
+          }
+        }
+      }
+    }
+    return;
+  }
   float* red = reinterpret_cast<float*>(smem);     // reuse LDS: [WGM][2][BN]
   MSML_LDS_REGION(red, WGM * 2 * BN * 4);
   if (p.stats) __syncthreads();
@@ -301,12 +340,12 @@ __global__ void __launch_bounds__(256) k_conv_igemm(const ConvArgs p) {
   }
 }
 
-template <typename TIN, typename TOUT, int BM, int BN, int WGM, int WGN>
+template <typename TIN, typename TOUT, int BM, int BN, int WGM, int WGN, bool MFM = false>
 static int launch(const ConvArgs& a, hipStream_t stream) {
   constexpr int CPR = Elem<TIN>::CPR;
   size_t lds = (size_t)2 * (BM + BN) * CPR * 16;
   dim3 grid(cdiv(a.M, BM), cdiv(a.coutp, BN));
-  hipLaunchKernelGGL((k_conv_igemm<TIN, TOUT, BM, BN, WGM, WGN>), grid, dim3(256), lds, stream, a);
+  hipLaunchKernelGGL((k_conv_igemm<TIN, TOUT, BM, BN, WGM, WGN, MFM>), grid, dim3(256), lds, stream, a);
   return 0;
 }
 
@@ -368,6 +407,7 @@ extern "C" int msml_conv2d(const void* in0, int c0p, const void* in1, int c1p, c
   a.pad_h = pad_h; a.pad_w = pad_w; a.transposed = transposed;
   a.wp = wp; a.out = out; a.coutp = coutp; a.bias = bias; a.stats = stats;
   a.stats_acc = stats ? msml_tl_stats_acc : 0;
+  a.residual = nullptr; a.sel = nullptr;
   a.M = (long)N * P * Q;
   const int bn = msml_conv_tile_n(coutp);
   MSML_CHECK(kop >= cdiv(coutp, bn) * bn, MSML_ERR_SHAPE,
@@ -717,6 +757,12 @@ extern "C" int msml_conv2d_bnbwd_in_acc(const void* in0, int c0p, const void* up
 extern "C" const char* msml_conv2d_kernel(int c0p, int c1p, int coutp, int N, int H, int W, int P, int Q,
                                           int R, int S, int stride, int pad_h, int pad_w, int transposed,
                                           int in_dtype, int out_dtype, int want_stats) {
+  if (want_stats & MSML_KERNEL_MFM) {       // msml_conv2d_mfm: coutp = the GEMM columns (2 x the output channels)
+    const int bm = msml_conv_tile_n(coutp);
+    if (in_dtype == MSML_F32)
+      return bm == 128 ? "k_conv_igemm<mfm, f32, 128 x 128>" : (bm == 64 ? "k_conv_igemm<mfm, f32, 256 x 64>" : "k_conv_igemm<mfm, f32, 256 x 32>");
+    return bm == 128 ? "k_conv_igemm<mfm, bf16, 128 x 128>" : (bm == 64 ? "k_conv_igemm<mfm, bf16, 256 x 64>" : "k_conv_igemm<mfm, bf16, 256 x 32>");
+  }
   const int bn = msml_conv_tile_n(coutp);
   const bool fast = in_dtype == MSML_BF16 && !getenv("MSML_NO_FAST_CONV") && c0p % 32 == 0 && c1p % 32 == 0 &&
                     (c1p == 0 || ((R * S * (c0p / 32)) & 1) == 0) && (long)N * P * Q < (1L << 24);
@@ -750,4 +796,51 @@ extern "C" const char* msml_conv2d_kernel(int c0p, int c1p, int coutp, int N, in
   }
   if (fast) return bn == 128 ? "k_conv_fast<128 x 128, 4 waves>" : (bn == 64 ? "k_conv_fast<256 x 64, 4 waves>" : "k_conv_fast<256 x 32, 4 waves>");
   return bn == 128 ? "k_conv_igemm<128 x 128>" : (bn == 64 ? "k_conv_igemm<256 x 64>" : "k_conv_igemm<256 x 32>");
+}
+
+// Convolution + max-feature-map, backbones/frb/lightcnn.py:25-39 (mfm: `filter` conv with 2C outputs, then
+// torch.max(z[:, :C], z[:, C:])) and :53-66 (resblock: mfm(mfm(x)) + x with `residual`).  wp is the packed weight of the
+// filter with its output rows interleaved (row 2k = channel k, 2k + 1 = channel k + C, rows >= 2C zero), bias the same
+// order, padded to 2 * coutp; out / residual / sel are [N*P*Q][coutp].  Bias, max and residual are applied to the f32
+// accumulators; the 2C-channel pre-activation is never stored.  sel: 0 tie, 1 first half larger, 2 second half larger,
+// 3 unordered (a NaN) -- what msml_mfm_bwd needs to route the gradient as torch does.  Runs on the general implicit-GEMM
+// kernel (every stride / kernel size / channel count it takes; the im2col'd 5x5 stem is a 1x1 conv over its patches).
+extern "C" int msml_conv2d_mfm(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out, int coutp,
+                               const void* residual, unsigned char* sel, int N, int H, int W, int P, int Q, int R, int S,
+                               int stride, int pad_h, int pad_w, int dtype, void* stream) {
+  MSML_CHECK(in0 && wp && out && sel, MSML_ERR_SHAPE, "conv2d_mfm: null pointer");
+  MSML_CHECK(N > 0 && H > 0 && W > 0 && P > 0 && Q > 0 && R > 0 && S > 0, MSML_ERR_SHAPE, "conv2d_mfm: bad dims");
+  MSML_CHECK(c0p > 0 && c0p % 8 == 0 && coutp > 0 && coutp % 16 == 0, MSML_ERR_SHAPE,
+             "conv2d_mfm: channel counts c0p=%d coutp=%d", c0p, coutp);
+  MSML_CHECK(stride == 1 || stride == 2 || stride == 4, MSML_ERR_UNSUPPORTED, "conv2d_mfm: stride %d", stride);
+  MSML_CHECK((H + 2 * pad_h - R) / stride + 1 == P && (W + 2 * pad_w - S) / stride + 1 == Q, MSML_ERR_SHAPE,
+             "conv2d_mfm: P,Q inconsistent with H,W,R,S,stride,pad");
+  MSML_CHECK(dtype == MSML_F32 || dtype == MSML_BF16, MSML_ERR_DTYPE, "conv2d_mfm: dtype %d", dtype);
+  ConvArgs a;
+  a.in[0] = in0; a.in[1] = nullptr;
+  a.cp[0] = c0p; a.cp[1] = 0;
+  a.nseg = 1;
+  a.ksteps[0] = (R * S * c0p + 31) / 32;
+  a.ksteps[1] = 0;
+  a.Ktot = 32 * a.ksteps[0];
+  a.N = N; a.H = H; a.W = W; a.P = P; a.Q = Q; a.R = R; a.S = S;
+  a.stride = stride;
+  a.stride_shift = stride == 1 ? 0 : (stride == 2 ? 1 : 2);
+  a.pad_h = pad_h; a.pad_w = pad_w; a.transposed = 0;
+  a.wp = wp; a.out = out; a.coutp = 2 * coutp; a.bias = bias; a.stats = nullptr; a.stats_acc = 0;
+  a.residual = residual; a.sel = sel;
+  a.M = (long)N * P * Q;
+  const int bn = msml_conv_tile_n(2 * coutp);
+  MSML_CHECK(kop >= cdiv(2 * coutp, bn) * bn, MSML_ERR_SHAPE, "conv2d_mfm: packed weight has %d rows, need %d", kop,
+             cdiv(2 * coutp, bn) * bn);
+  hipStream_t st = (hipStream_t)stream;
+#define MFM_CASE(T)                                                                \
+  if (bn == 128) launch<T, T, 128, 128, 2, 2, true>(a, st);                        \
+  else if (bn == 64) launch<T, T, 256, 64, 4, 1, true>(a, st);                     \
+  else launch<T, T, 256, 32, 4, 1, true>(a, st);
+  if (dtype == MSML_F32) { MFM_CASE(float) }
+  else { MFM_CASE(unsigned short) }
+#undef MFM_CASE
+  MSML_LAUNCH_OK("conv2d_mfm");
+  return MSML_OK;
 }

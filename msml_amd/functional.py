@@ -348,6 +348,8 @@ def bn_act(x, stats, bn, prelu=None, residual=None, res_first=False, emit_stats=
     if training:
         ops.bn_counter(bn)
     c = x.shape[-1]
+    if bn.num_features != c:
+        return _bn_act_padded(x, stats, bn, prelu, residual, res_first, training)
     emit = bool(emit_stats and training and ops.EMIT_STEM_STATS and x.dtype == torch.bfloat16 and ops.acc_applies(c, BF16)
                 and (stats is None or stats.dtype == torch.float64) and 256 % (c // 8) == 0)
     out = _BnAct.apply(x, stats, bn.weight, bn.bias, prelu.weight if prelu is not None else None,
@@ -361,6 +363,26 @@ def bn_act(x, stats, bn, prelu=None, residual=None, res_first=False, emit_stats=
         if residual is None and ops.STEM_BWD_SUMS:
             y._msml_bn3 = (x, coef, prelu.weight if prelu is not None else None)
         return y
+    return out
+
+
+def _bn_act_padded(x, stats, bn, prelu, residual, res_first, training):
+    """bn_act on a map stored wider than the layer (the LightCNN FRB's 24 / 48 / 96 / 192-channel FM maps in
+    32 / 64 / 128 / 256 storage channels): the kernels see every parameter and running statistic zero-padded to the storage width (a
+    zero gamma / beta / alpha keeps the pad channels zero), the updated running statistics are copied back."""
+    import torch.nn.functional as F
+    c, cr = x.shape[-1], bn.num_features
+    assert cr < c and bn.weight is not None
+    pad = (0, c - cr)
+    rm = F.pad(bn.running_mean, pad)
+    rv = F.pad(bn.running_var, pad, value=1.0)
+    out = _BnAct.apply(x, stats, F.pad(bn.weight, pad), F.pad(bn.bias, pad),
+                       F.pad(prelu.weight, pad) if prelu is not None else None, residual, rm, rv, training,
+                       0.1 if bn.momentum is None else bn.momentum, bn.eps, res_first, False)
+    if training:
+        with torch.no_grad():
+            bn.running_mean.copy_(rm[:cr])
+            bn.running_var.copy_(rv[:cr])
     return out
 
 
@@ -950,7 +972,7 @@ def _x3_pack(owner, key, w, transpose, segs):
         wexp = _x3_expand(w.detach().float(), 0 if transpose else 1, segs)
         c1 = 3 * segs[0][1]
         c2 = 3 * segs[1][1] if len(segs) > 1 else 0
-        hit = (stamp, ops.pack_weight(wexp, transpose, c1, c2, BF16))
+        hit = (stamp, ops.pack_weight(wexp, transpose, c1, c2, BF16, stored=True))
         cache[key] = hit
     return hit[1]
 
@@ -1038,7 +1060,7 @@ def bn_conv_bn_eval_x3(x, bn_in, conv_m, bn_m, prelu):
         c_out = _eval_bn_coef(bn_m, coutp).double()
         wd = cw.detach().double()
         wf = (wd * c_in[0, :cin].view(1, cin, 1, 1)).float()
-        wp = ops.pack_weight(_x3_expand(wf, 1, [(cin, cp)]), False, 3 * cp, 0, BF16)
+        wp = ops.pack_weight(_x3_expand(wf, 1, [(cin, cp)]), False, 3 * cp, 0, BF16, stored=True)
         tap = (wd * c_in[1, :cin].view(1, cin, 1, 1)).sum(1)                  # [cout][3][3]: W t1 per tap
         rows = ((1, 2), (0, 1, 2), (0, 1))                                    # taps inside the map: first / inner / last
         b9 = torch.zeros(9, coutp, dtype=torch.float64, device=cw.device)
@@ -1104,7 +1126,7 @@ def stem_conv_bn_x3(raw, conv_m, bn_m, prelu):
     stamp = (conv_m.weight._version, ops.WEIGHT_EPOCH, conv_m.weight.data_ptr())
     hit = conv_m.__dict__.get("_msml_x3_stem")
     if hit is None or hit[0] != stamp:
-        hit = (stamp, ops.pack_weight(_x3_expand(w2.float(), 1, [(k, kp)]), False, 3 * kp, 0, BF16))
+        hit = (stamp, ops.pack_weight(_x3_expand(w2.float(), 1, [(k, kp)]), False, 3 * kp, 0, BF16, stored=True))
         conv_m.__dict__["_msml_x3_stem"] = hit
     wp = hit[1]
     coutp = cpad(cout)
@@ -1124,7 +1146,7 @@ def flat_fc_x3(x, fc_m):
     hit = fc_m.__dict__.get("_msml_x3_fc")
     if hit is None or hit[0] != stamp:
         w4 = fc_m.weight.detach().float().view(e, c, h, w)
-        hit = (stamp, ops.pack_weight(_x3_expand(w4, 1, [(c, c)]), False, 3 * c, 0, BF16))      # [E][H*W*3C]
+        hit = (stamp, ops.pack_weight(_x3_expand(w4, 1, [(c, c)]), False, 3 * c, 0, BF16, stored=True))      # [E][H*W*3C]
         fc_m.__dict__["_msml_x3_fc"] = hit
     wp = hit[1]
     y = ops.gemm_splitk(x.t.reshape(n, h * w * 3 * c), wp, cpad(e))
@@ -1296,3 +1318,148 @@ def relu_res(x, residual=None):
     y = torch.empty_like(x)
     call("msml_bn_act_fwd", x, one, zero, zero, residual, 1, y, m, c, DTYPE_OF[x.dtype])
     return y
+
+
+# ---------------------------------------------------------------------------------------------
+# LightCNN-29v2 FRB (backbones/frb/lightcnn.py): max-feature-map conv and the max + avg pool.
+
+def _mfm_pack(conv_m, weight, c, dtype):
+    """Packed operand + padded bias of an mfm filter for msml_conv2d_mfm: output rows interleaved (2k = channel k,
+    2k + 1 = channel k + C), 2 * cpad(C) rows, the rest zero.  `weight` is the parameter or its (2C, K, 1, 1) view
+    (the im2col'd stem); refreshed when the parameter changes."""
+    w0, b0 = conv_m.weight, conv_m.bias
+    stamp = (w0._version, b0._version, ops.WEIGHT_EPOCH, w0.data_ptr(), dtype)
+    hit = getattr(conv_m, "_msml_mfm_pack", None)
+    if hit is None or hit[0] != stamp:
+        cp = cpad(c)
+        w = weight.detach()
+        a, b, r, s = w.shape
+        wi = torch.zeros(2 * cp, b, r, s, dtype=torch.float32, device=w.device)
+        wi[:2 * c] = w.reshape(2, c, b, r, s).transpose(0, 1).reshape(2 * c, b, r, s)
+        bi = torch.zeros(2 * cp, dtype=torch.float32, device=w.device)
+        bi[:2 * c] = b0.detach().reshape(2, c).t().reshape(2 * c)
+        hit = (stamp, ops.pack_weight(wi, False, b, 0, dtype), bi)
+        conv_m._msml_mfm_pack = hit
+    return hit[1], hit[2]
+
+
+class _BwdCtx:
+    """The attributes _Conv._bwd reads, for a backward that feeds it a gradient of its own (the mfm expansion)."""
+
+    def __init__(self, saved, cfg, wobj, wparam, bparam):
+        self.saved_tensors = saved
+        self.cfg = cfg
+        self.wobj, self.wparam, self.bparam = wobj, wparam, bparam
+        self.has_bias = bparam is not None
+
+
+class _MfmConv(torch.autograd.Function):
+    """mfm (lightcnn.py:25-39): y = max(z[:, :C], z[:, C:]) (+ residual, lightcnn.py:65), z = conv(x, W) + b, in one
+    kernel that never stores z (msml_conv2d_mfm).  Backward: msml_mfm_bwd expands dY to dZ through the selector bytes,
+    then the filter's backward-data, weight- and bias-gradient run as for a plain conv (_Conv._bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, conv_m, c, geom, grad_param):
+        r, s, stride, pad = geom
+        n, h, w, cinp = x.shape
+        dtype = DTYPE_OF[x.dtype]
+        p = ops.conv_out_size(h, r, stride, pad, False)
+        q = ops.conv_out_size(w, s, stride, pad, False)
+        cp = cpad(c)
+        wp, bp = _mfm_pack(conv_m, weight, c, dtype)
+        out = torch.empty(n, p, q, cp, dtype=x.dtype, device=x.device)
+        sel = torch.empty(n, p, q, cp, dtype=torch.uint8, device=x.device)
+        if residual is not None:
+            assert residual.shape == out.shape and residual.dtype == x.dtype
+            residual = residual.contiguous()
+        name = "conv_mfm"
+        if ops.PROFILE.on:
+            kern = _lib.value("msml_conv2d_kernel", cinp, 0, 2 * cp, n, h, w, p, q, r, s, stride, pad, pad, 0, dtype,
+                              dtype, 2).decode()
+            name = "conv mfm%s c%d->%d %dx%d k%dx%d s%d n%d [%s]" % ("+res" if residual is not None else "", cinp, cp, h,
+                                                                     w, r, s, stride, n, kern)
+        with ops.PROFILE.rec(name, 2.0 * n * p * q * weight.shape[1] * r * s * 2 * c):
+            call("msml_conv2d_mfm", x, cinp, wp, wp.shape[0], bp, out, cp, residual, sel, n, h, w, p, q, r, s, stride,
+                 pad, pad, dtype)
+        ctx.c, ctx.geom, ctx.has_res = c, geom, residual is not None
+        ctx.grad_param = weight if grad_param is None else grad_param
+        ctx.bias = bias
+        ctx.save_for_backward(x, weight, sel)
+        ctx.mark_non_differentiable(sel)
+        return out, sel
+
+    @staticmethod
+    def backward(ctx, dy, _dsel):
+        x, weight, sel = ctx.saved_tensors
+        c = ctx.c
+        r, s, stride, pad = ctx.geom
+        dy = dy.contiguous()
+        if dy.dtype != x.dtype:
+            dy = dy.to(x.dtype)
+        n, p, q, cp = dy.shape
+        czp = cpad(2 * c)
+        dz = torch.empty(n, p, q, czp, dtype=dy.dtype, device=dy.device)
+        with ops.PROFILE.rec("mfm_bwd", 0.0, dy.numel() * dy.element_size() + sel.numel() + dz.numel() * dz.element_size()):
+            call("msml_mfm_bwd", dy, sel, dz, n * p * q, cp, c, czp, DTYPE_OF[dy.dtype])
+        cfg = {"deconv": False, "c0": weight.shape[1], "c1": 0, "cout": 2 * c, "stride": stride, "pad_h": pad,
+               "pad_w": pad}
+        bctx = _BwdCtx((x, None, weight), cfg, weight, ctx.grad_param, ctx.bias)
+        need = (ctx.needs_input_grad[0], False, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        g = _Conv._bwd(bctx, dz, need)
+        dres = dy if ctx.has_res and ctx.needs_input_grad[3] else None
+        return g[0], g[2], g[3], dres, None, None, None, None
+
+
+def mfm_conv(conv_m, c, x, residual=None):
+    """mfm filter `conv_m` (nn.Conv2d with 2C outputs) on the NHWC map x; returns the C-channel NHWC output."""
+    assert conv_m.groups == 1 and conv_m.dilation == (1, 1) and conv_m.stride[0] == conv_m.stride[1]
+    assert conv_m.padding[0] == conv_m.padding[1] and conv_m.out_channels == 2 * c
+    r, s = conv_m.kernel_size
+    geom = (r, s, conv_m.stride[0], conv_m.padding[0])
+    y, _ = _MfmConv.apply(x, conv_m.weight, conv_m.bias, residual, conv_m, c, geom, None)
+    return y
+
+
+def mfm_stem(conv_m, c, raw, dtype):
+    """mfm stem on the NCHW f32 image (lightcnn.py:150, 5x5 / 1 channel): im2col to K = R*S*Cin -> 32 patches
+    (msml_stem_im2col) and a 1x1 mfm conv over them -- no conv over a channel-padded image.  Only the filter gets
+    gradients (the image is a leaf)."""
+    cout, cin, r, s = conv_m.weight.shape
+    # (cin == 1: the view below is the parameter's own memory, so an in-place gradient arena receives dW directly)
+    assert cout == 2 * c and cin == 1 and r * s <= 32 and conv_m.stride[0] == 1
+    col = ops.stem_im2col(raw, r, s, conv_m.stride[0], conv_m.padding[0], dtype=dtype)
+    # im2col's k = (r*S + s)*Cin + c, the row-major flatten of the (Cin = 1) filter: a view of the parameter
+    wv = conv_m.weight.permute(0, 2, 3, 1).reshape(cout, r * s * cin, 1, 1)
+    y, _ = _MfmConv.apply(col, wv, conv_m.bias, None, conv_m, c, (1, 1, 1, 0), conv_m.weight)
+    return y
+
+
+class _Pool2(torch.autograd.Function):
+    """F.max_pool2d(x, 2) + F.avg_pool2d(x, 2) (lightcnn.py:211,216,221,228), NHWC, padded channels kept (zero)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        n, h, w, cp = x.shape
+        y = torch.empty(n, h // 2, w // 2, cp, dtype=x.dtype, device=x.device)
+        nb = (x.numel() + y.numel()) * x.element_size()
+        with ops.PROFILE.rec("pool2_fwd", 0.0, nb):
+            call("msml_pool2_fwd", x.contiguous(), y, n, h, w, cp, DTYPE_OF[x.dtype])
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        n, h, w, cp = x.shape
+        dy = dy.contiguous()
+        if dy.dtype != x.dtype:
+            dy = dy.to(x.dtype)
+        dx = torch.empty_like(x)
+        nb = (2 * x.numel() + dy.numel()) * x.element_size()
+        with ops.PROFILE.rec("pool2_bwd", 0.0, nb):
+            call("msml_pool2_bwd", dy, x, dx, n, h, w, cp, DTYPE_OF[x.dtype])
+        return dx
+
+
+def pool2(x):
+    return _Pool2.apply(x)

@@ -87,8 +87,12 @@ def inplace(p):
 def cpad(c):
     """Storage channel count: a multiple of 32, so that every conv over the tensor (the RGB
     stems included) takes the LDS-DMA fast path (conv_fast.hip needs Cp % 32 == 0); pad
-    channels hold exact zeros."""
-    return (c + 31) // 32 * 32
+    channels hold exact zeros.  Between 64 and 256 it is a power of two (96 -> 128, 192 -> 256:
+    the LightCNN FRB's maps), because the element-wise BatchNorm kernels need Cp / 8 to divide 256."""
+    cp = (c + 31) // 32 * 32
+    if 64 < cp < 256 and cp & (cp - 1):
+        cp = 128 if cp < 128 else 256
+    return cp
 
 
 def kpad(k):
@@ -120,12 +124,13 @@ def to_nchw(t, c):
     return out
 
 
-def pack_weight(w, transpose, c1, c2, dtype):
-    """w[A][B][R][S] f32 -> packed [KOp][Ktot] (see msml_pack_weight).  Returns (wp, KOp)."""
+def pack_weight(w, transpose, c1, c2, dtype, stored=False):
+    """w[A][B][R][S] f32 -> packed [KOp][Ktot] (see msml_pack_weight).  Returns (wp, KOp).
+    stored: c1 / c2 already are the storage widths of the input segments (the split-bf16 operands' 3 x Cp)."""
     a, b, r, s = w.shape
     ko = b if transpose else a
     kop = (cpad(ko) + tile_n(cpad(ko)) - 1) // tile_n(cpad(ko)) * tile_n(cpad(ko))
-    c1p, c2p = cpad(c1), cpad(c2) if c2 else 0
+    c1p, c2p = (c1, c2) if stored else (cpad(c1), cpad(c2) if c2 else 0)
     ktot = kpad(r * s * c1p) + (kpad(r * s * c2p) if c2 else 0)
     wp = torch.empty(kop, ktot, dtype=TORCH_DTYPE[dtype], device=w.device)
     call("msml_pack_weight", w.contiguous(), wp, a, b, r, s, int(transpose), c1, c1p, c2, c2p, kop,

@@ -20,13 +20,20 @@ def images(batch, seed=1, size=112):
     return torch.randn(batch, 3, size, size, generator=g).clamp_(-1.0, 1.0)
 
 
+def gray_images(batch, seed=1, size=128):
+    """Gray faces for the LightCNN FRB (config.py:47-56 of the reference: 1 x 128 x 128, no normalisation, [0, 1])."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.rand(batch, 1, size, size, generator=g)
+
+
 def labels(batch, num_classes, seed=1):
     g = torch.Generator().manual_seed(seed)
     return torch.randint(0, num_classes, (batch,), generator=g)
 
 
 def rect_occlusion(x, seed=1, lo=0, hi=36):
-    """Paste one random rectangle per image; returns (x_occluded, mask int64 (B,H,W) in {0,1})."""
+    """Paste one random rectangle per image (one colour draw per channel of x); returns (x_occluded, mask int64 (B,H,W)
+    in {0,1})."""
     rng = np.random.RandomState(seed)
     b, _, h, w = x.shape
     x = x.clone()
@@ -38,7 +45,7 @@ def rect_occlusion(x, seed=1, lo=0, hi=36):
         oh = int(area / ow)
         ox = rng.randint(0, w - ow + 1)
         oy = rng.randint(0, h - oh + 1)
-        for c in range(3):
+        for c in range(x.shape[1]):
             val = rng.randint(0, 256) / 255.0 * 2.0 - 1.0
             x[i, c, oy:oy + oh, ox:ox + ow] = val
         msk[i, oy:oy + oh, ox:ox + ow] = 0
