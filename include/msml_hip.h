@@ -48,11 +48,6 @@ enum { MSML_ARITH_ADD = 0, MSML_ARITH_SUB = 1, MSML_ARITH_MUL = 2, MSML_ARITH_DI
 
 int msml_version(void);
 const char* msml_last_error(void);
-/* 1 when the library was built with -DMSML_EXPERIMENTS (tools/build_variant.py --all MSML_EXPERIMENTS): the measured-slower
- * kernel variants of DESIGN.md section 8 are instantiated and their opt-in switches live (MSML_HALO_R15, MSML_BNBWD_IN,
- * MSML_BNIN_ACC_WS, MSML_HALO_WGRAD_S2).  The shipped library returns 0: those entry points answer
- * MSML_ERR_UNSUPPORTED / their *_applies queries 0. */
-int msml_has_experiments(void);
 /* Id of the graph capture `stream` is currently part of (hipStreamGetCaptureInfo; every stream forked into
  * one capture reports the same id), 0 when the stream is not capturing, negative on a HIP error.  The host
  * side keys per-capture scratch state on it (zeroed accumulator chunks: a second capture must not inherit the
@@ -244,17 +239,6 @@ int msml_bn_fin_bwd_apply(const void* dy, const void* x, const float* scale, con
                           int add_w, void* dx, void* dres, float* dgamma, float* dbeta, float* dalpha,
                           int accumulate, long M, int C, const void* next_x, const float* next_mean,
                           const float* next_invstd, double* next_acc, int dtype, void* stream);
-/* msml_bn_fin_bwd_apply whose NEXT BatchNorm is followed by a PReLU (round 6; the stems, iresnet.py:209-211 / unet.py:193-195:
- * conv -> bn -> prelu -> first IBasicBlock's bn1): dx is the gradient of PReLU(next_x * next_scale + next_shift) and next_acc
- * receives that BatchNorm's three sums (sum g', sum g' * xhat, sum dx * min(z, 0); g' = dx through the PReLU mask), so the
- * stem's own backward is an apply pass only (msml_bn_fin_bwd_apply with next_acc as its `acc`). */
-int msml_bn_fin_bwd_apply_next_act(const void* dy, const void* x, const float* scale, const float* shift,
-                                   const float* alpha, const float* save_mean, const float* save_invstd,
-                                   const double* acc, const void* residual_first, const void* add, int add_h,
-                                   int add_w, void* dx, void* dres, float* dgamma, float* dbeta, float* dalpha,
-                                   int accumulate, long M, int C, const void* next_x, const float* next_scale,
-                                   const float* next_shift, const float* next_alpha, const float* next_mean,
-                                   const float* next_invstd, double* next_acc, int dtype, void* stream);
 int msml_bn_act_bwd_acc(const void* dy, const void* x, const float* scale, const float* shift,
                         const float* alpha, const float* save_mean, const float* save_invstd,
                         const void* residual_first, const void* add, void* dx, void* dres, float* dgamma,
@@ -571,9 +555,9 @@ int msml_bn_act_bwd_apply_next(const void* dy, const void* x, const float* scale
  * acc_in (double[8][2][c0p], the producer's sums) in the kernel prologue, the normalised input applied in LDS and written
  * to act_out (NHWC like in0; the weight gradient reads it), coef_out = float[4][c0p] (scale, shift, mean, invstd), running
  * statistics updated, the output's sums added to acc_out (zero-initialised double[8][2][coutp]).  Bit-identical to
- * msml_bn_fin_act_fwd + msml_conv2d_acc.  Shapes: msml_conv2d_bnin_acc_applies -- 1: served by the halo-tile conv, 2: by the
- * weights-stationary 64-channel kernel (experiment builds only, msml_has_experiments), 3: by the persistent 128-channel halo
- * tile (round 6: 64 k input channels, 128 output channels, at least two rounds of tiles), 0: not covered. */
+ * msml_bn_fin_act_fwd + msml_conv2d_acc.  Shapes: msml_conv2d_bnin_acc_applies -- 1: served by the halo-tile conv, 3: by
+ * the persistent 128-channel halo tile (round 6: 64 k input channels, 128 output channels, at least two rounds of tiles),
+ * 0: not covered. */
 int msml_conv2d_bnin_acc_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
                                  int pad_h, int pad_w);
 int msml_conv2d_bnin_acc(const void* in0, int c0p, const double* acc_in, double count, const float* gamma,
@@ -581,23 +565,6 @@ int msml_conv2d_bnin_acc(const void* in0, int c0p, const double* acc_in, double 
                          float* coef_out, const float* in_alpha, void* act_out, const void* wp, int kop, void* out,
                          int coutp, double* acc_out, int N, int H, int W, int P, int Q, int R, int S, int stride,
                          int pad_h, int pad_w, void* stream);
-
-/* BatchNorm BACKWARD -> 3x3 / stride-1 backward-data conv -> sums of the next BatchNorm backward, ONE launch in
- * accumulator mode (the backward of conv2 / conv1 of IBasicBlock with bn3 / bn2 in front, backbones/frb/iresnet.py:59-65):
- * in0 = dy of the upper BatchNorm, up_x its saved input, up_scale ... up_invstd its saved coefficients, up_acc the three
- * sums double[8][3][c0p] its producer accumulated; dc = the BatchNorm's input gradient is formed in LDS, written to dc_out
- * (NHWC like in0; the weight gradient reads it) and convolved; dgamma / dbeta / dalpha (+)= its parameter gradients; the
- * epilogue adds the sums of the LOWER BatchNorm (bn_*, acc) exactly like msml_conv2d_bnbwd_acc.  Bit-identical to
- * msml_bn_fin_bwd_apply + msml_conv2d_bnbwd_acc.  Shapes: msml_conv2d_bnbwd_in_acc_applies. */
-int msml_conv2d_bnbwd_in_acc_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
-                                     int pad_h, int pad_w);
-int msml_conv2d_bnbwd_in_acc(const void* in0, int c0p, const void* up_x, const float* up_scale, const float* up_shift,
-                             const float* up_alpha, const float* up_mean, const float* up_invstd, const double* up_acc,
-                             float* dgamma, float* dbeta, float* dalpha, int accumulate, void* dc_out, const void* wp,
-                             int kop, void* out, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
-                             int pad_h, int pad_w, const void* bn_x, const float* bn_scale, const float* bn_shift,
-                             const float* bn_alpha, const float* bn_mean, const float* bn_invstd, double* acc,
-                             void* stream);
 
 /* Block-level entry point: every launch of one IBasicBlock forward (backbones/frb/iresnet.py:56-67; the OSB encoder's
  * copy backbones/osb/unet.py:80-91) in the bf16 training path with accumulator-mode statistics, enqueued by ONE call:

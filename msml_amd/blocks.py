@@ -204,22 +204,6 @@ def _dgrad(dy, cp, h, w, bn_x=None, coef=None, alpha=None):
     return dx, None
 
 
-def _bn_bwd_dgrad(dy, up_x, up_k, up_alpha, pgr, part, cp, h, w, bn_x, coef, alpha):
-    """BatchNorm backward + the backward-data conv behind it in one launch (ops.conv_dgrad_bnbwd_in) when the shape is
-    covered and the BatchNorm's sums arrived in an accumulator; None otherwise.  Returns (dc, dx, lower sums)."""
-    if part is None or part.dtype != torch.float64 or dy.dtype != torch.bfloat16:
-        return None
-    wparam, (cout, cin, r, s), stride, ph, pw = cp
-    n, hh, ww, c_dy = dy.shape
-    if ph != pw or hh != h or ww != w or not ops.bnbwd_in_applies(n, hh, ww, c_dy, cpad(cin), r, s, stride, ph):
-        return None
-    wp = ops.PACKS.get(wparam, True, 0, cout, 0, cin, cout, 0, BF16)
-    dc, dx, acc = ops.conv_dgrad_bnbwd_in(dy, up_x, up_k, up_alpha, part, pgr.tg, pgr.inplace, wp, cpad(cin), bn_x, coef,
-                                          alpha, real=(cout, cin))
-    pgr.done()
-    return dc, dx, acc
-
-
 def _dgrad_plus(dy, cp, h, w, other):
     """dX of a stride-1 conv plus another gradient of the same tensor, summed in the conv epilogue
     (msml_conv2d_fused with unit scale / zero shift and `other` as its residual) instead of a separate add pass."""
@@ -306,15 +290,9 @@ def _bn_bwd(dy, x, coef, alpha, pgr, partial=None, add=None, nxt=None, add_s2=Fa
         if nxt is not None and 256 % (c // 8) == 0:
             nacc = ops.stats_acc(c, x.device, 3)
             with ops.PROFILE.rec("bn_act_bwd_apply", 0.0, x.numel() * x.element_size() * (5 if add is not None else 4)):
-                if len(nxt) > 2 and nxt[2] is not None:
-                    # the NEXT BatchNorm is followed by a PReLU (a stem): its sums through the PReLU mask
-                    call("msml_bn_fin_bwd_apply_next_act", dy, x, coef[0], coef[1], alpha, coef[2], coef[3], partial, None, add,
-                         ah, aw, dx, None, pgr.tg[0], pgr.tg[1], pgr.tg[2], int(pgr.inplace), m, c, nxt[0], nxt[1][0],
-                         nxt[1][1], nxt[2], nxt[1][2], nxt[1][3], nacc, BF16)
-                else:
-                    call("msml_bn_fin_bwd_apply", dy, x, coef[0], coef[1], alpha, coef[2], coef[3], partial, None, add, ah, aw,
-                         dx, None, pgr.tg[0], pgr.tg[1], pgr.tg[2], int(pgr.inplace), m, c, nxt[0], nxt[1][2], nxt[1][3],
-                         nacc, BF16)
+                call("msml_bn_fin_bwd_apply", dy, x, coef[0], coef[1], alpha, coef[2], coef[3], partial, None, add, ah, aw,
+                     dx, None, pgr.tg[0], pgr.tg[1], pgr.tg[2], int(pgr.inplace), m, c, nxt[0], nxt[1][2], nxt[1][3],
+                     nacc, BF16)
             pgr.done()
             return dx, nacc
         with ops.PROFILE.rec("bn_act_bwd_apply", 0.0, x.numel() * x.element_size() * (4 if add is not None else 3)):
@@ -322,9 +300,7 @@ def _bn_bwd(dy, x, coef, alpha, pgr, partial=None, add=None, nxt=None, add_s2=Fa
                  dx, None, pgr.tg[0], pgr.tg[1], pgr.tg[2], int(pgr.inplace), m, c, None, None, None, None, BF16)
     else:
         cw = torch.empty(98 * c, dtype=torch.float32, device=x.device)
-        if nxt is not None and len(nxt) > 2 and nxt[2] is not None:
-            nxt = ()            # (partial-row protocol: no PReLU-aware NEXT kernel -- the stem reduces its own sums)
-        if nxt and 256 % (c // 8) == 0:
+        if nxt is not None and 256 % (c // 8) == 0:
             npart = torch.empty(_lib.value("msml_bn_act_bwd_apply_rows", m, c), 3, c, dtype=torch.float32,
                                 device=x.device)
             with ops.PROFILE.rec("bn_act_bwd_apply", 0.0, x.numel() * x.element_size() * (5 if add is not None else 4)):
@@ -461,10 +437,7 @@ def _iblock_fwd_fast(x, bp, xstats):
 
 class _IBlock(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, bp, xstats, pc2, pk3, palpha, *params):
-        # (pc2, pk3, palpha): saved input, coefficients and PReLU slope (None: no activation) of the BatchNorm that
-        # produced x -- the previous block's bn3, or a stem's bn + prelu
-        ctx.palpha = palpha
+    def forward(ctx, x, bp, xstats, pc2, pk3, *params):
         if _iblock_fwd_applies(x, bp):
             fast = _iblock_fwd_fast(x, bp, xstats)
             if fast is not None:
@@ -519,30 +492,16 @@ class _IBlock(torch.autograd.Function):
         part3 = dout.__dict__.pop("_msml_bn3_partial", None) if bp["emit_stats"] else None
         if part3 is not None:
             ops.COUNTERS["bn3_partial_hits"] += 1
-        # bn3's backward -> conv2's backward-data (+ bn2's sums): one launch where the halo kernel takes the BatchNorm
-        # backward as an input transform (ops.bnbwd_in_applies), else apply kernel + conv
-        fused = _bn_bwd_dgrad(dout, c2, k3, None, g3, part3, bp["c2"], c1.shape[1], c1.shape[2], c1, k2, alpha) \
-            if (o2 is not None and ops.FUSE_BN_BWD) else None
-        if fused is not None:
-            dc2, do2, part2 = fused
-            dw2 = _wgrad(dc2, o2, bp["c2"])
-        else:
-            dc2 = _bn_bwd(dout, c2, k3, None, g3, part3)
-            # conv2: dW beside, dX with bn2's backward sums from the epilogue
-            dw2 = _wgrad(dc2, o2, bp["c2"]) if o2 is not None else _wgrad(dc2, c1, bp["c2"], (k2, alpha))
-            do2, part2 = _dgrad(dc2, bp["c2"], c1.shape[1], c1.shape[2], c1, k2, alpha)
+        dc2 = _bn_bwd(dout, c2, k3, None, g3, part3)
+        # conv2: dW beside, dX with bn2's backward sums from the epilogue
+        dw2 = _wgrad(dc2, o2, bp["c2"]) if o2 is not None else _wgrad(dc2, c1, bp["c2"], (k2, alpha))
+        do2, part2 = _dgrad(dc2, bp["c2"], c1.shape[1], c1.shape[2], c1, k2, alpha)
         g2 = _ParamGrads((bn2[0], bn2[1], alpha), c1.shape[-1], dev)
         # bn2 (+ PReLU) backward -> conv1's backward-data (+ bn1's sums)
-        fused = _bn_bwd_dgrad(do2, c1, k2, alpha, g2, part2, bp["c1"], h, w, x, k1, None) \
-            if (o1 is not None and ops.FUSE_BN_BWD) else None
-        if fused is not None:
-            dc1, do1, part1 = fused
-            dw1 = _wgrad(dc1, o1, bp["c1"])
-        else:
-            dc1 = _bn_bwd(do2, c1, k2, alpha, g2, part2)
-            # conv1
-            dw1 = _wgrad(dc1, o1, bp["c1"]) if o1 is not None else _wgrad(dc1, x, bp["c1"], (k1, None))
-            do1, part1 = _dgrad(dc1, bp["c1"], h, w, x, k1, None)
+        dc1 = _bn_bwd(do2, c1, k2, alpha, g2, part2)
+        # conv1
+        dw1 = _wgrad(dc1, o1, bp["c1"]) if o1 is not None else _wgrad(dc1, x, bp["c1"], (k1, None))
+        do1, part1 = _dgrad(dc1, bp["c1"], h, w, x, k1, None)
         # identity / downsample path
         dwd, gd = None, None
         if ds is not None:
@@ -564,7 +523,7 @@ class _IBlock(torch.autograd.Function):
         g1 = _ParamGrads((bn1[0], bn1[1], None), x.shape[-1], dev)
         if pc2 is not None and part1 is not None and ops.FUSE_BN_BWD:
             # x is the previous block's output: reduce its bn3 sums while writing its output gradient
-            dx, pprev = _bn_bwd(do1, x, k1, None, g1, part1, add=join, nxt=(pc2, pk3, ctx.palpha), add_s2=join_s2)
+            dx, pprev = _bn_bwd(do1, x, k1, None, g1, part1, add=join, nxt=(pc2, pk3), add_s2=join_s2)
             if pprev is not None:
                 dx._msml_bn3_partial = pprev
         else:
@@ -575,7 +534,7 @@ class _IBlock(torch.autograd.Function):
         grads += [g1.out(0), g1.out(1), g2.out(0), g2.out(1), g2.out(2), g3.out(0), g3.out(1)]
         if ds is not None:
             grads += [gd.out(0), gd.out(1)]
-        return (dx, None, None, None, None, None) + tuple(grads)
+        return (dx, None, None, None, None) + tuple(grads)
 
 
 def iblock(blk, x):
@@ -594,8 +553,7 @@ def iblock(blk, x):
         blk.__dict__["_msml_pack"] = bp       # (plain attribute: not a module / parameter registration)
     xd = x.__dict__ if hasattr(x, "__dict__") else {}
     xstats, prev = xd.get("_msml_stats"), xd.get("_msml_bn3")
-    out, ostats = _IBlock.apply(x, bp, xstats, prev[0] if prev else None, prev[1] if prev else None,
-                                prev[2] if prev and len(prev) > 2 else None, *bp["params"])
+    out, ostats = _IBlock.apply(x, bp, xstats, prev[0] if prev else None, prev[1] if prev else None, *bp["params"])
     last = bp.pop("_last_bn3", None)
     if ostats.numel():
         out._msml_stats = ostats           # read by the next block (same tensor object in nn.Sequential)

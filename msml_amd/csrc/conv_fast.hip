@@ -589,8 +589,7 @@ bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, 
                              int coutp, float* stats, int N, int H, int W, int P, int Q, int R, int S,
                              int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
                              const float* scale, const float* alpha, const void* residual, int res_first,
-                             const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin = nullptr, int x3 = 0,
-                             const BnBwdIn* bin = nullptr);
+                             const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin = nullptr, int x3 = 0);
 
 // Called by msml_conv2d (conv_igemm.hip) when the fast-path conditions hold.  Returns false if
 // this kernel does not apply.
@@ -598,7 +597,7 @@ bool msml_conv_ws_dispatch(const void* in0, int c0p, const void* wp, int kop, co
                            int coutp, float* stats, int N, int H, int W, int P, int Q, int R, int S,
                            int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
                            const float* scale, const float* alpha, const void* residual, int res_first,
-                           const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin = nullptr);
+                           const BnBwdFuse* bnb, int* bnb_rows);
 
 bool msml_conv_r32_dispatch(const void* in0, int c0p, const void* wp, int kop, int ktot, const float* bias, void* out,
                             int coutp, float* stats, int stats_acc, int N, int H, int W, int P, int Q, int R, int S,

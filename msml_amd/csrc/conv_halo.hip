@@ -47,7 +47,6 @@ struct ConvHaloArgs {
   int stats_acc;      // accumulator mode (common.h): stats is double[MSML_ACC_ROWS][2][coutp]
   BnBwdFuse bnb;      // bnb.partial != nullptr: fused BatchNorm backward-reduce (common.h)
   BnIn xin;           // xin.scale != nullptr: BatchNorm(+PReLU) applied to the input image in LDS (common.h)
-  BnBwdIn bin;        // bin.x != nullptr: BatchNorm BACKWARD applied to the input image in LDS (common.h; XB kernels)
 };
 
 #define HALO_OOB 0x78000000u
@@ -83,27 +82,10 @@ extern "C" int msml_halo_trace_read(unsigned long long* dst, int n) {
 // M16: the MFMAs are v_mfma_f32_16x16x32_bf16 (28 accumulator tiles of 16 channels x 16 pixels per wave instead of 7 of
 // 32 x 32): same fragments, LDS reads and FLOP per stage, but the chip holds a higher clock under a 16x16x32 stream
 // (MI355X_MICROARCH.md, DVFS give-back item 7).  Plain forward and FUSE launches only (no XF / X3).
-// XB: backward-data launch whose input is the BatchNorm backward of (in = dy, bin.x = the BatchNorm's saved input), applied
-// per slab in LDS from the producer's accumulated sums, written through to bin.store (M16 + FUSE instantiations only).
-// R15 (round 5, M16 kernels): the weight ring with a prefetch distance of 1.5 stages on the same 8 KB per wave.  A stage's
-// weights are two k-window halves [w][32 rows][64 B] (chunk c at c ^ ((row >> 2) & 3), the 64-B-row swizzle of
-// conv_line.hip); half w = 0 of stage s + 2 is requested in the MIDDLE of stage s (its slot is free once the w = 0 fragments
-// are in registers), half w = 1 of stage s + 1 at the start of stage s: two requests at a time, the mid-stage ones in the
-// shadow of the MFMAs, instead of four in front of every stage with all eight waves queueing on the CU's one path into LDS;
-// every wait is counted (s_waitcnt vmcnt(N) returns when all but the N youngest requests are done: N = 4, + 4 while a slab
-// image requested after the wanted half is still among them), and the image is requested after the mid-stage weights.
-// BREG (round 6, M16 kernels, experiment builds, opt-in MSML_HALO_BREG=1): the wave's weights never touch LDS.  The B fragment of the 16x16x32
-// MFMA is 16 B per lane (output channel 16 g + l16, k chunk 4 w + q16) -- exactly one buffer_load_dwordx4 per (g, w) from the
-// packed weights, four per stage and wave, double-buffered in registers (the stage's fragments are copied out of the landing
-// registers behind the stage's wait, then the next stage's loads are issued into them).  What it takes off the CU's LDS:
-// 32 KB of LDS-DMA writes and 32 KB of fragment reads per stage (of 288 KB), and the DMA requests' issue cost.
-template <int BN, int NWM, bool FUSE, bool XF = false, bool X3 = false, bool M16 = false, bool XB = false, bool R15 = false,
-          bool BREG = false>
+template <int BN, int NWM, bool FUSE, bool XF = false, bool X3 = false, bool M16 = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_conv_halo(const ConvHaloArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  static_assert(!R15 || M16, "the half-stage ring rides on the 16x16x32 tiling");
-  static_assert(!BREG || (M16 && !R15), "weights in registers: 16x16x32 tiling, two-slot schedule");
   constexpr int PL2 = 4, PITCH = 16, MT = 7, KG = BN / 32, NW = KG * NWM, NT = NW * 64, BM = MT * 32;
   constexpr int TW = 14, TH = 14, HR = TH + 2, HPX = HR << PL2;
   constexpr int MTW = NWM == 1 ? MT : 4;               // accumulator tiles of one wave (at most)
@@ -119,7 +101,6 @@ k_conv_halo(const ConvHaloArgs p) {
   MSML_LDS_REGION(As, 2 * ABYTES);
   MSML_LDS_REGION(Bs, NW * 8192);
   if (XF) MSML_LDS_REGION(xtab, 3 * p.C * 4);
-  if (XB) MSML_LDS_REGION(xtab, 7 * p.C * 4);
 
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);     // scalar: LDS-DMA bases go to M0
@@ -164,7 +145,6 @@ k_conv_halo(const ConvHaloArgs p) {
     const int logical = (lane & 7) ^ skey(row);
     boffg[i] = (unsigned int)((n0 + kg * 32 + row) * p.Ktot) * 2u + logical * 16u;
   }
-  u32x4 xr2[XB ? NAI : 1];                             // XB: this lane's chunks of the BatchNorm's saved input
   auto issue_a = [&](int cs, int buf) {
     char* a = As + buf * ABYTES;
 #pragma unroll
@@ -172,11 +152,6 @@ k_conv_halo(const ConvHaloArgs p) {
       const int j = wave + i * NW;
       if (j < NAJ)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lptr_t)(a + j * 1024), 16, aoff[i] + cs * 128u, 0, 0, 0);
-      if constexpr (XB) {
-        xr2[i] = (j < NAJ && aoff[i] != HALO_OOB)
-                     ? *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(p.bin.x) + aoff[i] + cs * 128u)
-                     : u32x4{0, 0, 0, 0};
-      }
     }
   };
   // XF: every wave normalises the chunks it DMA'd itself (ordered by its own vmcnt wait); the
@@ -187,7 +162,7 @@ k_conv_halo(const ConvHaloArgs p) {
     // 16x16x32 tiling (key p & 7): hp & 7 == (lane >> 3) & 7 for every chunk of this lane, i.e. ONE channel chunk per
     // lane and slab -- its coefficients are read from the table once
     f32x4 rsc[2], rsh[2], ral[2];
-    if constexpr (M16 && !XB) {
+    if constexpr (M16) {
       const float* tb = xtab + cs * 64 + (((lane & 7) ^ ((lane >> 3) & 7)) << 3);
 #pragma unroll
       for (int hf = 0; hf < 2; hf++) {
@@ -202,13 +177,12 @@ k_conv_halo(const ConvHaloArgs p) {
       const int hp = j * 8 + (lane >> 3);
       const int logical = (lane & 7) ^ skey(hp);
       if (j < NAJ && aoff[i] != HALO_OOB) {
-        if constexpr (XB) bnbin_chunk(a + j * 1024 + lane * 16, xr2[i], xtab, p.C, cs * 64 + logical * 8, p.bin.alpha != nullptr);
-        else if constexpr (M16) bn_in_chunk_r(a + j * 1024 + lane * 16, rsc, rsh, ral, has_alpha);
+        if constexpr (M16) bn_in_chunk_r(a + j * 1024 + lane * 16, rsc, rsh, ral, has_alpha);
         else bn_in_chunk(a + j * 1024 + lane * 16, xtab, p.C, cs * 64 + logical * 8, has_alpha);
         // write-through of the normalised image (accumulator mode): the pixels this tile OWNS (not its halo), once
         // per pixel tile (the first channel block of the grid)
         const int hy = hp >> PL2, hx = hp & (PITCH - 1);
-        unsigned short* through = XB ? p.bin.store : p.xin.store;
+        unsigned short* through = p.xin.store;
         if (through && blockIdx.y == 0 && hy >= 1 && hy <= TH && hx >= 1 && hx <= TW)
           *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(through) + aoff[i] + cs * 128u) =
               *reinterpret_cast<const u32x4*>(a + j * 1024 + lane * 16);
@@ -223,41 +197,9 @@ k_conv_halo(const ConvHaloArgs p) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lptr_t)(b + i * 1024), 16, boffg[i] + col, 0, 0, 0);
   };
 
-  // BREG: this lane's 16 B of (channel 16 g + l16, k chunk 4 w + q16) of stage (cs, tap) straight into registers
-  u32x4 bnx[2][2];                                     // [w][g]: landing registers of the NEXT stage
-  unsigned int boffr[2];
-#pragma unroll
-  for (int g = 0; g < 2; g++)
-    boffr[g] = (unsigned int)((n0 + kg * 32 + 16 * g + (lane & 15)) * p.Ktot) * 2u + (unsigned int)((lane >> 4) * 16);
-  auto load_b = [&](int cs_, int tap) {
-    const unsigned int col = (unsigned int)(tap * p.C + cs_ * 64) * 2u;
-#pragma unroll
-    for (int w = 0; w < 2; w++)
-#pragma unroll
-      for (int g = 0; g < 2; g++)
-        bnx[w][g] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, boffr[g] + w * 64u, col, 0);
-  };
-
-  // R15: half (tap, slab cs, window w) -> slot `buf`: two requests of 16 rows x 64 B
-  auto key2 = [](int row) { return (row >> 2) & 3; };
-  unsigned int boffh[2];
-#pragma unroll
-  for (int i = 0; i < 2; i++) {
-    const int row = i * 16 + (lane >> 2);
-    boffh[i] = (unsigned int)((n0 + kg * 32 + row) * p.Ktot) * 2u + (unsigned int)(((lane & 3) ^ key2(row)) * 16);
-  }
-  auto issue_h = [&](int cs_, int tap, int w, int buf) {
-    char* b = Bs + wave * 8192 + buf * 4096 + w * 2048;
-    const unsigned int col = (unsigned int)(tap * p.C + cs_ * 64 + w * 32) * 2u;
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lptr_t)(b + i * 1024), 16, boffh[i] + col, 0, 0, 0);
-  };
-
   // D = W_frag x X_frag: accumulator rows = output channels, columns (lanes) = pixels, so a lane
   // ends up with 4 consecutive channels of one pixel per register quad (8-B LDS stores below)
   static_assert(!M16 || !X3, "the 16x16x32 variant serves the plain forward, FUSE and XF launches");
-  static_assert(!XB || (M16 && FUSE && !XF), "the backward input transform rides on the 16x16x32 FUSE launch");
   constexpr int NG = 2 * MTW, NGH = NG / 2;            // M16: 16-pixel groups of one wave (at most), per pipeline phase
   f32x16 acc[M16 ? 1 : MTW];
   f32x4 acc4[M16 ? NG : 1][2];                         // M16: [pixel group][channel half]: channels 16 g + 4 q + j
@@ -286,28 +228,18 @@ k_conv_halo(const ConvHaloArgs p) {
 #pragma unroll
     for (int w = 0; w < 2; w++) {
       const int row = 16 * g + l16;
-      bfr16[g][w] = R15 ? wave * 8192 + w * 2048 + row * 64 + ((q16 ^ key2(row)) << 4)
-                        : wave * 8192 + row * 128 + (((4 * w + q16) ^ skey(row)) << 4);
+      bfr16[g][w] = wave * 8192 + row * 128 + (((4 * w + q16) ^ skey(row)) << 4);
     }
 
   const int nslab = p.C >> 6, nstage = nslab * 9;
   issue_a(0, 0);
-  if constexpr (R15) {                                 // stage 0 whole, window 0 of stage 1 (stage q = slab q / 9, tap q % 9)
-    issue_h(0, 0, 0, 0);
-    issue_h(0, 0, 1, 0);
-    issue_h(0, 1, 0, 1);
-  } else if constexpr (BREG) {
-    load_b(0, 0);
-  } else {
-    issue_b(0, 0, 0);
-  }
+  issue_b(0, 0, 0);
   if (XF) {
     if (p.xin.acc) bn_in_fill_acc(p.xin, xtab, p.C, t, NT, blockIdx.x == 0 && blockIdx.y == 0);
     else bn_in_fill(p.xin, xtab, 0, p.C, t, NT);
   }
-  if (XB) bnbin_fill_acc(p.bin, xtab, p.C, t, NT, blockIdx.x == 0 && blockIdx.y == 0);
   __syncthreads();                                     // (drains vmcnt first)
-  if (XF || XB) {
+  if (XF) {
     xform(0, 0);
     __syncthreads();
   }
@@ -322,8 +254,6 @@ k_conv_halo(const ConvHaloArgs p) {
   if (HALO_PRIO == 1 ? (wave >= 4) : (wave < 4)) __builtin_amdgcn_s_setprio(1);
 #endif
   u32x4 a[2][MTW], b[2];
-  u32x4 bcur[2][2];                                    // BREG: [w][g] fragments of the current stage
-  int img_m1 = 0, img_m2 = 0;                          // R15: a slab image was requested in the middle of stage q - 1 / q - 2
 #ifdef HALO_ABLATE_READS
   u32x4 a16x[2][MTW], b16x[2][2];                      // (ablation build: fragments read once, reused by every stage)
 #endif
@@ -339,48 +269,22 @@ k_conv_halo(const ConvHaloArgs p) {
     if (wave >= 4 && (tr | ts) == 0) __builtin_amdgcn_s_sleep(HALO_SKEW);
 #endif
     HALO_STAMP(1);
-    if constexpr (R15) {
-      // window 0 of this stage (requested in the middle of stage q - 2); younger: window 1 of this stage, window 0 of the
-      // next one, and a slab image if one was requested in the middle of one of the last two stages
-      if (img_m1 | img_m2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      HALO_STAMP(2);
-      // window 1 of stage q + 1 (its slot: read last in stage q - 1); past the last stage: a harmless re-read that keeps
-      // the request pattern, and with it the counts, the same to the end
-      {
-        const int qn = q + 1 < nstage ? q + 1 : q;
-        issue_h(qn / 9, qn % 9, 1, (q + 1) & 1);
-      }
-    } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     HALO_STAMP(2);
-    if constexpr (BREG) {
-#pragma unroll
-      for (int w = 0; w < 2; w++)
-#pragma unroll
-        for (int g = 0; g < 2; g++) bcur[w][g] = bnx[w][g];
-    }
 #ifndef HALO_ABLATE_LOADS
     if (q + 1 < nstage) {
-      if constexpr (BREG) load_b(ncs, ntr * 3 + nts);
-      else issue_b(ncs, ntr * 3 + nts, (q + 1) & 1);
+      issue_b(ncs, ntr * 3 + nts, (q + 1) & 1);
       if ((tr | ts) == 0 && cs + 1 < nslab) issue_a(cs + 1, (cs + 1) & 1);
     }
 #endif
-    }
     // (the image chunks requested one stage ago have landed for this wave: the wait above)
     // (round 5: waves 4-7, the SIMD partners of 0-3, transform one tap later -- one wave's VALU beside the other's MFMAs;
     // bit-identical, 128 @ 28x28 bn + conv 103.6 -> 101.8 us, the step 29.41 / 29.50 -> 29.36 / 29.39 ms on one box.
     // -DHALO_XF_NO_STAGGER: all eight waves at tap 1)
 #ifdef HALO_XF_NO_STAGGER
-    if ((XF || XB) && tr == 0 && ts == 1 && cs + 1 < nslab) xform(cs + 1, (cs + 1) & 1);
+    if (XF && tr == 0 && ts == 1 && cs + 1 < nslab) xform(cs + 1, (cs + 1) & 1);
 #else
-    if constexpr (R15) {
-      // (the image was requested in the middle of tap 0: by tap 3 two waits with four requests to spare lie behind it)
-      if ((XF || XB) && tr == 1 && ts == (wave < 4 ? 0 : 1) && cs + 1 < nslab) xform(cs + 1, (cs + 1) & 1);
-    } else {
-      if ((XF || XB) && tr == 0 && ts == (wave < 4 ? 1 : 2) && cs + 1 < nslab) xform(cs + 1, (cs + 1) & 1);
-    }
+    if (XF && tr == 0 && ts == (wave < 4 ? 1 : 2) && cs + 1 < nslab) xform(cs + 1, (cs + 1) & 1);
 #endif
     __builtin_amdgcn_sched_barrier(0);
     HALO_STAMP(3);
@@ -408,22 +312,12 @@ k_conv_halo(const ConvHaloArgs p) {
 #pragma unroll
       for (int j = 0; j < NGH; j++)
         if (j < ng) a16[0][j] = *reinterpret_cast<const u32x4*>(Arow + ((q16 ^ asw) << 4) + j * 2048);
-      if constexpr (!BREG) {
 #pragma unroll
-        for (int g = 0; g < 2; g++) b16[0][g] = *reinterpret_cast<const u32x4*>(B + bfr16[g][0]);
-      }
+      for (int g = 0; g < 2; g++) b16[0][g] = *reinterpret_cast<const u32x4*>(B + bfr16[g][0]);
 #endif
 #pragma unroll
       for (int ph = 0; ph < 4; ph++) {
         const int cb = ph & 1, nb = cb ^ 1, w = ph >> 1, hf = ph & 1;
-        if constexpr (R15) {
-          if (ph == 1) {
-            // window 1 of this stage (requested at the start of stage q - 1); younger: window 0 of stage q + 1, the
-            // image of the middle of stage q - 1 (if any), window 1 of stage q + 1
-            if (img_m1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-          }
-        }
 #ifndef HALO_ABLATE_READS
         if (ph + 1 < 4) {
           const int nw = (ph + 1) >> 1, nhf = (ph + 1) & 1;
@@ -431,7 +325,7 @@ k_conv_halo(const ConvHaloArgs p) {
 #pragma unroll
           for (int j = 0; j < NGH; j++)
             if (nhf * NGH + j < ng) a16[nb][j] = *reinterpret_cast<const u32x4*>(Arow + ao + (nhf * NGH + j) * 2048);
-          if (nhf == 0 && !BREG) {
+          if (nhf == 0) {
 #pragma unroll
             for (int g = 0; g < 2; g++) b16[nw & 1][g] = *reinterpret_cast<const u32x4*>(B + bfr16[g][nw]);
           }
@@ -444,23 +338,9 @@ k_conv_halo(const ConvHaloArgs p) {
 #pragma unroll
             for (int g = 0; g < 2; g++)
               acc4[hf * NGH + j][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                  __builtin_bit_cast(bf16x8, BREG ? bcur[w][g] : b16[w & 1][g]), __builtin_bit_cast(bf16x8, a16[cb][j]),
+                  __builtin_bit_cast(bf16x8, b16[w & 1][g]), __builtin_bit_cast(bf16x8, a16[cb][j]),
                   acc4[hf * NGH + j][g], 0, 0, 0);
           }
-        if constexpr (R15) {
-          if (ph == (wave < 4 ? 1 : 2)) {              // (the two waves of a SIMD one phase apart: one requests while the other computes)
-            // middle of the stage, behind the MFMAs just issued: window 0 of stage q + 2 into the slot whose fragments are
-            // in registers, then (first tap of a slab) the next slab's image
-            const int qn = q + 2 < nstage ? q + 2 : q;
-            issue_h(qn / 9, qn % 9, 0, q & 1);
-            img_m2 = img_m1;
-            img_m1 = 0;
-            if ((tr | ts) == 0 && cs + 1 < nslab) {
-              issue_a(cs + 1, (cs + 1) & 1);
-              img_m1 = 1;
-            }
-          }
-        }
         __builtin_amdgcn_sched_barrier(0);
       }
     } else {
@@ -509,16 +389,7 @@ k_conv_halo(const ConvHaloArgs p) {
 #endif
     HALO_STAMP(4);
     if (ncs != cs && ncs < nslab) {
-      if constexpr (R15) {
-        // (no drain of the request queue: this wave's share of the next image was requested nine stages ago and the
-        // counted waits since have long covered it; what is in flight are the next stages' weights.  LDS traffic of the
-        // in-LDS BatchNorm is waited for, the barrier orders the rest)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      } else {
-        __syncthreads();                               // slab switch: next image landed everywhere
-      }
+      __syncthreads();                                 // slab switch: next image landed everywhere
       HALO_STAMP(5);
     }
     cs = ncs; tr = ntr; ts = nts;
@@ -1173,21 +1044,19 @@ k_conv_halo_p(const ConvHaloArgs p, const int ntiles, const unsigned int out_byt
 #endif
 }
 
-template <int BN, int NWM, bool FUSE, bool XF = false, bool X3 = false, bool M16 = false, bool XB = false, bool R15 = false,
-          bool BREG = false>
+template <int BN, int NWM, bool FUSE, bool XF = false, bool X3 = false, bool M16 = false>
 static void launch_halo(ConvHaloArgs& a, hipStream_t st) {
   size_t lds = 2 * (size_t)256 * 128 + 8 * 8192;      // two halo images + eight private weight rings
   size_t olds = (size_t)224 * (BN + 8) * 2;
   if (olds > lds) lds = olds;
   if (XF) lds += 3 * 1024 * sizeof(float);             // coefficient table, C <= 1024
-  if (XB) lds += 7 * 512 * sizeof(float);              // backward coefficient table, C <= 512
   static std::once_flag attr_once;                     // (per template instantiation; launches come from
   std::call_once(attr_once, [&] {                      //  the forward thread AND the autograd thread)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_halo<BN, NWM, FUSE, XF, X3, M16, XB, R15, BREG>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_halo<BN, NWM, FUSE, XF, X3, M16>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
   dim3 grid(a.N * a.tpy * a.tpx, a.coutp / BN);
-  k_conv_halo<BN, NWM, FUSE, XF, X3, M16, XB, R15, BREG><<<grid, dim3(512), lds, st>>>(a);
+  k_conv_halo<BN, NWM, FUSE, XF, X3, M16><<<grid, dim3(512), lds, st>>>(a);
 }
 
 static int halo_num_cus() {
@@ -1244,16 +1113,15 @@ bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, 
                              int coutp, float* stats, int N, int H, int W, int P, int Q, int R, int S,
                              int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
                              const float* scale, const float* alpha, const void* residual, int res_first,
-                             const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin, int x3, const BnBwdIn* bin) {
+                             const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin, int x3) {
   static const int m16_ = getenv("MSML_HALO_M16") ? atoi(getenv("MSML_HALO_M16")) : 2;
   static const bool xfp_ = !(getenv("MSML_BNIN_ACC_PERSIST") && atoi(getenv("MSML_BNIN_ACC_PERSIST")) == 0);
-  const bool pshape = m16_ >= 2 && !x3 && !bin && !bias && !scale && !alpha && !residual &&
+  const bool pshape = m16_ >= 2 && !x3 && !bias && !scale && !alpha && !residual &&
                       (!xin || (xfp_ && xin->acc && !transposed && !bnb && stats && c0p <= 1024)) &&
                       (!stats || msml_tl_stats_acc) && (!bnb || bnb->acc) &&
                       msml_conv_halo_persist_shape(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w) != 0;
   if (!pshape && !msml_conv_halo_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, stats != nullptr))
     return false;
-  if (bin && (!bnb || !transposed || x3 || xin || c0p > 512)) return false;
   if (x3 && (bnb || xin || stats || transposed)) return false;
   if (bnb && (bias || scale || alpha || residual || stats)) return false;
   if (xin && (bnb || transposed || c0p > 1024)) return false;
@@ -1275,23 +1143,12 @@ bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, 
   if (bnb) a.bnb = *bnb;
   a.xin = BnIn{nullptr, nullptr, nullptr};
   if (xin) a.xin = *xin;
-  a.bin = BnBwdIn{};
-  if (bin) a.bin = *bin;
   if (bnb_rows) *bnb_rows = (int)tiles;
   const bool wide = coutp % 256 == 0;
   // the 16x16x32 MFMA variant serves the plain forward / FUSE launches (round 4: +4...8 % on every shape, interleaved
   // A/B on one box, LDS conflicts 0.7 %).  MSML_HALO_M16=0 restores the 32x32x16 kernels, 1 limits
   // the variant to the 256-channel tile.
   static const int m16 = getenv("MSML_HALO_M16") ? atoi(getenv("MSML_HALO_M16")) : 2;
-  if (bin) {                             // BatchNorm backward in the prologue: 16x16x32 FUSE instantiations only
-#ifdef MSML_EXPERIMENTS
-    if (wide) launch_halo<256, 1, true, false, false, true, true>(a, st);
-    else launch_halo<128, 2, true, false, false, true, true>(a, st);
-    return true;
-#else
-    return false;                        // (measured slower: `XB` is instantiated in experiment builds only, tools/build_variant.py)
-#endif
-  }
   // 128-channel tile, several rounds of tiles per launch (128 -> 128 @ 28x28, 64 -> 128 @ 56x56): the persistent kernel
   if (pshape) {
     const size_t lds = 2 * (size_t)256 * 128 + 8 * 8192;
@@ -1319,32 +1176,6 @@ bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, 
     }
     return true;
   }
-  // the half-stage weight ring (template parameter R15) on the 256-channel tile; MSML_HALO_R15=0 (read per call: the tests
-  // compare the two): the two-slot ring with full waits
-  // (experiment builds only, -DMSML_EXPERIMENTS: measured slower)
-#ifdef MSML_EXPERIMENTS
-  const char* r15e = getenv("MSML_HALO_R15");
-  const bool r15 = r15e != nullptr && atoi(r15e) != 0;
-  if (m16 && !x3 && wide && r15) {
-    if (xin) launch_halo<256, 1, false, true, false, true, false, true>(a, st);
-    else if (bnb) launch_halo<256, 1, true, false, false, true, false, true>(a, st);
-    else launch_halo<256, 1, false, false, false, true, false, true>(a, st);
-    return true;
-  }
-#endif
-  // weights in registers (template parameter BREG) on the 256-channel tile; MSML_HALO_BREG read per call (A/B in one process).
-  // Measured neutral (round 6, tools/bench_breg.py: bit-identical, 256 @ 14x14 forward 59.5 -> 57.4 us, with the BatchNorm
-  // prologue 60.7 -> 60.8, backward-data + sums 56.6 -> 56.2; the step 29.53 -> 29.53 ms, three interleaved pairs): the
-  // weights' trip through LDS is not what the tile waits for.  Experiment builds only.
-#ifdef MSML_EXPERIMENTS
-  const char* brege = getenv("MSML_HALO_BREG");
-  if (m16 && !x3 && wide && brege != nullptr && atoi(brege) != 0) {
-    if (xin) launch_halo<256, 1, false, true, false, true, false, false, true>(a, st);
-    else if (bnb) launch_halo<256, 1, true, false, false, true, false, false, true>(a, st);
-    else launch_halo<256, 1, false, false, false, true, false, false, true>(a, st);
-    return true;
-  }
-#endif
   if (m16 && !x3 && (wide || m16 >= 2)) {
     if (xin) {                           // (same tiling as the plain launch: the two stay bit-identical)
       if (wide) launch_halo<256, 1, false, true, false, true>(a, st);

@@ -600,26 +600,18 @@ bool msml_conv_ws_applies(int c0p, int kop, int coutp, int N, int H, int W, int 
 // Forward conv whose input is X = PReLU(in0 * in_scale + in_shift) -- a training-mode BatchNorm
 // (+PReLU) in front of the conv -- applied to the halo image while it sits in LDS, so X is never
 // written to HBM (zero padding applies to X, as in the unfused graph).  Only the shapes of the
-// halo-tile kernels (conv_ws.hip, conv_halo.hip): 3x3 / stride 1 / pad 1, see
+// halo-tile kernels (conv_halo.hip): 3x3 / stride 1 / pad 1, see
 // msml_conv2d_bnin_applies; MSML_ERR_UNSUPPORTED otherwise.  stats as in msml_conv2d.
 bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out,
                              int coutp, float* stats, int N, int H, int W, int P, int Q, int R, int S,
                              int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
                              const float* scale, const float* alpha, const void* residual, int res_first,
-                             const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin, int x3 = 0, const BnBwdIn* bin = nullptr);
-bool msml_conv_ws_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out,
-                           int coutp, float* stats, int N, int H, int W, int P, int Q, int R, int S,
-                           int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
-                           const float* scale, const float* alpha, const void* residual, int res_first,
-                           const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin);
+                             const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin, int x3 = 0);
 
 extern "C" int msml_conv2d_bnin_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S,
                                         int stride, int pad_h, int pad_w, int want_stats) {
   if (getenv("MSML_NO_FAST_CONV") || c0p > 1024 || (long)N * P * Q >= (1L << 24)) return 0;
   const int bn = msml_conv_tile_n(coutp), kop = cdiv(coutp, bn) * bn;
-#ifdef MSML_EXPERIMENTS      // (the weights-stationary kernel takes an input transform in experiment builds only)
-  if (msml_conv_ws_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, want_stats != 0)) return 1;
-#endif
   return msml_conv_halo_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, want_stats != 0) ? 1 : 0;
 }
 
@@ -636,26 +628,18 @@ extern "C" int msml_conv2d_bnin(const void* in0, int c0p, const float* in_scale,
              MSML_ERR_UNSUPPORTED, "conv2d_bnin: shape not covered by the halo-tile kernels");
   const BnIn xin{in_scale, in_shift, in_alpha};
   hipStream_t st = (hipStream_t)stream;
-  const bool ok =
-      msml_conv_ws_dispatch(in0, c0p, wp, kop, nullptr, out, coutp, stats, N, H, W, P, Q, R, S, stride, pad_h, pad_w,
-                            0, st, nullptr, nullptr, nullptr, 0, nullptr, nullptr, &xin) ||
-      msml_conv_halo_dispatch(in0, c0p, wp, kop, nullptr, out, coutp, stats, N, H, W, P, Q, R, S, stride, pad_h,
-                              pad_w, 0, st, nullptr, nullptr, nullptr, 0, nullptr, nullptr, &xin);
+  const bool ok = msml_conv_halo_dispatch(in0, c0p, wp, kop, nullptr, out, coutp, stats, N, H, W, P, Q, R, S, stride,
+                                          pad_h, pad_w, 0, st, nullptr, nullptr, nullptr, 0, nullptr, nullptr, &xin);
   MSML_CHECK(ok, MSML_ERR_UNSUPPORTED, "conv2d_bnin: launch refused");
   MSML_LAUNCH_OK("conv2d_bnin");
   return MSML_OK;
 }
 
-// 1 when msml_conv2d_bnin_acc serves the shape on the halo-tile conv, 2 on the weights-stationary 64-channel kernel
-// (round 5: the in-LDS transform of that kernel keeps a lane's coefficients in registers and staggers the two waves of a
-// SIMD, conv_ws.hip), 0 otherwise.
+// 1 when msml_conv2d_bnin_acc serves the shape on the halo-tile conv, 3 on the persistent 128-channel halo tile, 0 otherwise.
 extern "C" int msml_conv2d_bnin_acc_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S,
                                             int stride, int pad_h, int pad_w) {
   if (getenv("MSML_NO_FAST_CONV") || c0p > 1024 || c0p % 8 || 256 % (c0p / 8) || (long)N * P * Q >= (1L << 24)) return 0;
   const int bn = msml_conv_tile_n(coutp), kop = cdiv(coutp, bn) * bn;
-#ifdef MSML_EXPERIMENTS      // (the weights-stationary kernel's prologue transform measured slower: experiment builds only)
-  if (msml_conv_ws_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, true)) return 2;
-#endif
   // 3: the persistent 128-channel tile takes the launch (round 6: its prologue transform pays from 64 input channels on --
   // the one-slab shape 64 -> 128 @ 56x56, conv1 of a stage's first block, has no one-round kernel to fall back to)
   static const bool xfp = !(getenv("MSML_BNIN_ACC_PERSIST") && atoi(getenv("MSML_BNIN_ACC_PERSIST")) == 0);
@@ -691,64 +675,12 @@ extern "C" int msml_conv2d_bnin_acc(const void* in0, int c0p, const double* acc_
   xin.rmean = running_mean; xin.rvar = running_var; xin.momentum = momentum; xin.eps = eps;
   xin.coef_out = coef_out; xin.store = (unsigned short*)act_out;
   msml_tl_stats_acc = 1;
-  const bool ok = msml_conv_ws_dispatch(in0, c0p, wp, kop, nullptr, out, coutp, reinterpret_cast<float*>(acc_out), N, H, W,
-                                        P, Q, R, S, stride, pad_h, pad_w, 0, (hipStream_t)stream, nullptr, nullptr, nullptr,
-                                        0, nullptr, nullptr, &xin) ||
-                  msml_conv_halo_dispatch(in0, c0p, wp, kop, nullptr, out, coutp, reinterpret_cast<float*>(acc_out), N, H,
+  const bool ok = msml_conv_halo_dispatch(in0, c0p, wp, kop, nullptr, out, coutp, reinterpret_cast<float*>(acc_out), N, H,
                                           W, P, Q, R, S, stride, pad_h, pad_w, 0, (hipStream_t)stream, nullptr, nullptr,
                                           nullptr, 0, nullptr, nullptr, &xin);
   msml_tl_stats_acc = 0;
   MSML_CHECK(ok, MSML_ERR_UNSUPPORTED, "conv2d_bnin_acc: launch refused");
   MSML_LAUNCH_OK("conv2d_bnin_acc");
-  return MSML_OK;
-}
-
-// 1 when msml_conv2d_bnbwd_in_acc serves the shape: 3x3 / stride-1 backward-data conv on the halo-tile kernel, <= 512
-// input channels (the LDS coefficient table), accumulator-mode sums on both BatchNorms.
-extern "C" int msml_conv2d_bnbwd_in_acc_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S,
-                                                int stride, int pad_h, int pad_w) {
-#ifndef MSML_EXPERIMENTS     // measured slower than the two launches: compiled into experiment builds only
-  return 0;
-#endif
-  if (getenv("MSML_NO_FAST_CONV") || c0p > 512 || c0p % 8 || 256 % (c0p / 8) || coutp % 8 || 256 % (coutp / 8) ||
-      (long)N * P * Q >= (1L << 24))
-    return 0;
-  const int bn = msml_conv_tile_n(coutp), kop = cdiv(coutp, bn) * bn;
-  return msml_conv_halo_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, false) ? 1 : 0;
-}
-
-// BatchNorm backward -> backward-data conv -> (sums of the next BatchNorm backward) in ONE launch, accumulator mode:
-// in0 = dy, the gradient of the UPPER BatchNorm's output (bn3 of an IBasicBlock for conv2's backward-data, bn2 (+ PReLU)
-// for conv1's: backbones/frb/iresnet.py:59-65); up_* describe that BatchNorm (saved input up_x, coefficients, the three
-// sums up_acc = double[8][3][c0p] its producer accumulated); its input gradient dc = scale * (g - s0 / n - xhat * s1 / n)
-// is formed per slab in LDS, written through to dc_out (the weight gradient reads it) and convolved; one workgroup adds
-// dgamma / dbeta / dalpha.  The conv epilogue then accumulates the sums of the LOWER BatchNorm (bn_*: msml_conv2d_bnbwd_acc).
-// Replaces msml_bn_fin_bwd_apply (no add / next) + msml_conv2d_bnbwd_acc bit for bit.
-extern "C" int msml_conv2d_bnbwd_in_acc(const void* in0, int c0p, const void* up_x, const float* up_scale,
-                                        const float* up_shift, const float* up_alpha, const float* up_mean,
-                                        const float* up_invstd, const double* up_acc, float* dgamma, float* dbeta,
-                                        float* dalpha, int accumulate, void* dc_out, const void* wp, int kop, void* out,
-                                        int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
-                                        int pad_h, int pad_w, const void* bn_x, const float* bn_scale,
-                                        const float* bn_shift, const float* bn_alpha, const float* bn_mean,
-                                        const float* bn_invstd, double* acc, void* stream) {
-  MSML_CHECK(in0 && up_x && up_scale && up_shift && up_mean && up_invstd && up_acc && dc_out && wp && out && bn_x &&
-                 bn_scale && bn_shift && bn_mean && bn_invstd && acc, MSML_ERR_SHAPE, "conv2d_bnbwd_in_acc: null pointer");
-  const int bn = msml_conv_tile_n(coutp);
-  MSML_CHECK(kop >= cdiv(coutp, bn) * bn, MSML_ERR_SHAPE, "conv2d_bnbwd_in_acc: packed weight rows");
-  MSML_CHECK(msml_conv2d_bnbwd_in_acc_applies(c0p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w), MSML_ERR_UNSUPPORTED,
-             "conv2d_bnbwd_in_acc: shape not covered by the halo-tile kernel");
-  BnBwdFuse f{(const unsigned short*)bn_x, bn_scale, bn_shift, bn_alpha, bn_mean, bn_invstd, reinterpret_cast<float*>(acc), 1};
-  BnBwdIn b;
-  b.x = (const unsigned short*)up_x; b.scale = up_scale; b.shift = up_shift; b.alpha = up_alpha; b.mean = up_mean;
-  b.invstd = up_invstd; b.acc = up_acc; b.count = (double)N * H * W; b.dgamma = dgamma; b.dbeta = dbeta; b.dalpha = dalpha;
-  b.accumulate = accumulate; b.store = (unsigned short*)dc_out;
-  int rows = 0;
-  const bool ok = msml_conv_halo_dispatch(in0, c0p, wp, kop, nullptr, out, coutp, nullptr, N, H, W, P, Q, R, S, stride,
-                                          pad_h, pad_w, 1, (hipStream_t)stream, nullptr, nullptr, nullptr, 0, &f, &rows,
-                                          nullptr, 0, &b);
-  MSML_CHECK(ok, MSML_ERR_UNSUPPORTED, "conv2d_bnbwd_in_acc: launch refused");
-  MSML_LAUNCH_OK("conv2d_bnbwd_in_acc");
   return MSML_OK;
 }
 

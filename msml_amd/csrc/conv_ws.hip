@@ -34,17 +34,17 @@ struct ConvWsArgs {
   int stats_rows;
   int stats_acc;      // accumulator mode (common.h)
   BnBwdFuse bnb;
-  BnIn xin;           // xin.scale != nullptr: BatchNorm(+PReLU) applied to the input image in LDS (common.h)
+  BnIn xin;           // unused (the removed BatchNorm-in-the-prologue variant): without it hipcc allocates the registers of
+                      // k_conv_ws<false, false> differently
 };
 
 #define WS_OOB 0x78000000u
 
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-// XF: forward launch whose input is PReLU(in * xin.scale + xin.shift), applied to each image in LDS.
 // M16: v_mfma_f32_16x16x32_bf16 instead of 32x32x16 (see conv_halo.hip): 8 accumulator tiles of 16 channels x 16
 // pixels per wave, the 18 32-deep windows of a tile as one software pipeline; chunk key p & 7.
-template <bool FUSE, bool XF = false, bool M16 = false>
+template <bool FUSE, bool M16 = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) k_conv_ws(const ConvWsArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int C = 64, PL2 = 4, PITCH = 16, TW = 14, TH = 14, BM = 224, NT = 512;
@@ -55,10 +55,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Ws = smem;                                     // [9 taps][64 rows][128 B]
   char* As = smem + WBYTES;                            // [2][256 px][128 B]
-  float* xtab = reinterpret_cast<float*>(smem + WBYTES + 2 * ABYTES + 512);   // XF: [3][64]
   MSML_LDS_REGION(Ws, WBYTES);
   MSML_LDS_REGION(As, 2 * ABYTES + 2 * 128);           // (+ the two pixels the padding rows read past an image)
-  if (XF) MSML_LDS_REGION(xtab, 3 * C * 4);
   MSML_LDS_REGION(As, BM * OP * 2);                    // the transposed output tile goes through an image buffer
   MSML_LDS_REGION(As + ABYTES, BM * OP * 2);
 
@@ -97,34 +95,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
       const bool v = ((unsigned)iy < (unsigned)p.H) & ((unsigned)ix < (unsigned)p.W);
       const unsigned int off = v ? (unsigned int)((n * p.H + iy) * p.W + ix) * (unsigned int)(C * 2) + logical * 16u : WS_OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lptr_t)(a + j * 1024), 16, off, 0, 0, 0);
-    }
-  };
-
-  // XF: every wave normalises the chunks it DMA'd itself (after its own vmcnt wait); padding stays zero.  A lane's
-  // chunks all hold the SAME 8 channels (chunk key (hp >> 1) & 7 = (4 (wave & 1) + (lane >> 4)) & 7, M16: hp & 7 =
-  // (lane >> 3) & 7 -- neither depends on the DMA pass i), so its coefficients live in registers for the whole kernel
-  // (xcoef, read from the LDS table once).  Accumulator mode (xin.acc): the transformed pixels this tile OWNS (not its
-  // halo) are also written to xin.store -- the weight gradient reads that tensor (conv_halo.hip, XF).
-  f32x4 xsc[2], xsh[2], xal[2];
-  auto xform = [&](int tile, int buf) {
-    const int n = tile / tpi, trem = tile - n * tpi, ty = trem / p.tpx;
-    const int y0 = ty * TH, x0 = (trem - ty * p.tpx) * TW;
-    char* a = As + buf * ABYTES;
-    const bool has_alpha = p.xin.alpha != nullptr;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int j = wave + i * 8;
-      const int hp = j * 8 + (lane >> 3);
-      const int logical = (lane & 7) ^ skey(hp);
-      const int hy = hp >> PL2, hx = hp & (PITCH - 1);
-      const int iy = y0 + hy - 1, ix = x0 + hx - 1;
-      if (((unsigned)iy < (unsigned)p.H) & ((unsigned)ix < (unsigned)p.W)) {
-        bn_in_chunk_r(a + j * 1024 + lane * 16, xsc, xsh, xal, has_alpha);
-        if (p.xin.store && hy >= 1 && hy <= TH && hx >= 1 && hx <= TW)
-          *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(p.xin.store) +
-                                    (size_t)((n * p.H + iy) * p.W + ix) * (size_t)(C * 2) + logical * 16u) =
-              *reinterpret_cast<const u32x4*>(a + j * 1024 + lane * 16);
-      }
     }
   };
 
@@ -176,22 +146,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 
   int tile = blockIdx.x;
   if (tile < p.ntiles) issue_a(tile, 0);
-  if (XF) {
-    if (p.xin.acc) bn_in_fill_acc(p.xin, xtab, C, t, NT, blockIdx.x == 0);
-    else bn_in_fill(p.xin, xtab, 0, C, t, NT);
-  }
   __syncthreads();                                     // weights + first image landed (drains vmcnt)
-  if (XF) {
-    const int ch = ((lane & 7) ^ skey(wave * 8 + (lane >> 3))) << 3;
-#pragma unroll
-    for (int hf = 0; hf < 2; hf++) {
-      xsc[hf] = *reinterpret_cast<const f32x4*>(xtab + ch + hf * 4);
-      xsh[hf] = *reinterpret_cast<const f32x4*>(xtab + C + ch + hf * 4);
-      xal[hf] = *reinterpret_cast<const f32x4*>(xtab + 2 * C + ch + hf * 4);
-    }
-    if (tile < p.ntiles) xform(tile, 0);
-    __syncthreads();
-  }
 
   // ---- direct epilogue of the 16x16x32 tiling (round 5): forward launches without a residual and backward-data launches
   // with the fused BatchNorm sums store straight from registers -- v_permlane16_swap leaves every lane with 8 contiguous
@@ -318,11 +273,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
       for (int step = 0; step < 18; step++) {
         const int cb = step & 1, nb = cb ^ 1;
-        if (XF && step == (wave < 4 ? 6 : 12) && tile + (int)gridDim.x < p.ntiles) {   // next image: requested at the top of this tile;
-          // waves 4-7 (the SIMD partners of 0-3) transform six steps later: one wave's VALU beside the other's MFMAs
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          xform(tile + gridDim.x, cur ^ 1);
-        }
 #ifdef WS_ABLATE_READS
         if (step + 1 < 18) { a16[nb][0] = a16[cb][0]; a16[nb][1] = a16[cb][1]; a16[nb][2] = a16[cb][2]; a16[nb][3] = a16[cb][3];
                              b16[nb][0] = b16[cb][0]; b16[nb][1] = b16[cb][1]; }   // (timing build: fragments read once per tile)
@@ -350,11 +300,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
       const int arow = r32 + s, asw = (arow >> 1) & 7;
       const char* Arow = Abase + ((r << PL2) + arow) * 128;
       const char* B = Ws + tap * 8192;
-      if (XF && tap == (wave < 4 ? 3 : 6) && tile + (int)gridDim.x < p.ntiles) {   // next image: requested >= 3 taps ago; waves
-        // 4-7 (the SIMD partners of 0-3) transform three taps later: one wave's VALU beside the other's MFMAs
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        xform(tile + gridDim.x, cur ^ 1);
-      }
 #pragma unroll
       for (int i = 0; i < 2; i++)
         if (i < nmt) a[0][i] = *reinterpret_cast<const u32x4*>(Arow + ((h ^ asw) << 4) + i * 4096);
@@ -558,17 +503,16 @@ bool msml_conv_ws_applies(int c0p, int kop, int coutp, int N, int H, int W, int 
   return (long)N * H * W * c0p * 2 < 0x70000000L && tiles < (1L << 30);
 }
 
-template <bool FUSE, bool XF = false, bool M16 = false>
+template <bool FUSE, bool M16 = false>
 static void launch_ws(ConvWsArgs& a, hipStream_t st) {
-  // (+ the 2 pixels the padding rows read past an image, + the input-transform coefficient table)
-  const size_t lds = 9 * 64 * 128 + 2 * 256 * 128 + 512 + (XF ? 3 * 64 * sizeof(float) : 0);
+  const size_t lds = 9 * 64 * 128 + 2 * 256 * 128 + 512;   // (+ the 2 pixels the padding rows read past an image)
   static std::once_flag attr_once;                     // (per template instantiation; launches come from
   std::call_once(attr_once, [&] {                      //  the forward thread AND the autograd thread)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_ws<FUSE, XF, M16>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_ws<FUSE, M16>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
   const int wgs = a.ntiles < ws_num_cus() ? a.ntiles : ws_num_cus();
-  k_conv_ws<FUSE, XF, M16><<<dim3(wgs), dim3(512), lds, st>>>(a);
+  k_conv_ws<FUSE, M16><<<dim3(wgs), dim3(512), lds, st>>>(a);
 }
 
 // Tried by msml_conv_fast_dispatch before the im2col kernel; false = shape not covered here.
@@ -576,14 +520,10 @@ bool msml_conv_ws_dispatch(const void* in0, int c0p, const void* wp, int kop, co
                            int coutp, float* stats, int N, int H, int W, int P, int Q, int R, int S,
                            int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
                            const float* scale, const float* alpha, const void* residual, int res_first,
-                           const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin) {
+                           const BnBwdFuse* bnb, int* bnb_rows) {
   if (!msml_conv_ws_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, stats != nullptr))
     return false;
   if (bnb && (bias || scale || alpha || residual || stats)) return false;
-  if (xin && (bnb || transposed)) return false;
-#ifndef MSML_EXPERIMENTS
-  if (xin) return false;       // (BatchNorm in this kernel's prologue measured slower, DESIGN section 8: experiment builds only)
-#endif
   ConvWsArgs a;
   a.tpy = cdiv(H, 14); a.tpx = cdiv(W, 14);
   a.ntiles = N * a.tpy * a.tpx;
@@ -597,8 +537,6 @@ bool msml_conv_ws_dispatch(const void* in0, int c0p, const void* wp, int kop, co
   a.stats_acc = stats ? msml_tl_stats_acc : 0;
   a.bnb = BnBwdFuse{};
   if (bnb) a.bnb = *bnb;
-  a.xin = BnIn{nullptr, nullptr, nullptr};
-  if (xin) a.xin = *xin;
   if (bnb_rows) *bnb_rows = a.ntiles < ws_num_cus() ? a.ntiles : ws_num_cus();
   // 16x16x32 variant: measured neutral here (64 -> 64 @ 112x112 forward 426 -> 408 us, backward-data and the 56x56 maps
   // +-1 %: this kernel waits on its image loads and transposes, not on the MFMA clock) -- opt-in, MSML_WS_M16=1
@@ -606,11 +544,7 @@ bool msml_conv_ws_dispatch(const void* in0, int c0p, const void* wp, int kop, co
   // 112x112 forward 431 -> 385 us, @ 56x56 100 -> 93 us, the step 29.38 -> 29.17 / 29.26 ms (one box, twice): default;
   // MSML_WS_M16=0 restores the 32x32x16 kernels.
   static const bool m16 = !(getenv("MSML_WS_M16") && atoi(getenv("MSML_WS_M16")) == 0);
-#ifdef MSML_EXPERIMENTS
-  if (xin) { if (m16) launch_ws<false, true, true>(a, st); else launch_ws<false, true>(a, st); }   // (same tiling as the plain launch)
-  else
-#endif
-  if (bnb) { if (m16) launch_ws<true, false, true>(a, st); else launch_ws<true>(a, st); }
-  else { if (m16) launch_ws<false, false, true>(a, st); else launch_ws<false>(a, st); }
+  if (bnb) { if (m16) launch_ws<true, true>(a, st); else launch_ws<true>(a, st); }
+  else { if (m16) launch_ws<false, true>(a, st); else launch_ws<false>(a, st); }
   return true;
 }

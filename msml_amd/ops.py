@@ -309,14 +309,6 @@ def bnin_applies(n, h, w, cin_p, cout_p, a_real, b_real):
 # (tools/bench_bnin.py: 256 -> 256 @ 14x14 bn 12 + conv 65 us -> 67-70 us; 128 @ 28x28 only 18 + 82 -> 96).
 BNIN_ACC = os.environ.get("MSML_NO_BNIN_ACC") is None
 BNIN_ACC_MIN_C = int(os.environ.get("MSML_BNIN_ACC_MIN_C", "256"))
-# ... and on the weights-stationary 64 -> 64 channel kernel (the 112x112 / 56x56 levels, where a BatchNorm pass is a
-# 0.2 - 0.8 GB round trip): built in round 5 with lane-resident coefficients, the two waves of a SIMD
-# transforming three taps apart and write-through -- bit-identical (test_conv_bn_from_accumulator_in_the_prologue), but
-# NOT faster: tools/bench_bnin_acc.py, cold operands, 64 -> 64 @ 56x56 bn + conv 146.8 us -> 155.4 us in one launch (conv
-# alone 106.1), @ 112x112 532.1 -> 523.2 (conv alone 367.4); without the write-through the transform alone adds 34 / 141 us
-# (tools/bench_bnin.py) -- exactly the cost of the separate pass.  With K = 576 a tile's 16 K elements are ~1 100 VALU
-# cycles per wave against 2 300 MFMA cycles and do not hide beside the partner wave's MFMAs.  Opt-in: MSML_BNIN_ACC_WS=1.
-BNIN_ACC_WS = os.environ.get("MSML_BNIN_ACC_WS") is not None
 _BNIN_ACC_OK = {}
 
 
@@ -330,7 +322,7 @@ def bnin_acc_applies(n, h, w, cin_p, cout_p, r, s, stride, pad):
             kind = _lib.value("msml_conv2d_bnin_acc_applies", cin_p, cout_p, n, h, w, h, w, 3, 3, 1, 1, 1)
             # kind 3 (round 6): the persistent 128-channel tile takes the launch -- its prologue transform pays at 128 input
             # channels already (MSML_BNIN_ACC_PERSIST=0: the library answers 1 for these shapes again)
-            ok = (kind == 1 and cin_p >= BNIN_ACC_MIN_C) or (kind == 2 and BNIN_ACC_WS) or kind == 3
+            ok = (kind == 1 and cin_p >= BNIN_ACC_MIN_C) or kind == 3
         _BNIN_ACC_OK[key] = ok
     return ok
 
@@ -352,45 +344,6 @@ def conv2d_bnin_acc(x, acc_in, bnp, alpha, wp, coutp, real=None):
         call("msml_conv2d_bnin_acc", x, c0p, acc_in, float(n * h * w), bnp[0], bnp[1], bnp[2], bnp[3], bnp[4], bnp[5], coef,
              alpha, act, wp, wp.shape[0], out, coutp, acc_out, n, h, w, h, w, 3, 3, 1, 1, 1)
     return act, coef, out, acc_out
-
-
-# The backward counterpart (msml_conv2d_bnbwd_in_acc): the BatchNorm backward-apply in front of a backward-data conv is
-# formed in that conv's prologue from the producer's accumulated sums, written through for the weight gradient.
-# Measured (round 4, one box, 12 steps, twice): bit-identical but NOT faster -- 30.27 / 30.34 ms without, 30.41 / 30.41 ms
-# with (the transform needs the BatchNorm's saved input as a second operand, 25 MB more per launch through the conv's
-# load path, and lands on a kernel that already sits at 245 VGPRs), so it is opt-in: MSML_BNBWD_IN=1.
-BNBWD_IN = os.environ.get("MSML_BNBWD_IN") is not None
-BNBWD_IN_MIN_C = int(os.environ.get("MSML_BNBWD_IN_MIN_C", "256"))
-_BNBWD_IN_OK = {}
-
-
-def bnbwd_in_applies(n, h, w, c_dy, c_dx, r, s, stride, pad):
-    key = (n, h, w, c_dy, c_dx, r, s, stride, pad)
-    ok = _BNBWD_IN_OK.get(key)
-    if ok is None:
-        ok = bool(BNBWD_IN and ACC_STATS and FUSE_BN_BWD and c_dy >= BNBWD_IN_MIN_C and r == 3 and s == 3 and stride == 1
-                  and pad == 1 and _lib.value("msml_conv2d_bnbwd_in_acc_applies", c_dy, c_dx, n, h, w, h, w, 3, 3, 1, 1, 1))
-        _BNBWD_IN_OK[key] = ok
-    return ok
-
-
-def conv_dgrad_bnbwd_in(dy, up_x, up_coef, up_alpha, up_acc, tg, accumulate, wp, coutp, bn_x, coef, alpha, real=None):
-    """BatchNorm backward (upper BatchNorm: saved input up_x, coef[4][C], sums up_acc, parameter-gradient targets tg =
-    (dgamma, dbeta, dalpha)) -> 3x3 / stride-1 backward-data conv -> sums of the lower BatchNorm (bn_x, coef, alpha) in
-    one launch.  Returns (dc = the upper BatchNorm's input gradient, dx of the conv, accumulator of the lower sums)."""
-    n, h, w, c0p = dy.shape
-    dc = torch.empty_like(dy)
-    out = torch.empty(n, h, w, coutp, dtype=torch.bfloat16, device=dy.device)
-    acc = stats_acc(coutp, dy.device, 3)
-    cin, cout = real if real is not None else (c0p, coutp)
-    name = "conv_igemm"
-    if PROFILE.on:
-        name = conv_label("T+bnb+bn", c0p, 0, coutp, n, h, w, h, w, 3, 3, 1, 1, 1, 1, BF16, BF16, False)
-    with PROFILE.rec(name, 2.0 * n * h * w * cin * cout * 9):
-        call("msml_conv2d_bnbwd_in_acc", dy, c0p, up_x, up_coef[0], up_coef[1], up_alpha, up_coef[2], up_coef[3], up_acc,
-             tg[0], tg[1], tg[2], int(accumulate), dc, wp, wp.shape[0], out, coutp, n, h, w, h, w, 3, 3, 1, 1, 1,
-             bn_x, coef[0], coef[1], alpha, coef[2], coef[3], acc)
-    return dc, out, acc
 
 
 def conv2d_bnin(x, coef, alpha, wp, coutp, real=None):
@@ -510,15 +463,6 @@ FUSE_BN_BWD = os.environ.get("MSML_NO_FUSE_BN_BWD") is None
 BLOCK_C_ENTRY = os.environ.get("MSML_BLOCK_C_ENTRY") is not None
 # The stem's BatchNorm + PReLU pass also emits the statistics of its output for layer1's first bn1 (no bn_stats pass)
 EMIT_STEM_STATS = os.environ.get("MSML_NO_EMIT_STEM_STATS") is None
-# ... and in the backward the first block's bn1 apply kernel CAN reduce the stem BatchNorm's three sums while it writes that
-# BatchNorm's output gradient (msml_bn_fin_bwd_apply_next_act, round 6: the stem's own backward is then an apply pass, 3 streams
-# instead of 5).  Measured, interleaved on one box (20 steps each, one-stream event pass): BatchNorm family 7.575 / 7.635 ms
-# without, 7.644 ms with -- the stem's reduce + apply leaves `bn_act_bwd` (1.76 -> 1.39 ms) and comes back in `bn_act_bwd_apply`
-# (3.04 -> 3.48): the 112 x 112 apply kernel with the compact stride-2 add, the NEXT sums AND the PReLU mask is no longer
-# byte-bound (it ran at 6.8 TB/s before).  Step 29.49 / 30.71 without, 29.90 / 30.68 with.  Opt-in: MSML_STEM_BWD_SUMS=1
-# on an experiment build.
-# (the kernel variant is instantiated in experiment builds only: tools/build_variant.py --all MSML_EXPERIMENTS)
-STEM_BWD_SUMS = bool(os.environ.get("MSML_STEM_BWD_SUMS")) and bool(_lib.value("msml_has_experiments"))
 # FMCnn: the two gradients of the stage input (same_conv path + act / arith / skip path) summed in same_conv's backward-data
 # epilogue instead of by autograd's fan-out add
 FM_TEE = os.environ.get("MSML_NO_FM_TEE") is None

@@ -10,16 +10,6 @@ from msml_amd import _lib, ops
 pytestmark = pytest.mark.gpu
 
 
-def _experiments():
-    """The measured-slower kernel variants are compiled into experiment builds only
-    (tools/build_variant.py --all MSML_EXPERIMENTS, selected with MSML_LIB; tools/experiments_run.sh runs their tests)."""
-    return bool(_lib.value("msml_has_experiments"))
-
-
-def needs_experiments():
-    if not _experiments():
-        pytest.skip("kernel variant of an experiment build (tools/experiments_run.sh; profiles/r06_experiments_variant.log)")
-
 # (Cin1, Cin2, Cout, H, R, S, stride, pad_h, pad_w, bias)
 SHAPES = [
     (3, 0, 64, 28, 3, 3, 1, 1, 1, False),      # FRB stem (C=3 padded to 8)
@@ -476,8 +466,6 @@ def test_conv_wgrad_group(shape, group):
 # (msml_conv2d_bnin / msml_conv_wgrad_bnin): must equal msml_bn_act_fwd -> msml_conv2d / msml_conv_wgrad
 # bit for bit (same rounding of the normalised activation, same MFMA order)
 BNIN = [
-    (22, 64, 64, 56, 56),        # weights-stationary kernel, more tiles than one pass (it needs
-    (60, 64, 64, 28, 40),        # ... ragged tile column     >= as many statistics rows as workgroups)
     (9, 128, 128, 28, 28),       # halo kernel, 128 output channels, two slabs
     (6, 128, 256, 28, 28),       # halo kernel, 256 output channels
     (7, 256, 256, 14, 14),       # four slabs: the image double buffer wraps twice
@@ -485,12 +473,11 @@ BNIN = [
 ]
 
 
+# (the ids keep the numbers these shapes had behind the two removed 64-channel cases: shape2 ... shape5)
 @pytest.mark.parametrize("with_alpha", [False, True])
-@pytest.mark.parametrize("shape", BNIN)
+@pytest.mark.parametrize("shape", BNIN, ids=["shape%d" % i for i in range(2, 2 + len(BNIN))])
 def test_conv_bn_in_lds_matches_unfused(shape, with_alpha):
     n, cin, cout, h, w_ = shape
-    if cin == 64:                # (the weights-stationary kernel takes an input transform in experiment builds only)
-        needs_experiments()
     g = torch.Generator().manual_seed(sum(shape) + int(with_alpha))
     x = ops.to_nhwc(torch.randn(n, cin, h, w_, generator=g).cuda(), _lib.BF16)
     w = (torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (cin * 9)) ** 0.5).cuda()
@@ -806,17 +793,13 @@ def test_conv_small_map_tiles(shape):
                                    # the persistent 128-channel tile (round 6): two and more rounds of tiles, ragged tile column
                                    # and row, 256 input channels (four slabs per tile)
                                    (128, 128, 128, 28, 28), (150, 128, 128, 27, 26), (131, 256, 128, 28, 28), (37, 128, 128, 56, 56),
-                                   (33, 64, 128, 56, 56),          # ... and its one-slab shape (conv1 of a stage's first block)
-                                   # the weights-stationary 64-channel kernel (round 5): more tiles than CUs, ragged tile column, 112 x 112
-                                   (24, 64, 64, 56, 56), (60, 64, 64, 28, 40), (6, 64, 64, 112, 112)])
+                                   (33, 64, 128, 56, 56)])         # ... and its one-slab shape (conv1 of a stage's first block)
 def test_conv_bn_from_accumulator_in_the_prologue(shape, with_alpha):
     """msml_conv2d_bnin_acc: training-mode BatchNorm (+ PReLU) -> 3x3 conv in ONE launch (coefficients derived from the
     producer's f64 accumulator in the kernel prologue, normalised tile applied in LDS and written through, running
     statistics updated by one workgroup) against msml_bn_fin_act_fwd + msml_conv2d_acc: activation, conv output, saved
     coefficients and running statistics bit for bit, output statistics to the order of the f64 adds."""
     n, cin, cout, h, w_ = shape
-    if cin == 64 and cout == 64:  # (k_conv_ws's prologue transform: measured slower, experiment builds only)
-        needs_experiments()
     g = torch.Generator().manual_seed(sum(shape) + int(with_alpha))
     x = ops.to_nhwc((torch.randn(n, cin, h, w_, generator=g) * 1.7 + 0.3).cuda(), _lib.BF16)
     w = (torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (cin * 9)) ** 0.5).cuda()
@@ -828,7 +811,7 @@ def test_conv_bn_from_accumulator_in_the_prologue(shape, with_alpha):
     tiles = n * ((h + 13) // 14) * ((w_ + 13) // 14)
     persistent = cout == 128 and tiles >= 512                         # (>= two rounds on 256 CUs: k_conv_halo_p)
     assert _lib.value("msml_conv2d_bnin_acc_applies", cin, cout, n, h, w_, h, w_, 3, 3, 1, 1, 1) == \
-        (3 if persistent else (2 if cin == 64 else 1))
+        (3 if persistent else 1)
 
     def stats_of_x():
         acc = ops.stats_acc(cin, x.device)
@@ -850,57 +833,8 @@ def test_conv_bn_from_accumulator_in_the_prologue(shape, with_alpha):
     assert torch.equal(y_b, y_a)
     assert torch.equal(coef_b, coef_a)
     assert torch.equal(rm_b, rm_a) and torch.equal(rv_b, rv_a)
-    # (64 channels: the two-launch side's conv runs on k_conv_s2r, the fused one on k_conv_ws -- identical outputs, but the
-    # f32 per-workgroup partial sums of the statistics are cut differently before they meet in f64)
     sa, sb = st_a.sum(0), st_b.sum(0)
-    assert torch.allclose(sb, sa, rtol=1e-12, atol=0) if (cin != 64 or persistent) else \
-        torch.allclose(sb, sa, rtol=1e-6, atol=1e-6 * sa.abs().max().item())
-
-
-@pytest.mark.parametrize("with_alpha", [False, True])
-@pytest.mark.parametrize("shape", [(7, 256, 256, 14, 14), (4, 256, 128, 13, 27), (3, 512, 256, 14, 14), (5, 256, 512, 14, 14),
-                                   (9, 128, 128, 28, 28)])
-def test_conv_dgrad_bn_backward_in_the_prologue(shape, with_alpha):
-    """msml_conv2d_bnbwd_in_acc: BatchNorm backward (sums from the producer's accumulator) -> 3x3 backward-data conv ->
-    sums of the next BatchNorm backward in ONE launch, against msml_bn_fin_bwd_apply + msml_conv2d_bnbwd_acc: the
-    BatchNorm's input gradient (written through), the conv's input gradient and the parameter gradients bit for bit,
-    the lower sums to the order of the f64 adds."""
-    needs_experiments()                   # (measured slower than the two launches: the XB instantiations are not shipped)
-    n, cdy, cdx, h, w_ = shape            # dy has cdy channels (the conv's output side), dx cdx
-    g = torch.Generator().manual_seed(sum(shape) + int(with_alpha))
-    rnd = lambda *s: torch.randn(*s, generator=g)       # noqa: E731
-    dy = ops.to_nhwc(rnd(n, cdy, h, w_).cuda(), _lib.BF16)
-    up_x = ops.to_nhwc((rnd(n, cdy, h, w_) * 1.3 + 0.2).cuda(), _lib.BF16)
-    up_coef = torch.stack([torch.rand(cdy, generator=g) + 0.5, rnd(cdy) * 0.3, rnd(cdy) * 0.2,
-                           torch.rand(cdy, generator=g) + 0.5]).cuda()
-    up_alpha = (torch.rand(cdy, generator=g) * 0.3).cuda() if with_alpha else None
-    m = n * h * w_
-    up_acc = (torch.randn(8, 3, cdy, generator=g, dtype=torch.float64) * (m ** 0.5) / 8).cuda()
-    w = (rnd(cdy, cdx, 3, 3) * (2.0 / (cdx * 9)) ** 0.5).cuda()
-    wp = ops.pack_weight(w, True, cdy, 0, _lib.BF16)
-    bn_x = ops.to_nhwc(rnd(n, cdx, h, w_).cuda(), _lib.BF16)
-    coef = torch.stack([torch.rand(cdx, generator=g) + 0.5, rnd(cdx) * 0.3, rnd(cdx) * 0.2,
-                        torch.rand(cdx, generator=g) + 0.5]).cuda()
-    alpha = (torch.rand(cdx, generator=g) * 0.3).cuda()
-    assert _lib.value("msml_conv2d_bnbwd_in_acc_applies", cdy, cdx, n, h, w_, h, w_, 3, 3, 1, 1, 1) == 1
-    # two launches
-    pg_a = [torch.full((cdy,), 0.25, device="cuda") for _ in range(3)]
-    dc_a = torch.empty_like(dy)
-    _lib.call("msml_bn_fin_bwd_apply", dy, up_x, up_coef[0], up_coef[1], up_alpha, up_coef[2], up_coef[3], up_acc, None,
-              None, 0, 0, dc_a, None, pg_a[0], pg_a[1], pg_a[2] if with_alpha else None, 1, m, cdy, None, None, None, None,
-              _lib.BF16)
-    dx_a, acc_a = ops.conv_dgrad_bnbwd(dc_a, wp, cdx, 3, 3, 1, 1, 1, h, w_, bn_x, coef, alpha)
-    # one launch
-    pg_b = [torch.full((cdy,), 0.25, device="cuda") for _ in range(3)]
-    dc_b, dx_b, acc_b = ops.conv_dgrad_bnbwd_in(dy, up_x, up_coef, up_alpha, up_acc,
-                                                (pg_b[0], pg_b[1], pg_b[2] if with_alpha else None), True, wp, cdx, bn_x,
-                                                coef, alpha)
-    torch.cuda.synchronize()
-    assert torch.equal(dc_b, dc_a)
-    assert torch.equal(dx_b, dx_a)
-    for a, b in zip(pg_a[:3 if with_alpha else 2], pg_b):
-        assert torch.equal(a, b)
-    assert acc_a.dtype == torch.float64 and torch.allclose(acc_b.sum(0), acc_a.sum(0), rtol=1e-11, atol=1e-9)
+    assert torch.allclose(sb, sa, rtol=1e-12, atol=0)
 
 
 # Pointwise kernel (conv_pw.hip): 1x1 / stride-1 layers of the FM bottlenecks and the im2col'd stems -- every mode against
@@ -1154,28 +1088,6 @@ def test_conv_s2r_64_channel_stride2(shape):
         xh = (xf - coef[2]) * coef[3]
         want = torch.stack((gg.sum(0), (gg * xh).sum(0), torch.where(neg, gq * z, torch.zeros_like(z)).sum(0))).double()
         assert torch.allclose(acc.sum(0), want, rtol=2e-3, atol=2e-3 * want.abs().max().item())
-
-
-# stride-2 weight gradients on the strip kernel (k_wgrad_halo<64, S2>: the X strip as four parity planes): (N, Cin, Cout, H)
-# with H the conv INPUT size; more strips than splits, ragged strips (26 -> 13), the 256-channel layer (16 dW tiles)
-@pytest.mark.parametrize("accumulate", [False, True])
-@pytest.mark.parametrize("shape", [(6, 64, 64, 56), (3, 64, 64, 112), (9, 128, 128, 28), (4, 64, 128, 26), (5, 256, 256, 28)])
-def test_conv_wgrad_stride2_on_the_strip_kernel(shape, accumulate, monkeypatch):
-    needs_experiments()
-    monkeypatch.setenv("MSML_HALO_WGRAD_S2", "1")         # (opt-in: measured not faster than the im2col kernel)
-    n, cin, cout, h = shape
-    g = torch.Generator().manual_seed(sum(shape))
-    x = torch.randn(n, cin, h, h, generator=g).bfloat16().float()
-    ho = h // 2
-    dy = torch.randn(n, cout, ho, ho, generator=g).bfloat16().float()
-    w = torch.zeros(cout, cin, 3, 3, dtype=torch.double, requires_grad=True)
-    F.conv2d(x.double(), w, None, 2, 1).backward(dy.double())
-    ref = w.grad.float()
-    dw = torch.full((cout, cin, 3, 3), 2.0, device="cuda")
-    ops.conv_wgrad(ops.to_nhwc(dy.cuda(), _lib.BF16), ops.to_nhwc(x.cuda(), _lib.BF16), dw, cout, cin, cin, 0,
-                   3, 3, 2, 1, 1, accumulate=accumulate)
-    want = ref + (2.0 if accumulate else 0.0)
-    assert (dw.cpu() - want).abs().max().item() <= 1.5e-2 * ref.abs().max().item()
 
 
 # conv_s2r.hip, k_conv_s2r_x3: split-bf16 (config 5) 64 -> 64 channel 3x3 / stride-1 layers with both weight planes in
@@ -1490,50 +1402,3 @@ def test_stem_im2col_through_lds_is_the_gather(shape, dtype, monkeypatch):
     cols = F.unfold(x, 3, padding=1, stride=stride).view(n, 3, 9, -1).permute(0, 3, 2, 1).reshape(n, got.shape[1], got.shape[2], 27)
     want = cols.bfloat16().float() if dtype == "bf16" else cols
     assert torch.equal(got[..., :27].float(), want) and float(got[..., 27:].float().abs().max()) == 0.0
-
-
-# msml_bn_fin_bwd_apply_next_act (round 6): the apply pass that writes dx ALSO reduces the three backward sums of the BatchNorm
-# + PReLU that produced its input tensor (a stem in front of the first IBasicBlock): (M pixels, C, stride-2 compact add)
-@pytest.mark.parametrize("s2", [False, True])
-@pytest.mark.parametrize("shape", [(2 * 56 * 56, 64), (3 * 28 * 28, 64), (5 * 14 * 14, 128)])
-def test_bn_backward_apply_reduces_the_sums_of_a_stem_in_front_of_it(shape, s2):
-    needs_experiments()                   # (measured not faster, msml_amd/ops.py STEM_BWD_SUMS: not in the shipped library)
-    m, c = shape
-    n = {2 * 56 * 56: 2, 3 * 28 * 28: 3, 5 * 14 * 14: 5}[m]
-    h = int(round((m // n) ** 0.5))
-    g = torch.Generator().manual_seed(m + c + int(s2))
-    rnd = lambda *s: torch.randn(*s, generator=g)       # noqa: E731
-    dy = rnd(m, c).cuda().bfloat16()
-    x = (rnd(m, c) * 1.3 + 0.2).cuda().bfloat16()                          # input of THIS BatchNorm = output of the stem's PReLU
-    coef = torch.stack([torch.rand(c, generator=g) + 0.5, rnd(c) * 0.3, rnd(c) * 0.2, torch.rand(c, generator=g) + 0.5]).cuda()
-    acc = (torch.randn(8, 3, c, generator=g, dtype=torch.float64) * (m ** 0.5) / 8).cuda()
-    nx = (rnd(m, c) * 0.9 - 0.1).cuda().bfloat16()                         # saved input of the stem's BatchNorm
-    ncoef = torch.stack([torch.rand(c, generator=g) + 0.5, rnd(c) * 0.4, rnd(c) * 0.2, torch.rand(c, generator=g) + 0.5]).cuda()
-    nalpha = (torch.rand(c, generator=g) * 0.4).cuda()
-    add = None
-    ah = aw = 0
-    if s2:                       # the compact gradient of a 1x1 / stride-2 downsample joins at the even pixels
-        add = rnd(n * (h // 2) * (h // 2), c).cuda().bfloat16()
-        ah = aw = h
-
-    def run(fn, *extra):
-        dx = torch.empty_like(x)
-        pg = torch.zeros(3, c, device="cuda")
-        nacc = torch.zeros(8, 3, c, dtype=torch.float64, device="cuda")
-        _lib.call(fn, dy, x, coef[0], coef[1], None, coef[2], coef[3], acc, None, add, ah, aw, dx, None, pg[0], pg[1], None, 0,
-                  m, c, nx, *extra, nacc, _lib.BF16)
-        torch.cuda.synchronize()
-        return dx, pg, nacc
-    dx_a, pg_a, nacc_a = run("msml_bn_fin_bwd_apply", ncoef[2], ncoef[3])                                      # activation-free NEXT
-    dx_b, pg_b, nacc_b = run("msml_bn_fin_bwd_apply_next_act", ncoef[0], ncoef[1], nalpha, ncoef[2], ncoef[3])
-    assert torch.equal(dx_a, dx_b) and torch.equal(pg_a, pg_b)             # the apply itself is the same arithmetic
-    # the three sums through the PReLU mask, from the dx the kernel wrote, in f64
-    gq, xn = dx_b.double(), nx.double()
-    z = nx.float() * ncoef[0] + ncoef[1]
-    neg = z <= 0
-    gp = torch.where(neg, gq * nalpha.double(), gq)
-    xh = (nx.float() - ncoef[2]) * ncoef[3]
-    want = torch.stack((gp.sum(0), (gp * xh.double()).sum(0), torch.where(neg, gq * z.double(), torch.zeros_like(gq)).sum(0)))
-    got = nacc_b.sum(0)
-    assert torch.allclose(got, want, rtol=2e-3, atol=2e-3 * want.abs().max().item()), (got - want).abs().max()
-    assert float(nacc_a[:, 2].abs().max()) == 0.0 and float(nacc_b[:, 2].abs().max()) > 0.0
