@@ -611,6 +611,50 @@ int msml_pool2_fwd(const void* x, void* y, int N, int H, int W, int cp, int dtyp
  * position if the window holds one), recomputed from x. */
 int msml_pool2_bwd(const void* dy, const void* x, void* dx, int N, int H, int W, int cp, int dtype, void* stream);
 
+/* ---------------------------------------------------------------- template (IJB-B / IJB-C) verification ------
+ * Device side of eval/qeval_ijbc.py and of Verification.start_verification (eval/qeval_mxnet.py:422-483).
+ * All sums in f64 in a fixed order, no floating-point atomics: two runs give the same bits.
+ *
+ * msml_template_pool: image2template_feature (eval/qeval_ijbc.py:303-337) with the flip sum and detector-score
+ *   weighting of get_template_features (eval/qeval_ijbc.py:484-502) folded in.  feats [n_rows][ld] f32, the first E
+ *   columns the embedding, columns E..2E the embedding of the flipped image when flip != 0; faceness [n_rows] f32
+ *   or NULL.  order [n_rows]: image rows sorted by (template id, media id, row); media_start [n_media + 1]:
+ *   positions in `order`; tmpl_media_start [n_templates + 1]: media indices; launch [n_templates]: the template
+ *   each workgroup pools (any permutation; the host lists the largest templates first).  out [n_templates][E] f64,
+ *   template rows in ascending id order: sum over the template's medias of the mean of (orig + flip) * faceness
+ *   over the media's rows, L2-normalised by sklearn's rule (a zero row stays zero).  E a multiple of 4. */
+int msml_template_pool(const float* feats, long n_rows, long ld, int E, int flip, const float* faceness,
+                       const int* order, const int* media_start, const int* tmpl_media_start, const int* launch,
+                       int n_templates, double* out, void* stream);
+/* verification (eval/qeval_ijbc.py:343-369): score[i] = <tn[r1[i]], tn[r2[i]]> in f64; r1 / r2 are ROW indices (the
+ * host maps template ids to rows, template2id of :350-352, and rejects unknown ids); a row index outside
+ * 0..n_templates-1 gives NaN, never a read outside tn.  E even. */
+int msml_template_pair_score(const double* tn, int n_templates, int E, const int* r1, const int* r2, long n_pairs,
+                             double* score, void* stream);
+/* roc_curve + TPR @ FPR table + auc (eval/qeval_ijbc.py:565-585; also roc_curve of eval/qeval_mxnet.py:433) on
+ * integer counts.  sorted: the scores in DESCENDING order, label: their 0/1 labels, n < 2^31.
+ *   msml_roc_block_counts: blk[msml_roc_blocks(n)][2] = {positives, ends of runs of equal scores} per block;
+ *   msml_roc_points: off = the exclusive scan of blk (done by the caller on that small table) -> tps[k], fps[k] of
+ *     the k-th distinct score (sklearn's _binary_clf_curve), k < n_points = the total of run ends;
+ *   msml_roc_reduce: keep[k] = 1 where drop_intermediate=True keeps the point; part[msml_roc_reduce_blocks(n_points)]
+ *     [2 + 2 * n_targets] 64-bit words per block: points kept, twice the trapezoid area under the block's segments
+ *     in count units (exact), and per target FPR the bits of the smallest |fps / fps[last] - target| over the kept
+ *     points with its k (ties: the larger k, min(zip(diff, index)) after flipud, :582-583).  n_targets <= 16. */
+int msml_roc_blocks(int n);
+int msml_roc_block_counts(const double* sorted, const unsigned char* label, int n, int* blk, void* stream);
+int msml_roc_points(const double* sorted, const unsigned char* label, int n, const int* off, int* tps, int* fps,
+                    void* stream);
+int msml_roc_reduce_blocks(int n_points);
+int msml_roc_reduce(const int* tps, const int* fps, int n_points, const double* target, int n_targets,
+                    unsigned char* keep, unsigned long long* part, void* stream);
+/* cdist(a, b, 'cosine') of the sklearn-normalised rows 2i, 2i + 1 (eval/qeval_mxnet.py:419,426-430): dist[i] =
+ * 1 - a.b / (|a||b|) in f64, |cos| clipped to 1 as scipy does.  emb [2 * n_pairs][E], NOT normalised. */
+int msml_pair_cosdist(const float* emb, int n_pairs, int E, double* dist, void* stream);
+int msml_pair_cosdist_f64(const double* emb, int n_pairs, int E, double* dist, void* stream);
+/* The counting loops of eval/qeval_mxnet.py:461-478 as rank queries: out[j] = number of sorted[i] < q[j]
+ * (strict != 0) or <= q[j]; sorted ascending [n], q [m]. */
+int msml_rank_count(const double* sorted, int n, const double* q, int m, int strict, int* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

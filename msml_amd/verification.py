@@ -133,3 +133,66 @@ def evaluate(emb, issame, nrof_folds=10, far_target=1e-3):
         val[k] = float(np.sum(pred & issame[sl])) / float(np.sum(issame[sl]))
         far[k] = float(np.sum(pred & ~issame[sl])) / float(np.sum(~issame[sl]))
     return tpr, fpr, accuracy, float(np.mean(val)), float(np.std(val)), float(np.mean(far))
+
+
+@torch.no_grad()
+def pair_cosdist(emb):
+    """emb: (2 * n_pairs, E) f32 or f64 on the GPU, NOT normalised -> (n_pairs,) f64 cosine DISTANCES of rows 2i,
+    2i + 1: sklearn.preprocessing.normalize then scipy's cdist(..., metric='cosine') (qeval_mxnet.py:419,426-430)."""
+    f64 = emb.dtype == torch.float64
+    emb = emb.contiguous() if f64 else emb.float().contiguous()
+    n2, e = emb.shape
+    assert n2 % 2 == 0 and emb.is_cuda
+    dist = torch.empty(n2 // 2, dtype=torch.float64, device=emb.device)
+    call("msml_pair_cosdist_f64" if f64 else "msml_pair_cosdist", emb, n2 // 2, e, dist)
+    return dist
+
+
+def _rank(sorted_asc, queries, strict):
+    out = torch.empty(queries.numel(), dtype=torch.int32, device=queries.device)
+    call("msml_rank_count", sorted_asc, sorted_asc.numel(), queries, queries.numel(), 1 if strict else 0, out)
+    return out.cpu().numpy().astype(np.int64)
+
+
+@torch.no_grad()
+def roc_accuracy_tarfar(emb, issame):
+    """`Verification.start_verification` of the reference (eval/qeval_mxnet.py:422-483), which test.py prints for
+    every occlusion level: returns (acc, tarfar[5]).
+
+    emb: (2 * n_pairs, E) embeddings on the GPU (rows 2i, 2i + 1 form pair i), issame: n_pairs booleans.  The
+    reference's own conventions are kept:
+    * its label is 0 for a SAME pair and 1 for a different one (qeval_mxnet.py:550-551), and roc_curve runs on the
+      cosine DISTANCE with label 1 as the positive class; acc = tpr[argmin |tpr - (1 - fpr)|] over the points
+      roc_curve keeps, the first minimum;
+    * neg_cnt = pos_cnt = n_pairs // 2 whatever the real counts are, and the loops index the first n_pairs // 2
+      entries of each list, so the reference raises unless both lists are at least that long.  Precondition here:
+      exactly as many same as different pairs (n_pairs even); ValueError otherwise;
+    * tarfar[k] for FAR <= 1e-1 .. 1e-4: thresholds are the different-pair distances T with
+      #(different < T) / neg_cnt <= FAR (strict <), the value is the largest #(same <= T) / pos_cnt (<=);
+      the fifth entry (1e-5) stays 0.
+    The two O(n^2) Python loops are two rank queries on the sorted distances (msml_rank_count)."""
+    from . import ijb
+    issame = np.asarray(issame).astype(bool).reshape(-1)
+    dist = pair_cosdist(emb)
+    n = dist.numel()
+    if len(issame) != n:
+        raise ValueError("roc_accuracy_tarfar: %d pairs but %d labels" % (n, len(issame)))
+    cnt = n // 2
+    if n % 2 or int(issame.sum()) != cnt:
+        raise ValueError("roc_accuracy_tarfar: the reference needs as many same as different pairs "
+                         "(%d same, %d different)" % (int(issame.sum()), n - int(issame.sum())))
+    label = (~issame).astype(np.uint8)                                    # 0: same
+    r = ijb.roc_points(dist, label)
+    keep = r["keep"].bool()
+    fpr = np.r_[0, r["fps"][keep].cpu().numpy()] / r["n_neg"]
+    tpr = np.r_[0, r["tps"][keep].cpu().numpy()] / r["n_pos"]
+    acc = float(tpr[np.argmin(np.abs(tpr - (1 - fpr)))])
+    lab = torch.from_numpy(label).to(dist.device)
+    pos_sorted = torch.sort(dist[lab == 0])[0]
+    neg_sorted = torch.sort(dist[lab == 1])[0]
+    far = _rank(neg_sorted, neg_sorted, True) / cnt                       # ascending with the threshold
+    tarfar = np.zeros(5)
+    thr_idx = [int(np.flatnonzero(far <= fv)[-1]) for fv in (1e-1, 1e-2, 1e-3, 1e-4)]   # far[0] == 0 always qualifies
+    thr = neg_sorted[torch.tensor(thr_idx, device=dist.device)].contiguous()
+    tarfar[:4] = _rank(pos_sorted, thr, False) / cnt
+    return acc, tarfar
