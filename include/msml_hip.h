@@ -196,7 +196,11 @@ int msml_conv_wgrad_kernel_is_n32(int up, int vp, int N, int H, int W, int P, in
  * msml_bn_act_bwd (training statistics): dx, dgamma, dbeta, dalpha from dy and the saved x;
  *   residual_first (the saved residual, only for res_first == 1) and dres (gradient flowing
  *   to that residual) optional; accumulate != 0 adds the parameter gradients into dgamma / dbeta /
- *   dalpha (the flat gradient arena) instead of overwriting; workspace >= rows*3*C + 2*C floats. */
+ *   dalpha (the flat gradient arena) instead of overwriting; workspace >= rows*3*C + 2*C floats.
+ * The apply loops keep a thread's per-channel coefficients in registers: msml_bn_act_fwd_stats and msml_bn_act_bwd
+ *   (C <= 2048) need C / 8 to divide 256, msml_bn_act_fwd needs C / 8 to divide 256 or be a multiple of it;
+ *   MSML_ERR_UNSUPPORTED otherwise.  msml_bn_stats takes any C % 8 == 0 up to 2048, msml_bias_grad any Cp % 8 == 0 up to 2048,
+ *   msml_bn_finalize any C > 0. */
 int msml_bn_stats_rows(long M, int C);
 int msml_bn_stats(const void* x, long M, int C, float* partial, int dtype, void* stream);
 int msml_bn_finalize(const float* partial, int rows, int C, double count, const float* gamma,
@@ -227,7 +231,8 @@ int msml_bn_stats_acc(const void* x, long M, int C, double* acc, int dtype, void
  * the producer): msml_conv2d_bnbwd_acc is msml_conv2d_bnbwd with that output; msml_bn_fin_bwd_apply is
  * k_bn_bwd_finalize + msml_bn_act_bwd_apply[_next][_s2] in one launch (add_h > 0: compact stride-2 `add`; next_acc:
  * zero-initialised accumulator of the activation-free BatchNorm whose output gradient dx is); msml_bn_act_bwd_acc is
- * msml_bn_act_bwd with its reduce pass adding into `acc`.  C / 8 must divide 256. */
+ * msml_bn_act_bwd with its reduce pass adding into `acc`.  C / 8 must divide 256: MSML_ERR_UNSUPPORTED otherwise
+ * (msml_bn_act_bwd_acc refuses before its reduce launch, `acc` stays untouched). */
 int msml_conv2d_bnbwd_acc(const void* in0, int c0p, const void* wp, int kop, void* out, int coutp, int N,
                           int H, int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w,
                           int transposed, const void* bn_x, const float* bn_scale, const float* bn_shift,
@@ -470,7 +475,8 @@ int msml_deconv4_bwd_data(const void* dy, const void* wp0, const void* wp1, void
  * fall back to msml_conv2d + msml_bn_act_bwd).  partial needs msml_conv2d_bnbwd_rows() rows;
  * *rows_used = rows written (all of them fully).  msml_bn_act_bwd_apply finishes the job:
  * finalize over `rows` + dx = gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)) [+ add];
- * coef_ws: 98*C floats of scratch (2*C coefficients + 32 folded partial rows). */
+ * coef_ws: 98*C floats of scratch (2*C coefficients + 32 folded partial rows).  msml_bn_act_bwd_apply and its
+ * _next / _s2 / _next_s2 forms need C / 8 to divide 256 (MSML_ERR_UNSUPPORTED otherwise, before any launch). */
 int msml_conv2d_bnbwd_rows(int coutp, int N, int P, int Q);
 int msml_conv2d_bnbwd(const void* in0, int c0p, const void* wp, int kop, void* out, int coutp,
                       int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,

@@ -673,6 +673,8 @@ extern "C" int msml_bn_act_bwd(const void* dy, const void* x, const float* scale
   MSML_CHECK(dy && x && dx && scale && shift && save_mean && save_invstd && workspace && M > 0 &&
                  C > 0 && C % 8 == 0 && C <= 2048,
              MSML_ERR_SHAPE, "bn_act_bwd: bad args M=%ld C=%d", M, C);
+  // the apply loop keeps a thread's coefficients in registers: needs (threads in grid) % (C/8) == 0, see ew_grid_c
+  MSML_CHECK(256 % (C / 8) == 0, MSML_ERR_UNSUPPORTED, "bn_act_bwd: C/8 = %d must divide 256", C / 8);
   int rows = red_rows(M, C);
   long need = (long)rows * 3 * C + 2 * C;
   MSML_CHECK(ws_floats >= need, MSML_ERR_WORKSPACE, "bn_act_bwd: workspace %ld < %ld floats", ws_floats, need);
@@ -854,6 +856,8 @@ extern "C" int msml_bn_act_bwd_acc(const void* dy, const void* x, const float* s
                                    void* stream) {
   MSML_CHECK(dy && x && dx && scale && shift && save_mean && save_invstd && acc && M > 0 && C > 0 && C % 8 == 0 &&
                  C <= 2048, MSML_ERR_SHAPE, "bn_act_bwd_acc: bad args M=%ld C=%d", M, C);
+  // refused before the reduce launch: msml_bn_fin_bwd_apply would refuse after it, with `acc` already written
+  MSML_CHECK(256 % (C / 8) == 0, MSML_ERR_UNSUPPORTED, "bn_act_bwd_acc: C/8 = %d must divide 256", C / 8);
   const int rows = red_rows(M, C);
   hipStream_t st = (hipStream_t)stream;
   MSML_DISPATCH_DTYPE(
@@ -884,6 +888,7 @@ static int bn_bwd_apply_impl(const void* dy, const void* x, const float* scale, 
   MSML_CHECK(dy && x && dx && scale && shift && save_mean && save_invstd && partial && coef_ws && rows > 0 &&
                  M > 0 && C > 0 && C % 8 == 0 && C <= 2048,
              MSML_ERR_SHAPE, "bn_act_bwd_apply: bad args M=%ld C=%d rows=%d", M, C, rows);
+  MSML_CHECK(256 % (C / 8) == 0, MSML_ERR_UNSUPPORTED, "bn_act_bwd_apply: C/8 = %d must divide 256", C / 8);
   const bool s2 = add_h > 0;
   MSML_CHECK(!s2 || (add && add_w > 0 && M % ((long)add_h * add_w) == 0 && M < (1L << 24)), MSML_ERR_SHAPE,
              "bn_act_bwd_apply: stride-2 add needs M = N*H*W < 2^24 (M=%ld H=%d W=%d)", M, add_h, add_w);
@@ -1002,7 +1007,8 @@ __global__ void __launch_bounds__(1024) k_colsum_finalize(const float* __restric
 
 extern "C" int msml_bias_grad(const void* dy, long M, int Cp, int Creal, float* db, int accumulate,
                               float* workspace, long ws_floats, int dtype, void* stream) {
-  MSML_CHECK(dy && db && workspace && M > 0 && Cp > 0 && Cp % 8 == 0 && Creal <= Cp, MSML_ERR_SHAPE,
+  // Cp <= 2048: slab_reduce covers at most 256 eight-channel chunks per workgroup (as msml_bn_stats)
+  MSML_CHECK(dy && db && workspace && M > 0 && Cp > 0 && Cp % 8 == 0 && Cp <= 2048 && Creal <= Cp, MSML_ERR_SHAPE,
              "bias_grad: bad args");
   int rows = red_rows(M, Cp);
   MSML_CHECK(ws_floats >= (long)rows * 2 * Cp, MSML_ERR_WORKSPACE, "bias_grad: workspace too small");

@@ -26,6 +26,52 @@ def test_status_codes_without_gpu():
     rc = lib.msml_fm_fuse_fwd(None, None, None, 7, 0, 0, 0, None)   # n not a multiple of 8
     assert rc == -1
     assert b"multiple of 8" in lib.msml_last_error()
+    _bn_refusals_without_gpu()
+
+
+def _bn_refusals_without_gpu():
+    """The BatchNorm entry points with an apply loop keep a thread's coefficients in registers, which needs C / 8 to
+    divide 256: every one of them refuses other channel counts with MSML_ERR_UNSUPPORTED before any launch (the check sits
+    behind the null-pointer check, so it is reached with the address of a host buffer, which a refusing call never
+    dereferences), and the other host-side refusals of bn.hip."""
+    import ctypes
+    lib = _lib.load()
+    buf = (ctypes.c_double * 64)()
+    p = ctypes.addressof(buf)
+    co = (p, p, p, p, p)                      # scale, shift, alpha, save_mean, save_invstd
+    M, F32 = 64, _lib.F32
+    for C in (24, 96, 192, 320):
+        calls = [
+            lib.msml_bn_act_fwd(p, p, p, p, None, 0, p, M, C, F32, None),
+            lib.msml_bn_act_fwd_stats(p, p, p, p, None, 0, p, M, C, p, F32, None),
+            lib.msml_bn_fin_act_fwd(p, 64.0, p, p, p, p, 0.1, 1e-5, p, p, p, p, p, p, None, 0, p, M, C, None, F32, None),
+            lib.msml_bn_act_bwd(p, p, *co, None, p, None, p, p, p, 0, M, C, p, 1 << 40, F32, None),
+            lib.msml_bn_act_bwd_acc(p, p, *co, None, None, p, None, p, p, p, 0, M, C, p, F32, None),
+            lib.msml_bn_act_bwd_apply(p, p, *co, p, 4, None, p, p, p, p, 0, M, C, p, F32, None),
+            lib.msml_bn_act_bwd_apply_s2(p, p, *co, p, 4, p, 2, 2, p, p, p, p, 0, M, C, p, F32, None),
+            lib.msml_bn_act_bwd_apply_next(p, p, *co, p, 4, None, p, p, p, p, 0, M, C, p, p, p, p, p, F32, None),
+            lib.msml_bn_act_bwd_apply_next_s2(p, p, *co, p, 4, p, 2, 2, p, p, p, p, 0, M, C, p, p, p, p, p, F32, None),
+            lib.msml_bn_fin_bwd_apply(p, p, *co, p, None, None, 0, 0, p, None, p, p, p, 0, M, C, None, None, None, None,
+                                      F32, None),
+        ]
+        assert calls == [_lib.UNSUPPORTED] * len(calls), (C, calls)
+        assert b"must divide 256" in lib.msml_last_error()
+    C = 64
+    # stride-2 `add`: M >= 2^24, M not a multiple of H * W; undersized workspaces; null pointers
+    assert lib.msml_bn_act_bwd_apply_s2(p, p, *co, p, 4, p, 2, 2, p, p, p, p, 0, 1 << 24, 8, p, F32, None) == -1
+    assert lib.msml_bn_act_bwd_apply_s2(p, p, *co, p, 4, p, 3, 3, p, p, p, p, 0, M, C, p, F32, None) == -1
+    assert lib.msml_bn_fin_bwd_apply(p, p, *co, p, None, p, 3, 3, p, None, p, p, p, 0, M, C, None, None, None, None,
+                                     F32, None) == -1
+    assert lib.msml_bn_act_bwd(p, p, *co, None, p, None, p, p, p, 0, M, C, p, 5 * C - 1, F32, None) == -5
+    assert lib.msml_bias_grad(p, M, C, C, p, 0, p, 2 * C - 1, F32, None) == -5
+    assert lib.msml_bias_grad(p, M, 4096, 4096, p, 0, p, 1 << 40, F32, None) == -1     # more than 256 chunks per workgroup
+    assert lib.msml_bn_fin_bwd_apply(p, p, *co, p, None, p, 2, 2, p, None, p, p, p, 0, 1 << 24, 8, None, None, None, None,
+                                     F32, None) == -1
+    assert lib.msml_bn_stats(None, M, C, p, F32, None) == -1
+    assert lib.msml_bn_stats_acc(p, M, C, None, F32, None) == -1
+    assert lib.msml_bn_act_bwd(p, p, *co, None, None, None, p, p, p, 0, M, C, p, 1 << 40, F32, None) == -1
+    assert lib.msml_bn_finalize(None, 0, C, 0.0, None, None, None, None, 0.1, 1e-5, p, p, None, None, None) == -1
+    assert lib.msml_add(p, p, p, 63, F32, None) == -1
 
 
 def test_fast_call_binding_covers_the_header():
