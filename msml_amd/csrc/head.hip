@@ -74,7 +74,8 @@ __global__ void __launch_bounds__(256) k_rownorm_fwd_v8(const float* __restrict_
 extern "C" int msml_rownorm_fwd(const float* w, int R, int Rp, int E, void* dst, int ld,
                                 float* inv_norm, int dtype, void* stream) {
   MSML_CHECK(w && dst && R > 0 && Rp >= R && E > 0 && ld >= E, MSML_ERR_SHAPE, "rownorm_fwd: bad args");
-  if (E % 512 == 0 && E <= 1024 && ld == E) {
+  // (16-B pieces: a misaligned w or dst, e.g. a view into a flat arena, takes the scalar kernel, as in msml_rownorm_bwd)
+  if (E % 512 == 0 && E <= 1024 && ld == E && ((size_t)w % 16) == 0 && ((size_t)dst % 16) == 0) {
     MSML_DISPATCH_DTYPE(dtype, "rownorm_fwd",
                         k_rownorm_fwd_v8<DT><<<cdiv(Rp, 4), 256, 0, (hipStream_t)stream>>>(w, R, Rp, E, (DT*)dst, inv_norm);)
     MSML_LAUNCH_OK("rownorm_fwd");
