@@ -291,18 +291,14 @@ __global__ void __launch_bounds__(WGM * WGN * 64, FUSE ? 2 : 1) k_conv_fast(cons
 #pragma unroll
         for (int j = 0; j < TN; j++) b[nb][j] = *reinterpret_cast<const u32x4*>(B + boff[kk + 1] + j * 4096);
       }
-#ifndef MSML_NO_SCHED_FENCE
       __builtin_amdgcn_sched_barrier(0);               // keep the reads of step kk + 1 ahead of these MFMAs
-#endif
 #pragma unroll
       for (int i = 0; i < TM; i++)
 #pragma unroll
         for (int j = 0; j < TN; j++)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
               __builtin_bit_cast(bf16x8, a[cb][i]), __builtin_bit_cast(bf16x8, b[cb][j]), acc[i][j], 0, 0, 0);
-#ifndef MSML_NO_SCHED_FENCE
       __builtin_amdgcn_sched_barrier(0);
-#endif
     }
   };
 
@@ -313,13 +309,9 @@ __global__ void __launch_bounds__(WGM * WGN * 64, FUSE ? 2 : 1) k_conv_fast(cons
     for (int st = st0; st < stages; st++) {
       if (st + 1 < stages) {
         advance(st);
-#ifndef MSML_ABLATE_LOADS
         gissue(st + 1, cur ^ 1);
-#endif
       }
-#ifndef MSML_ABLATE_COMPUTE
       compute(cur);
-#endif
       __syncthreads();
       cur ^= 1;
     }
@@ -349,9 +341,6 @@ __global__ void __launch_bounds__(WGM * WGN * 64, FUSE ? 2 : 1) k_conv_fast(cons
   // ---------------- epilogue (same contract as k_conv_igemm) -----------------------------------
   // bf16 results go through an LDS transpose tile [BM][BN + 8] and leave as 16-B row chunks;
   // f32 results (head logits) are stored directly.
-#ifdef MSML_ABLATE_EPILOGUE
-  if (p.M >= 0) return;
-#endif
   TOUT* outp = reinterpret_cast<TOUT*>(p.out) + (p.ksplits > 1 ? blockIdx.z * p.split_stride : 0);
   constexpr bool VIA_LDS = sizeof(TOUT) == 2;
   constexpr int OP = BN + 8;                           // tile pitch in elements
@@ -372,11 +361,7 @@ __global__ void __launch_bounds__(WGM * WGN * 64, FUSE ? 2 : 1) k_conv_fast(cons
     for (int k = 0; k < ITERS; k++) {
       const long m = m0 + (t + k * NT) / C8;
       oo[k] = (m < Mc && ccol < p.coutp) ? (unsigned int)(out_pixel(m) * p.coutp + ccol) : NO_CHUNK;
-#ifdef FAST_ABL_BNB_LOAD
-      xr[k] = u32x4{0, 0, 0, 0};
-#else
       xr[k] = oo[k] != NO_CHUNK ? *reinterpret_cast<const u32x4*>(p.bnb.x + oo[k]) : u32x4{0, 0, 0, 0};
-#endif
     }
   }
   float s1v[TN], s2v[TN];
@@ -430,10 +415,8 @@ __global__ void __launch_bounds__(WGM * WGN * 64, FUSE ? 2 : 1) k_conv_fast(cons
           const int row = (t + k * NT) / C8;
           u32x4 v = *reinterpret_cast<const u32x4*>(otile + row * OP + c8 * 8);
           *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(p.out) + oo[k]) = v;
-#ifndef FAST_ABL_BNB_ACC
           bnb_accum(bk, p.bnb.alpha != nullptr, load8<unsigned short>(reinterpret_cast<const unsigned short*>(&v)),
                     load8<unsigned short>(reinterpret_cast<const unsigned short*>(&xr[k])), bq);
-#endif
         }
       }
       // the NT / C8 threads that share a channel chunk meet in LDS; fixed-order sums
@@ -569,12 +552,7 @@ static void launch_fast(ConvFastArgs& a, hipStream_t st) {
   // its allocation and returned wrong sums; found by the pointwise-kernel test of round 4, no layer of the MSML
   // networks takes that combination)
   const size_t rlds = FUSE ? (size_t)(WGM * WGN * 64 / (BN / 8)) * 3 * BN * 4 : 0;
-#ifdef MSML_LDS_GUARD
-  static const bool drop_rlds = getenv("MSML_LDS_GUARD_DROP_RLDS") != nullptr;   // guard self-test: the round-3 allocation
-  if (rlds > lds && !drop_rlds) lds = rlds;
-#else
   if (rlds > lds) lds = rlds;
-#endif
   if (lds > 64 * 1024) {                               // above the default dynamic-LDS limit
     static std::once_flag once;
     std::call_once(once, [] {

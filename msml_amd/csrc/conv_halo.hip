@@ -53,24 +53,6 @@ struct ConvHaloArgs {
 
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-#ifdef HALO_TRACE
-// (-DHALO_TRACE, tools/halo_trace.py: wave `HALO_TRACE_WAVE` of workgroup 0 stamps s_memrealtime at the points of every stage)
-__device__ unsigned long long g_halo_trace[8192];
-extern "C" int msml_halo_trace_read(unsigned long long* dst, int n) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_halo_trace), sizeof(unsigned long long) * n, 0, hipMemcpyDeviceToHost);
-}
-#define HALO_STAMP(k)                                                                           \
-  do {                                                                                          \
-    if (blockIdx.x == 0 && wave == HALO_TRACE_WAVE && lane == 0 && tix < 8192 - 8)              \
-      g_halo_trace[tix++] = ((unsigned long long)(k) << 56) | (__builtin_amdgcn_s_memrealtime() & 0xffffffffffffffull); \
-  } while (0)
-#ifndef HALO_TRACE_WAVE
-#define HALO_TRACE_WAVE 0
-#endif
-#else
-#define HALO_STAMP(k)
-#endif
-
 // FUSE: backward-data launch with the fused BatchNorm backward-reduce (no bias / scale / PReLU /
 // residual / statistics in that case) -- a compile-time split keeps both epilogues in registers.
 // BN output channels per workgroup, NWM wave groups along the pixel rows: (256, 1) = 8 waves x
@@ -244,51 +226,24 @@ k_conv_halo(const ConvHaloArgs p) {
     __syncthreads();
   }
   int cs = 0, tr = 0, ts = 0;                          // slab, tap row / column of stage q
-#ifdef HALO_TRACE
-  int tix = 0;
-  if (wave == 0 && lane == 0) g_halo_trace[4096 + 2 * (blockIdx.x & 1023)] = __builtin_amdgcn_s_memrealtime();
-#endif
-#if defined(HALO_PRIO)
-  // (experiment: one static priority for half of the waves -- the two waves of a SIMD otherwise run their MFMA phases in
-  // lockstep, sharing the pipe, and then wait / request together with the pipe idle)
-  if (HALO_PRIO == 1 ? (wave >= 4) : (wave < 4)) __builtin_amdgcn_s_setprio(1);
-#endif
   u32x4 a[2][MTW], b[2];
-#ifdef HALO_ABLATE_READS
-  u32x4 a16x[2][MTW], b16x[2][2];                      // (ablation build: fragments read once, reused by every stage)
-#endif
   for (int q = 0; q < nstage; q++) {
     int ncs = cs, ntr = tr, nts = ts + 1;
     if (nts == 3) { nts = 0; ntr++; }
     if (ntr == 3) { ntr = 0; ncs++; }
     // this wave's weights of stage q (issued one stage ago) have landed; queue stage q + 1 and,
     // at the first tap of a slab, this wave's share of the next slab's image
-#ifdef HALO_SKEW
-    // (experiment: the second wave of every SIMD half a stage behind the first, re-established after every slab-switch
-    // barrier -- while one waits for its weights and requests the next ones the other is in its MFMA phase)
-    if (wave >= 4 && (tr | ts) == 0) __builtin_amdgcn_s_sleep(HALO_SKEW);
-#endif
-    HALO_STAMP(1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    HALO_STAMP(2);
-#ifndef HALO_ABLATE_LOADS
     if (q + 1 < nstage) {
       issue_b(ncs, ntr * 3 + nts, (q + 1) & 1);
       if ((tr | ts) == 0 && cs + 1 < nslab) issue_a(cs + 1, (cs + 1) & 1);
     }
-#endif
     // (the image chunks requested one stage ago have landed for this wave: the wait above)
     // (round 5: waves 4-7, the SIMD partners of 0-3, transform one tap later -- one wave's VALU beside the other's MFMAs;
-    // bit-identical, 128 @ 28x28 bn + conv 103.6 -> 101.8 us, the step 29.41 / 29.50 -> 29.36 / 29.39 ms on one box.
-    // -DHALO_XF_NO_STAGGER: all eight waves at tap 1)
-#ifdef HALO_XF_NO_STAGGER
-    if (XF && tr == 0 && ts == 1 && cs + 1 < nslab) xform(cs + 1, (cs + 1) & 1);
-#else
+    // bit-identical to all eight waves at tap 1, 128 @ 28x28 bn + conv 103.6 -> 101.8 us, the step 29.41 / 29.50 ->
+    // 29.36 / 29.39 ms on one box)
     if (XF && tr == 0 && ts == (wave < 4 ? 1 : 2) && cs + 1 < nslab) xform(cs + 1, (cs + 1) & 1);
-#endif
     __builtin_amdgcn_sched_barrier(0);
-    HALO_STAMP(3);
-#ifndef HALO_ABLATE_COMPUTE
     const int r = p.flip ? 2 - tr : tr, s = p.flip ? 2 - ts : ts;
     if constexpr (M16) {
       // pixel row (16 j + l16) of tap (r, s) is LDS pixel 16 j + l16 + r PITCH + s; the swizzle key follows l16 + s
@@ -298,27 +253,15 @@ k_conv_halo(const ConvHaloArgs p) {
       const int arow = l16 + s, asw = skey(arow);
       const char* Arow = As + (cs & 1) * ABYTES + (((r << PL2) + i0 * 32) * 128) + arow * 128;
       const char* B = Bs + (q & 1) * 4096;
-#ifdef HALO_ABLATE_READS
-      if (q == 0) {
-#pragma unroll
-        for (int j = 0; j < NGH; j++) a16x[0][j] = a16x[1][j] = *reinterpret_cast<const u32x4*>(Arow + ((q16 ^ asw) << 4) + j * 2048);
-#pragma unroll
-        for (int g = 0; g < 2; g++) b16x[0][g] = b16x[1][g] = *reinterpret_cast<const u32x4*>(B + bfr16[g][0]);
-      }
-      u32x4 (&a16)[2][NGH] = a16x;
-      u32x4 (&b16)[2][2] = b16x;
-#else
       u32x4 a16[2][NGH], b16[2][2];
 #pragma unroll
       for (int j = 0; j < NGH; j++)
         if (j < ng) a16[0][j] = *reinterpret_cast<const u32x4*>(Arow + ((q16 ^ asw) << 4) + j * 2048);
 #pragma unroll
       for (int g = 0; g < 2; g++) b16[0][g] = *reinterpret_cast<const u32x4*>(B + bfr16[g][0]);
-#endif
 #pragma unroll
       for (int ph = 0; ph < 4; ph++) {
         const int cb = ph & 1, nb = cb ^ 1, w = ph >> 1, hf = ph & 1;
-#ifndef HALO_ABLATE_READS
         if (ph + 1 < 4) {
           const int nw = (ph + 1) >> 1, nhf = (ph + 1) & 1;
           const int ao = ((4 * nw + q16) ^ asw) << 4;
@@ -330,7 +273,6 @@ k_conv_halo(const ConvHaloArgs p) {
             for (int g = 0; g < 2; g++) b16[nw & 1][g] = *reinterpret_cast<const u32x4*>(B + bfr16[g][nw]);
           }
         }
-#endif
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < NGH; j++)
@@ -349,26 +291,13 @@ k_conv_halo(const ConvHaloArgs p) {
     const char* B = Bs + (q & 1) * 4096;
     // register double buffer of the fragments of one 16-deep k step; the fences keep hipcc from
     // sinking the reads next to their MFMAs (which exposes the LDS latency at every MFMA)
-#ifdef HALO_ABLATE_READS
-    if (q == 0) {
-#pragma unroll
-      for (int i = 0; i < MTW; i++) {
-        a[0][i] = *reinterpret_cast<const u32x4*>(Arow + ((h ^ asw) << 4) + i * 4096);
-        a[1][i] = a[0][i];
-      }
-      b[0] = *reinterpret_cast<const u32x4*>(B + bfr[0]);
-      b[1] = b[0];
-    }
-#else
 #pragma unroll
     for (int i = 0; i < MTW; i++)
       if (i < nmt) a[0][i] = *reinterpret_cast<const u32x4*>(Arow + ((h ^ asw) << 4) + i * 4096);
     b[0] = *reinterpret_cast<const u32x4*>(B + bfr[0]);
-#endif
 #pragma unroll
     for (int kk = 0; kk < 4; kk++) {
       const int cb = kk & 1, nb = cb ^ 1;
-#ifndef HALO_ABLATE_READS
       if (kk + 1 < 4) {
         const int ao = (((kk + 1) * 2 + h) ^ asw) << 4;
 #pragma unroll
@@ -376,7 +305,6 @@ k_conv_halo(const ConvHaloArgs p) {
           if (i < nmt) a[nb][i] = *reinterpret_cast<const u32x4*>(Arow + ao + i * 4096);
         b[nb] = *reinterpret_cast<const u32x4*>(B + bfr[kk + 1]);
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < MTW; i++)
@@ -386,21 +314,14 @@ k_conv_halo(const ConvHaloArgs p) {
       __builtin_amdgcn_sched_barrier(0);
     }
     }
-#endif
-    HALO_STAMP(4);
     if (ncs != cs && ncs < nslab) {
       __syncthreads();                                 // slab switch: next image landed everywhere
-      HALO_STAMP(5);
     }
     cs = ncs; tr = ntr; ts = nts;
   }
   __syncthreads();
-  HALO_STAMP(5);
 
   // ---------------- epilogue: affine / PReLU, BatchNorm partials, LDS transpose, 16-B stores -----
-#ifdef HALO_ABLATE_EPILOGUE
-  if (p.N >= 0) return;
-#endif
   constexpr int OP = BN + 8;                           // 528-B rows
   unsigned short* otile = reinterpret_cast<unsigned short*>(smem);
   MSML_LDS_REGION(otile, BM * OP * 2);
@@ -416,12 +337,9 @@ k_conv_halo(const ConvHaloArgs p) {
   // input fetched per (pixel group, lane) -- no LDS transpose, no barrier between the main loop and the stores
   // Measured NOT faster on these maps (round 5, tools/bench_bnbwd.py + step A/B on one box: 128 @ 28x28 102.1 -> 99.5 us, 256 @
   // 14x14 65.8 -> 65.8 us, the step 29.24 / 29.21 -> 29.35 / 29.35 ms: the per-lane loads of the saved input touch 64 B per
-  // pixel and wave where the copy-out loop reads whole 512-B pixel rows) -- kept as a build switch, -DHALO_FDIR.
-#ifdef HALO_FDIR
-  constexpr bool FDIR = FUSE && M16;
-#else
+  // pixel and wave where the copy-out loop reads whole 512-B pixel rows), so it is off here; k_conv_halo_p below, whose
+  // tiles never pass through LDS, takes its sums in this layout.
   constexpr bool FDIR = false;
-#endif
   const int cdir = kg * 32 + (q16 & 1) * 16 + (q16 >> 1) * 8;
   u32x4 xr[FDIR ? NG : ITERS];
   BnbCoef bk;
@@ -500,11 +418,7 @@ k_conv_halo(const ConvHaloArgs p) {
           o16[e] = sw[0]; o16[2 + e] = sw[1];
         }
         if (valid) {
-#ifdef HALO_NT_STORE
-          __builtin_nontemporal_store(o16, reinterpret_cast<u32x4*>(p.out + pix_off(m) + n0 + kg * 32 + (q16 & 1) * 16 + (q16 >> 1) * 8));
-#else
           *reinterpret_cast<u32x4*>(p.out + pix_off(m) + n0 + kg * 32 + (q16 & 1) * 16 + (q16 >> 1) * 8) = o16;
-#endif
           if constexpr (FDIR)
             bnb_accum(bk, p.bnb.alpha != nullptr, load8<unsigned short>(reinterpret_cast<const unsigned short*>(&o16)),
                       load8<unsigned short>(reinterpret_cast<const unsigned short*>(&xr[jg])), bq);
@@ -701,10 +615,6 @@ k_conv_halo(const ConvHaloArgs p) {
       for (int c = t; c < 2 * BN; c += NT)
         p.stats[((long)row * 2 + c / BN) * p.coutp + n0 + c % BN] = 0.f;
   }
-  HALO_STAMP(6);
-#ifdef HALO_TRACE
-  if (wave == 0 && lane == 0) g_halo_trace[4096 + 2 * (blockIdx.x & 1023) + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
 #endif
 }
 
@@ -718,7 +628,7 @@ k_conv_halo(const ConvHaloArgs p) {
 // statistics / fused backward sums stay in registers until the workgroup's last tile (one set of atomics per workgroup).
 // Same tiling, fragment maps and per-tile arithmetic as k_conv_halo<128, 2, FUSE, ..., M16>: outputs are bit-identical,
 // the sums differ in the order the tiles are added.  Plain forward (+ accumulator-mode statistics) and backward-data with
-// the fused BatchNorm sums (accumulator mode; register layout of -DHALO_FDIR); coutp == 128.
+// the fused BatchNorm sums (accumulator mode; register layout of k_conv_halo's FDIR epilogue); coutp == 128.
 // XF (round 6): the forward launch whose input is PReLU(BatchNorm(in)) with the coefficients derived from the producer's
 // f64 sums in the prologue (msml_conv2d_bnin_acc): every wave normalises the image chunks it requested itself, one or two
 // taps after the request (its own vmcnt wait orders them; the slab-switch barrier publishes them), and writes the tile's
@@ -852,18 +762,8 @@ k_conv_halo_p(const ConvHaloArgs p, const int ntiles, const unsigned int out_byt
     xform(aoff, 0, 0);
     __syncthreads();
   }
-#if defined(HALO_PRIO)
-  if (HALO_PRIO == 1 ? (wave >= 4) : (wave < 4)) __builtin_amdgcn_s_setprio(1);
-#endif
   int gs = 0, gq = 0;                                  // running slab / stage counters: image buffer gs & 1, weight slot gq & 1
   bool first = true;
-#ifdef HALO_TRACE
-  int tix = 0;
-#endif
-  HALO_STAMP(9);
-#ifdef HALO_TRACE
-  if (wave == 0 && lane == 0) g_halo_trace[4096 + 2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();   // every workgroup: start ...
-#endif
   for (; tile < ntiles; tile += gridDim.x) {
     const int n = tile / tpi, trem = tile - n * tpi, ty = trem / p.tpx;
     const int y0 = ty * TH, x0 = (trem - ty * p.tpx) * TW;
@@ -880,18 +780,12 @@ k_conv_halo_p(const ConvHaloArgs p, const int ntiles, const unsigned int out_byt
       int ncs = cs, ntr = tr, nts = ts + 1;
       if (nts == 3) { nts = 0; ntr++; }
       if (ntr == 3) { ntr = 0; ncs++; }
-      HALO_STAMP(1);
       // this wave's weights of stage q have landed.  Stage 0 of a later tile: they were requested BEFORE the previous
       // tile's epilogue, whose NG stores (always issued, out of range when masked) are the only younger operations.
       // (Also requesting stage 1's weights before the epilogue, so that stage 1 does not wait for the stores to be
       // acknowledged either -- counted waits of 12 -- measured no faster alone and slower in the step; not kept.)
-#ifdef HALO_ABLATE_EPILOGUE
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
       if (q == 0 && !first) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-      HALO_STAMP(2);
       if (q + 1 < nstage) issue_b(ncs, ntr * 3 + nts, (gq + 1) & 1);
       else issue_b(0, 0, (gq + 1) & 1);                // the next tile's first stage (past the end: a harmless re-read)
       if ((tr | ts) == 0) {                            // first tap of a slab: the next slab's image, this tile's or the next one's
@@ -905,7 +799,6 @@ k_conv_halo_p(const ConvHaloArgs p, const int ntiles, const unsigned int out_byt
         else xform(aoffn, 0, (gs + 1) & 1);
       }
       __builtin_amdgcn_sched_barrier(0);
-      HALO_STAMP(3);
       const int r = p.flip ? 2 - tr : tr, s = p.flip ? 2 - ts : ts;
       const int arow = l16 + s, asw = skey(arow);
       const char* Arow = As + (gs & 1) * ABYTES + (((r << PL2) + i0 * 32) * 128) + arow * 128;
@@ -942,22 +835,13 @@ k_conv_halo_p(const ConvHaloArgs p, const int ntiles, const unsigned int out_byt
           }
         __builtin_amdgcn_sched_barrier(0);
       }
-      HALO_STAMP(4);
       if (ncs != cs) {                                 // slab switch (also the tile's end): the next image has landed
         __syncthreads();                               // everywhere, and nobody reads the buffer the one after overwrites
         gs++;
-        HALO_STAMP(5);
       }
       cs = ncs; tr = ntr; ts = nts;
     }
     first = false;
-#ifdef HALO_ABLATE_EPILOGUE
-    if (p.N >= 0) {
-#pragma unroll
-      for (int i = 0; i < NAI; i++) aoff[i] = aoffn[i];
-      continue;
-    }
-#endif
     // ---- epilogue from registers: pair swap -> 8 contiguous channels per lane, one 16-B store per pixel group ----
     u32x4 xr[NG];
     if (FUSE) {
@@ -996,14 +880,10 @@ k_conv_halo_p(const ConvHaloArgs p, const int ntiles, const unsigned int out_byt
     }
 #pragma unroll
     for (int i = 0; i < NAI; i++) aoff[i] = aoffn[i];
-    HALO_STAMP(6);
   }
   // ---- the workgroup's sums: the lanes that share a channel meet in LDS (every image / ring request has landed) --
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-#ifdef HALO_TRACE
-  if (wave == 0 && lane == 0) g_halo_trace[4096 + 2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();  // ... and end of its tiles
-#endif
   if (FUSE) {
     constexpr int G = 16 * 2;                          // lanes (mg, l16) share an 8-channel chunk
     float* red = reinterpret_cast<float*>(smem);

@@ -134,11 +134,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   // (FUSE on the 16x16x32 tiling: the sums are taken in the register layout of the direct store -- after the permlane swap
   // a lane holds channels cdir .. cdir + 7 of its pixel -- so its coefficients are those of that chunk)
   const int cdir = kg * 32 + (q16 & 1) * 16 + (q16 >> 1) * 8;
-#ifdef WS_NO_FDIR
-  if (FUSE) bk = bnb_load_coef(p.bnb, c8 * 8);
-#else
   if (FUSE) bk = bnb_load_coef(p.bnb, M16 ? cdir : c8 * 8);
-#endif
 #pragma unroll
   for (int q = 0; q < 3; q++)
 #pragma unroll
@@ -150,17 +146,13 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 
   // ---- direct epilogue of the 16x16x32 tiling (round 5): forward launches without a residual and backward-data launches
   // with the fused BatchNorm sums store straight from registers -- v_permlane16_swap leaves every lane with 8 contiguous
-  // channels of its pixel (conv_halo.hip): no LDS transpose, one barrier per tile.  -DWS_STAGGER (tried, not faster): waves
-  // 4-7 (the SIMD partners of 0-3) keep their accumulators across the barrier and store tile t at the top of iteration
-  // t + 1, beside their partners' MFMAs (MI355X_MICROARCH.md, two waves per SIMD, item 9); bit-identical either way.
+  // channels of its pixel (conv_halo.hip): no LDS transpose, one barrier per tile.  `late` (tried, not faster, fixed off below):
+  // waves 4-7 (the SIMD partners of 0-3) keep their accumulators across the barrier and store tile t at the top of
+  // iteration t + 1, beside their partners' MFMAs (MI355X_MICROARCH.md, two waves per SIMD, item 9); bit-identical either way.
   f32x16 acc[2];
   f32x4 acc4[4][2];                                    // M16: [16-pixel group][channel half]
   u32x4 xr[ITERS];
-#ifdef WS_NO_FDIR
-  constexpr bool FDIR = false;                         // (A/B build)
-#else
   constexpr bool FDIR = M16 && FUSE;
-#endif
   auto epi_dir = [&](int tl) {
     const int n = tl / tpi, trem = tl - n * tpi, ty = trem / p.tpx;
     const int y0 = ty * TH, x0 = (trem - ty * p.tpx) * TW;
@@ -197,9 +189,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         o16[e] = sw[0]; o16[2 + e] = sw[1];
       }
       if (valid) {
-#ifndef WS_ABLATE_STORE
         *reinterpret_cast<u32x4*>(p.out + pix_off(m) + cdir) = o16;
-#endif
         if constexpr (FDIR)
           bnb_accum(bk, p.bnb.alpha != nullptr, load8<unsigned short>(reinterpret_cast<const unsigned short*>(&o16)),
                     load8<unsigned short>(reinterpret_cast<const unsigned short*>(&xr[jg])), bq);
@@ -207,12 +197,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     }
   };
   const bool dir = M16 && (FDIR || (!FUSE && p.residual == nullptr));
-#ifdef WS_STAGGER
-  const bool late = dir && wave >= 4;
-#else
   const bool late = false;     // measured (round 5, one box): staggered 398 / 89 us forward, 95.4 us fused backward-data against
-                               // 390 / 87 / 89.5 us unstaggered -- the late waves' image requests start later; build switch only
-#endif
+                               // 390 / 87 / 89.5 us unstaggered -- the late waves' image requests start later
   int ptile = -1;
 
   for (int it = 0; tile < p.ntiles; it++, tile += gridDim.x) {
@@ -224,9 +210,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     auto pix_off = [&](int m) { return ((long)(n * p.H + y0 + (m >> 4)) * p.W + x0 + (m & 15)) * C; };
     // next tile's image (its buffer was the transpose tile of the previous iteration: the barrier
     // that closes an iteration orders those reads before this write)
-#ifndef WS_ABLATE_LOADS
     if (tile + (int)gridDim.x < p.ntiles) issue_a(tile + gridDim.x, cur ^ 1);
-#endif
     if (FDIR) {                                        // saved BatchNorm input in the direct-store layout
 #pragma unroll
       for (int k = 0; k < 4; k++) {
@@ -273,12 +257,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
       for (int step = 0; step < 18; step++) {
         const int cb = step & 1, nb = cb ^ 1;
-#ifdef WS_ABLATE_READS
-        if (step + 1 < 18) { a16[nb][0] = a16[cb][0]; a16[nb][1] = a16[cb][1]; a16[nb][2] = a16[cb][2]; a16[nb][3] = a16[cb][3];
-                             b16[nb][0] = b16[cb][0]; b16[nb][1] = b16[cb][1]; }   // (timing build: fragments read once per tile)
-#else
         if (step + 1 < 18) frags(step + 1, a16[nb], b16[nb]);
-#endif
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < 4; j++)
@@ -431,10 +410,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     for (int q = 0; q < 3; q++)
 #pragma unroll
       for (int j = 0; j < 8; j++) {
-#ifndef WS_NO_FDIR
         if constexpr (M16) red[((((wave >> 1) * 16 + l16)) * 3 + q) * C + cdir + j] = bq[q][j];   // 64 lanes share a chunk
         else
-#endif
           red[((t / C8) * 3 + q) * C + c8 * 8 + j] = bq[q][j];
       }
     __syncthreads();

@@ -173,18 +173,14 @@ __global__ void __launch_bounds__(256) k_wgrad_fast(const WgradFastArgs p) {
 #pragma unroll
         for (int j = 0; j < TN; j++) b[nb][j] = trf(vb + (kk + 1) * (GB * 1024) + j * 1024);
       }
-#ifndef MSML_NO_SCHED_FENCE
       __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
       for (int i = 0; i < TM; i++)
 #pragma unroll
         for (int j = 0; j < TN; j++)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
               __builtin_bit_cast(bf16x8, a[cb][i]), __builtin_bit_cast(bf16x8, b[cb][j]), acc[i][j], 0, 0, 0);
-#ifndef MSML_NO_SCHED_FENCE
       __builtin_amdgcn_sched_barrier(0);
-#endif
     }
     __syncthreads();
     cur ^= 1;

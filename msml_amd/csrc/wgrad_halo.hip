@@ -215,9 +215,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   int cur = 0;
   s16x8 fa[2][NI], fb5[2][5];
   for (int strip = s_begin; strip < s_end; strip++) {
-#ifndef WH_ABLATE_LOADS
     if (strip + 1 < s_end) issue(strip + 1, cur ^ 1);
-#endif
     const char* ub = smem + cur * STAGE + aofs;
     const char* vb = smem + cur * STAGE + UB;
     // taps tap0 + k, k < ntaps, of this wave's group.  All fragments of k-step j + 1 are requested
@@ -231,18 +229,11 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
       for (int k = 0; k < 5; k++)
         if (k < ntaps) fb5[fb][k] = tr2(vb + j * 2048 + vlok[k], vb + j * 2048 + vhik[k]);
     };
-#ifdef WH_ABLATE_READS
-    if (strip == s_begin)
-#endif
     fetch(0, 0);
 #pragma unroll
     for (int j = 0; j < 7; j++) {                      // k-step = strip row j (16 pixels)
       const int fb = j & 1;
-#ifdef WH_ABLATE_READS
-      if (j == 0 && strip == s_begin) fetch(1, 1);
-#else
       if (j + 1 < 7) fetch(j + 1, fb ^ 1);
-#endif
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int k = 0; k < 5; k++)
@@ -265,9 +256,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     cur ^= 1;
   }
 
-#ifdef WH_ABLATE_EPI
-  if (p.N >= 0) return;
-#endif
   // slab [z][a][tap][b] (k_wgrad_reduce sums the zper splits of a layer in a fixed order)
   const int h = lane >> 5, c32 = lane & 31;
   const int b = b0 + nh * 32 + c32;
