@@ -457,6 +457,26 @@ int msml_occ_resize(const unsigned char* atlas, const int* meta, const int* dir,
 int msml_occ_apply_tex(const unsigned char* src, const int* desc, const unsigned char* patch, long patch_stride,
                        float* img, long* msk, float* ori, int N, int H, int W, int light, void* stream);
 
+/* Gray / resized / unnormalised output: FaceByRandOccMask.__getitem__ with is_gray, out_size, use_norm
+ * (datasets/load_dataset.py:86-139,179,183-201; the LightCNN recipe of config.py:99-102 is gray, 128 x 128, no Normalize).
+ * msml_occ_draw_out: msml_occ_draw_tex (all modes; meta may be NULL for modes 0-4) with the light centre drawn over
+ *   out_w x out_h, the image the light is added to.  Same draw indices: with out_h = H, out_w = W the descriptors equal
+ *   msml_occ_draw[_tex]'s word for word; otherwise only words 9 and 10 differ.
+ * msml_occ_apply_out: occlusion at the source size (patch: msml_occ_resize's output for texture descriptors, or NULL),
+ *   convert('L') when gray (L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16), Image.resize((out_w, out_h), BILINEAR) of
+ *   face, 0 / 255 mask and clean face bit for bit (horizontal pass, uint8 intermediate, vertical pass; an axis whose
+ *   size does not change is skipped), flip, ToTensor, light at the output size, mask != 255 -> 0 else 1, Normalize(0.5,
+ *   0.5) only when norm != 0.  img / ori [N][C][out_h][out_w] f32 with C = 1 (gray) or 3, msk [N][out_h][out_w] int64;
+ *   ori may be NULL.  tabw / tabh: Pillow's triangle-filter coefficients of W -> out_w / H -> out_h in the layout of
+ *   msml_occ_resize's tables ([out][10] int32: first tap, taps, 22-bit fixed-point coefficients), built on the host;
+ *   NULL for an axis that keeps its size.  One workgroup per image with every intermediate in LDS: returns
+ *   MSML_ERR_UNSUPPORTED before any launch when the planes need more than 160 KB (RGB 112 -> 224) or out_w % 4 != 0. */
+int msml_occ_draw_out(long seed, long offset, int N, int H, int W, int out_h, int out_w, int mode, int lo, int hi,
+                      int flip, const int* meta, int nsets, int* desc, void* stream);
+int msml_occ_apply_out(const unsigned char* src, const int* desc, const unsigned char* patch, long patch_stride,
+                       const int* tabw, const int* tabh, float* img, long* msk, float* ori, int N, int H, int W,
+                       int out_h, int out_w, int gray, int norm, int light, void* stream);
+
 /* Backward-data of the OSB decoder's ConvTranspose2d(36 -> 18, k 4, s 2, p 1) on cat(seg, gcm) (backbones/osb/unet.py:
  * 140-156, autograd of deconv2..5) for BOTH input segments from one pass over dY (bf16):
  *   dxS[n, i, j, ci] = sum_{r, s, co} dy[n, 2i - 1 + r, 2j - 1 + s, co] * w[S * 18 + ci][co][r][s]

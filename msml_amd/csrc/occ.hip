@@ -92,7 +92,8 @@ __device__ inline int occ_pick_set(const int* meta, int nsets, int kind, unsigne
 }
 
 __global__ void k_occ_draw(unsigned long long seed, unsigned long long offset, int N, int H, int W, int mode, int lo,
-                           int hi, int flip_on, const int* __restrict__ meta, int nsets, int* __restrict__ desc) {
+                           int hi, int flip_on, const int* __restrict__ meta, int nsets, int* __restrict__ desc,
+                           int LH, int LW) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const unsigned long long img = offset + (unsigned long long)i;
@@ -207,8 +208,10 @@ __global__ void k_occ_draw(unsigned long long seed, unsigned long long offset, i
   }
   d[0] = kind;
   d[8] = flip_on ? (occ_randint(occ_u32(seed, img, 8), 1, 11) >= 5 ? 1 : 0) : 0;    // load_dataset.py:120
-  d[9] = __float_as_int((float)W * occ_unif(occ_u32(seed, img, 9)));              // _get_gauss :307-309
-  d[10] = __float_as_int((float)H * occ_unif(occ_u32(seed, img, 10)));
+  // _get_gauss :307-309: the light centre is uniform over the image the light is added to (LW x LH: the OUTPUT size,
+  // load_dataset.py:183-201 runs after the resize; = W x H for msml_occ_draw[_tex])
+  d[9] = __float_as_int((float)LW * occ_unif(occ_u32(seed, img, 9)));
+  d[10] = __float_as_int((float)LH * occ_unif(occ_u32(seed, img, 10)));
   d[11] = __float_as_int(0.7f + (1.4f - 0.7f) * occ_unif(occ_u32(seed, img, 11)));  // :194
   for (int k = 0; k < OCC_DESC; k++) desc[i * OCC_DESC + k] = d[k];
 }
@@ -399,7 +402,7 @@ extern "C" int msml_occ_draw(long seed, long offset, int N, int H, int W, int mo
                              int flip, int* desc, void* stream) {
   MSML_CHECK(desc && N > 0 && H >= 32 && W >= 32 && mode >= 0 && mode <= 4 && lo >= 0 && hi > lo && hi <= 101,
              MSML_ERR_SHAPE, "occ_draw: bad arguments N=%d H=%d W=%d mode=%d lo=%d hi=%d", N, H, W, mode, lo, hi);
-  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, nullptr, 0, desc);
+  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, nullptr, 0, desc, H, W);
   MSML_LAUNCH_OK("occ_draw");
   return MSML_OK;
 }
@@ -410,7 +413,7 @@ extern "C" int msml_occ_draw_tex(long seed, long offset, int N, int H, int W, in
              MSML_ERR_SHAPE, "occ_draw_tex: bad arguments N=%d H=%d W=%d mode=%d lo=%d hi=%d", N, H, W, mode, lo, hi);
   MSML_CHECK(mode < 5 || (meta && nsets > 0 && nsets <= 16), MSML_ERR_SHAPE,
              "occ_draw_tex: modes 5-9 need 1..16 occluder sets (got %d)", nsets);
-  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, meta, nsets, desc);
+  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, meta, nsets, desc, H, W);
   MSML_LAUNCH_OK("occ_draw_tex");
   return MSML_OK;
 }
@@ -445,5 +448,275 @@ extern "C" int msml_occ_apply_tex(const unsigned char* src, const int* desc, con
   MSML_CHECK(src && desc && patch && img && msk && N > 0 && H > 0 && W > 0, MSML_ERR_SHAPE, "occ_apply_tex: bad arguments");
   k_occ_apply<<<N, 256, 0, (hipStream_t)stream>>>(src, desc, img, msk, ori, H, W, light, patch, patch_stride);
   MSML_LAUNCH_OK("occ_apply_tex");
+  return MSML_OK;
+}
+
+// ---------------------------------------------------------------- gray / resized / unnormalised output
+// FaceByRandOccMask.__getitem__ with is_gray / out_size / use_norm (datasets/load_dataset.py:86-139,179,183-201; the
+// LightCNN recipe config.py:99-102 sets gray, 128 x 128, no Normalize): occlude at the SOURCE size -> convert('L')
+// (L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16) -> transforms.Resize of face, 0 / 255 mask and clean face
+// (Image.resize(BILINEAR): Pillow's separable resampling with the triangle filter -- horizontal pass, uint8 intermediate,
+// vertical pass, 22-bit fixed-point coefficients built on the host; an axis whose size does not change is skipped) ->
+// flip -> ToTensor -> light at the OUTPUT size -> mask != 255 -> 0 else 1 -> Normalize only when asked.  The mask is
+// interpolated as an image: every output pixel the filter mixes with an occluded one is occluded.
+//
+// One workgroup of 1024 threads per image, everything between the source read and the output stores in LDS:
+//   raw  [H][W][3]   the decoded face, read once, 16 B per lane
+//   Mk   [H][W]      0 (occluded) / 255 mask at source size
+//   S    [H][W]      the plane being resampled (one colour plane of the occluded or of the clean face; L when gray)
+//   Bh   [H][ow]     S after the horizontal pass (absent when ow == W)
+//   O    [C][oh][ow] the occluded face after both passes and the flip: the light's  / max  needs every value of the
+//                    image before the first one can be written, so img is kept here as uint8 and written ONCE
+// Planes go through S / Bh one after the other (mask, C face planes, C clean planes), so RGB with a resize and ori fits:
+// 136 960 B at 112 -> 128 RGB, 104 192 B gray.  Every global store is 16 B per lane (float4 / two int64); needs ow % 4 == 0.
+#define OCC_OUT_T 1024
+#define OCC_OUT_HDR 512          // desc[64] int32 + the 16 per-wave maxima
+struct OccOutLds {
+  long tabw, tabh, raw, mk, s, bh, o, total;
+};
+__host__ __device__ inline long occ_r16(long b) { return (b + 15) & ~15L; }
+__host__ __device__ inline OccOutLds occ_out_lds(int H, int W, int oh, int ow, int C) {
+  OccOutLds L;
+  long off = OCC_OUT_HDR;
+  L.tabw = off; off += ow != W ? occ_r16((long)ow * OCC_RT * 4) : 0;
+  L.tabh = off; off += oh != H ? occ_r16((long)oh * OCC_RT * 4) : 0;
+  L.raw = off;  off += occ_r16((long)H * W * 3);
+  L.mk = off;   off += occ_r16((long)H * W);
+  L.s = off;    off += occ_r16((long)H * W);
+  L.bh = off;   off += ow != W ? occ_r16((long)H * ow) : 0;
+  L.o = off;    off += occ_r16((long)C * oh * ow);
+  L.total = off;
+  return L;
+}
+__device__ __forceinline__ unsigned int occ_luma(unsigned int r, unsigned int g, unsigned int b) {
+  return (19595u * r + 38470u * g + 7471u * b + 0x8000u) >> 16;          // Pillow Convert.c L24 + rounding
+}
+
+__global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_out(
+    const unsigned char* __restrict__ src, const int* __restrict__ desc, const unsigned char* __restrict__ patch,
+    long pstride, const int* __restrict__ tabw, const int* __restrict__ tabh, float* __restrict__ img,
+    long* __restrict__ msk, float* __restrict__ ori, int H, int W, int oh, int ow, int gray, int norm, int light) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smo[];
+  const int n = blockIdx.x, t = threadIdx.x;
+  const int C = gray ? 1 : 3, HW = H * W, ohow = oh * ow;
+  const OccOutLds L = occ_out_lds(H, W, oh, ow, C);
+  int* d = reinterpret_cast<int*>(smo);
+  float* red = reinterpret_cast<float*>(smo + OCC_DESC * 4);
+  const int* tw = ow != W ? reinterpret_cast<const int*>(smo + L.tabw) : nullptr;
+  const int* th = oh != H ? reinterpret_cast<const int*>(smo + L.tabh) : nullptr;
+  unsigned char* raw = smo + L.raw;
+  unsigned char* Mk = smo + L.mk;
+  unsigned char* S = smo + L.s;
+  unsigned char* Bh = smo + L.bh;
+  unsigned char* O = smo + L.o;
+  MSML_LDS_REGION(O, (long)C * ohow);
+  if (t < OCC_DESC) d[t] = desc[n * OCC_DESC + t];
+  if (tw) for (int i = t; i < ow * OCC_RT; i += OCC_OUT_T) reinterpret_cast<int*>(smo + L.tabw)[i] = tabw[i];
+  if (th) for (int i = t; i < oh * OCC_RT; i += OCC_OUT_T) reinterpret_cast<int*>(smo + L.tabh)[i] = tabh[i];
+  {
+    const unsigned char* s = src + (long)n * HW * 3;
+    if ((HW * 3) % 16 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+      for (int i = t; i < HW * 3 / 16; i += OCC_OUT_T)
+        reinterpret_cast<u32x4*>(raw)[i] = reinterpret_cast<const u32x4*>(s)[i];
+    } else {
+      for (int i = t; i < HW * 3; i += OCC_OUT_T) raw[i] = s[i];
+    }
+  }
+  __syncthreads();
+  const int kind = d[0];
+  const bool flip = d[8] != 0;
+  const bool tex = kind >= OCC_GLASSES && patch != nullptr;     // (no patch buffer on texture descriptors = clean)
+  const unsigned char* pt = tex ? patch + (long)n * pstride : nullptr;
+  // the 0 / 255 mask at source size (occ_inside / alpha != 0 of the paste, as k_occ_apply)
+  for (int p = t; p < HW; p += OCC_OUT_T) {
+    const int y = p / W, x = p - y * W;
+    bool in = occ_inside(d, x, y);
+    if (tex) {
+      const int px = x - d[1], py = y - d[2];
+      if (px >= 0 && px < d[3] && py >= 0 && py < d[4]) in = pt[((long)py * d[3] + px) * 4 + 3] != 0;
+    }
+    Mk[p] = in ? 0 : 255;
+  }
+  __syncthreads();
+  // planes: 0 = mask, 1 .. C = occluded face, C + 1 .. 2 C = clean face (ori)
+  const int planes = ori ? 1 + 2 * C : 1 + C;
+  for (int pl = 0; pl < planes; pl++) {
+    const bool face = pl >= 1 && pl <= C;
+    const int c = pl == 0 ? 0 : (pl - 1) % C;
+    const unsigned char* P = Mk;
+    if (pl > 0) {
+      for (int p = t; p < HW; p += OCC_OUT_T) {
+        const unsigned char* q = raw + p * 3;
+        unsigned int r = q[0], g = q[1], b = q[2];
+        if (face) {
+          if (tex) {                                  // glasses replace where alpha > 10, scarf / object where alpha != 0
+            const int y = p / W, x = p - y * W;
+            const int px = x - d[1], py = y - d[2];
+            if (px >= 0 && px < d[3] && py >= 0 && py < d[4]) {
+              const unsigned char* tp = pt + ((long)py * d[3] + px) * 4;
+              if (kind == OCC_GLASSES ? tp[3] > 10 : tp[3] != 0) { r = tp[0]; g = tp[1]; b = tp[2]; }
+            }
+          } else if (Mk[p] == 0) {
+            if (kind == OCC_BLOCK) r = g = b = 0;
+            else { r = (unsigned int)d[5]; g = (unsigned int)d[6]; b = (unsigned int)d[7]; }
+          }
+        }
+        S[p] = (unsigned char)(gray ? occ_luma(r, g, b) : (c == 0 ? r : (c == 1 ? g : b)));
+      }
+      __syncthreads();
+      P = S;
+    }
+    const unsigned char* Q = P;                       // [H][ow]
+    if (tw) {                                         // horizontal pass, four outputs per lane
+      for (int i = t; i < H * ow / 4; i += OCC_OUT_T) {
+        const int y = (i * 4) / ow, xx = i * 4 - y * ow;
+        unsigned int pack = 0;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          const int* k = tw + (xx + e) * OCC_RT;
+          const unsigned char* row = P + y * W + k[0];
+          int ss = 1 << 21;
+          for (int j = 0; j < k[1]; j++) ss += (int)row[j] * k[2 + j];
+          pack |= (unsigned int)occ_clip8(ss >> 22) << (8 * e);
+        }
+        reinterpret_cast<unsigned int*>(Bh)[i] = pack;
+      }
+      __syncthreads();
+      Q = Bh;
+    }
+    // vertical pass + flip, four outputs per lane: the mask and the clean face go to HBM, the occluded face to O
+    for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
+      const int p = i * 4, yy = p / ow, x = p - yy * ow;
+      const int base = flip ? ow - 4 - x : x;         // the four source columns, a 4-byte aligned word of every row
+      int v[4];
+      if (th) {
+        const int* k = th + yy * OCC_RT;
+        int ss[4] = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
+        for (int j = 0; j < k[1]; j++) {
+          const unsigned int wd = *reinterpret_cast<const unsigned int*>(Q + (k[0] + j) * ow + base);
+          const int kk = k[2 + j];
+#pragma unroll
+          for (int e = 0; e < 4; e++) ss[e] += (int)((wd >> (8 * e)) & 255u) * kk;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; e++) v[e] = occ_clip8(ss[e] >> 22);
+      } else {
+        const unsigned int wd = *reinterpret_cast<const unsigned int*>(Q + yy * ow + base);
+#pragma unroll
+        for (int e = 0; e < 4; e++) v[e] = (int)((wd >> (8 * e)) & 255u);
+      }
+      if (flip) {
+        int s0 = v[0], s1 = v[1];
+        v[0] = v[3]; v[1] = v[2]; v[2] = s1; v[3] = s0;
+      }
+      if (pl == 0) {                                  // Msk2Tenser: != 255 -> 0, else 1
+        longlong2 a, b;
+        a.x = v[0] == 255; a.y = v[1] == 255; b.x = v[2] == 255; b.y = v[3] == 255;
+        longlong2* o = reinterpret_cast<longlong2*>(msk + (long)n * ohow + p);
+        o[0] = a;
+        o[1] = b;
+      } else if (face) {
+        reinterpret_cast<unsigned int*>(O + (long)c * ohow)[i] =
+            (unsigned int)v[0] | ((unsigned int)v[1] << 8) | ((unsigned int)v[2] << 16) | ((unsigned int)v[3] << 24);
+      } else {
+        f32x4 r;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          const float cl = (float)v[e] / 255.0f;      // ToTensor
+          r[e] = norm ? (cl - 0.5f) / 0.5f : cl;
+        }
+        *reinterpret_cast<f32x4*>(ori + ((long)n * C + c) * ohow + p) = r;
+      }
+    }
+    __syncthreads();                                  // S / Bh are rebuilt for the next plane; O is complete after the last
+  }
+  // ToTensor, light at the output size, / max, Normalize: img is written once
+  const float lcx = __int_as_float(d[9]), lcy = __int_as_float(d[10]), lscale = __int_as_float(d[11]);
+  auto lightmap = [&](int x, int y) -> float {        // as k_occ_apply
+    const int ix = (int)((float)x - lcx), iy = (int)((float)y - lcy);
+    const float dist = sqrtf((float)(ix * ix + iy * iy));
+    const float g = expf(-0.5f * (dist * dist) / 16384.0f);
+    const __half g16 = __float2half(g);
+    const __half l16 = __float2half(__half2float(g16) * __half2float(__float2half(lscale)));
+    return __half2float(l16);
+  };
+  float vmax = 0.f;
+  if (light) {
+    for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
+      const int p = i * 4, y = p / ow, x = p - y * ow;
+      float l[4];
+#pragma unroll
+      for (int e = 0; e < 4; e++) l[e] = lightmap(x + e, y);
+      for (int c = 0; c < C; c++) {
+        const unsigned int wd = reinterpret_cast<const unsigned int*>(O + (long)c * ohow)[i];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          float v = (float)((wd >> (8 * e)) & 255u) / 255.0f;
+          v *= l[e];
+          vmax = fmaxf(vmax, v);
+        }
+      }
+    }
+    vmax = wave_max(vmax);
+    if ((t & 63) == 0) red[t >> 6] = vmax;
+    __syncthreads();
+    vmax = red[0];
+#pragma unroll
+    for (int w = 1; w < OCC_OUT_T / 64; w++) vmax = fmaxf(vmax, red[w]);
+  }
+  for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
+    const int p = i * 4, y = p / ow, x = p - y * ow;
+    float l[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) l[e] = light ? lightmap(x + e, y) : 1.f;
+    for (int c = 0; c < C; c++) {
+      const unsigned int wd = reinterpret_cast<const unsigned int*>(O + (long)c * ohow)[i];
+      f32x4 r;
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        float v = (float)((wd >> (8 * e)) & 255u) / 255.0f;
+        v *= l[e];
+        if (light) v = v / vmax;                      // out_img / out_img.max()  (load_dataset.py:199)
+        r[e] = norm ? (v - 0.5f) / 0.5f : v;
+      }
+      *reinterpret_cast<f32x4*>(img + ((long)n * C + c) * ohow + p) = r;
+    }
+  }
+}
+
+extern "C" int msml_occ_draw_out(long seed, long offset, int N, int H, int W, int out_h, int out_w, int mode, int lo,
+                                 int hi, int flip, const int* meta, int nsets, int* desc, void* stream) {
+  MSML_CHECK(desc && N > 0 && H >= 32 && W >= 32 && out_h > 0 && out_w > 0 && mode >= 0 && mode <= 9 && lo >= 0 &&
+                 hi > lo && hi <= 101, MSML_ERR_SHAPE,
+             "occ_draw_out: bad arguments N=%d H=%d W=%d out=%dx%d mode=%d lo=%d hi=%d", N, H, W, out_h, out_w, mode, lo, hi);
+  MSML_CHECK(mode < 5 || (meta && nsets > 0 && nsets <= 16), MSML_ERR_SHAPE,
+             "occ_draw_out: modes 5-9 need 1..16 occluder sets (got %d)", nsets);
+  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, mode < 5 ? nullptr : meta, mode < 5 ? 0 : nsets, desc, out_h, out_w);
+  MSML_LAUNCH_OK("occ_draw_out");
+  return MSML_OK;
+}
+
+extern "C" int msml_occ_apply_out(const unsigned char* src, const int* desc, const unsigned char* patch,
+                                  long patch_stride, const int* tabw, const int* tabh, float* img, long* msk, float* ori,
+                                  int N, int H, int W, int out_h, int out_w, int gray, int norm, int light, void* stream) {
+  MSML_CHECK(src && desc && img && msk && N > 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0 && H <= 4096 && W <= 4096 &&
+                 out_h <= 4096 && out_w <= 4096 && (patch == nullptr || patch_stride > 0),
+             MSML_ERR_SHAPE, "occ_apply_out: bad arguments N=%d H=%d W=%d out=%dx%d", N, H, W, out_h, out_w);
+  MSML_CHECK((out_w == W || tabw) && (out_h == H || tabh), MSML_ERR_SHAPE,
+             "occ_apply_out: %dx%d -> %dx%d needs the resampling table of every axis that changes", H, W, out_h, out_w);
+  MSML_CHECK(out_w % 4 == 0, MSML_ERR_UNSUPPORTED,
+             "occ_apply_out: output width %d is not a multiple of 4 (16-byte stores)", out_w);
+  const OccOutLds L = occ_out_lds(H, W, out_h, out_w, gray ? 1 : 3);
+  MSML_CHECK(L.total <= 160 * 1024, MSML_ERR_UNSUPPORTED,
+             "occ_apply_out: %dx%d -> %dx%d %s needs %ld bytes of LDS (163840 available)", H, W, out_h, out_w,
+             gray ? "gray" : "RGB", L.total);
+  static int attr_lds = 0;
+  if ((int)L.total > attr_lds) {                // (monotonic; racing callers set the same or a larger value)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_occ_apply_out), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)L.total);
+    attr_lds = (int)L.total;
+  }
+  k_occ_apply_out<<<N, OCC_OUT_T, (size_t)L.total, (hipStream_t)stream>>>(src, desc, patch, patch_stride, tabw, tabh, img, msk, ori, H, W, out_h, out_w, gray, norm, light);
+  MSML_LAUNCH_OK("occ_apply_out");
   return MSML_OK;
 }

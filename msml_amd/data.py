@@ -10,6 +10,10 @@ bottleneck: here the host only hands over decoded uint8 faces (37.6 KB per image
 * `DeviceLoaderX(source, device, ...)`    -- datasets/dataloaderx.py:40-66 semantics: a background thread
   pulls host batches, the next batch is copied on a side stream from pinned memory and augmented there
   while the current step runs, `__next__` makes the compute stream wait for that stream.
+* `gray=True, out_size=128, use_norm=False` on `augment` / `DeviceLoaderX` -- the reference's is_gray / out_size /
+  use_norm switches (load_dataset.py:86-139,179; the LightCNN recipe, config.py:99-102): occlusion at the source size,
+  convert('L'), bilinear Resize of face, mask and clean face, flip, light at the output size, no Normalize -- one
+  kernel, bit for bit in the integer part (msml_occ_apply_out).
 * `SynthFaceSource`                        -- stand-in for the record reader: a pool of random uint8 faces in
   pinned host memory (no dataset travels with this repo).
 """
@@ -38,14 +42,25 @@ def _bicubic(x):
     return 0.0
 
 
-def resample_table(insz, outsz):
-    """Pillow's bicubic resampling coefficients for one axis (Resample.c precompute_coeffs + normalize_coeffs_8bpc,
-    what Image.resize -- the call of rand_occ.py:375,466,562 -- uses): int32 [outsz][10] = first tap, taps, up to 8
-    coefficients in 22-bit fixed point.  Double precision on the host, exactly as the library computes them."""
+def _bilinear(x):
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+_FILTERS = {"bicubic": (_bicubic, 2.0), "bilinear": (_bilinear, 1.0)}      # Resample.c: filter, support
+
+
+def resample_table(insz, outsz, filter="bicubic"):
+    """Pillow's resampling coefficients for one axis (Resample.c precompute_coeffs + normalize_coeffs_8bpc): int32
+    [outsz][10] = first tap, taps, up to 8 coefficients in 22-bit fixed point.  "bicubic" is what Image.resize -- the
+    call of rand_occ.py:375,466,562 -- uses by default; "bilinear" (the triangle filter, support 1) is
+    transforms.Resize on a PIL image (load_dataset.py:117-120).  Double precision on the host, exactly as the library
+    computes them."""
     import numpy as np
+    kernel, support = _FILTERS[filter]
     scale = insz / outsz
     fscale = max(scale, 1.0)
-    support = 2.0 * fscale
+    support = support * fscale
     tab = np.zeros((outsz, RT_WORDS), np.int32)
     for xx in range(outsz):
         center = (xx + 0.5) * scale
@@ -53,7 +68,7 @@ def resample_table(insz, outsz):
         cnt = min(int(center + support + 0.5), insz) - xmin
         if cnt > RT_WORDS - 2:
             raise ValueError("resample_table: %d -> %d needs %d taps (at most %d)" % (insz, outsz, cnt, RT_WORDS - 2))
-        k = [_bicubic((x + xmin - center + 0.5) / fscale) for x in range(cnt)]
+        k = [kernel((x + xmin - center + 0.5) / fscale) for x in range(cnt)]
         ww = 0.0
         for v in k:
             ww += v
@@ -155,14 +170,43 @@ def load_occluder_sets(root):
             ("scarf", folder("scarf_crop", fixed(90, 90))), ("object", folder("object_train", center_crop))]
 
 
-def draw(n, seed, offset, mode="train", lo=0, hi=36, flip=True, size=112, device="cuda", atlas=None):
-    """Per-image occlusion / flip / light descriptors (msml_occ_draw[_tex]), int32 [n, 64] on the device."""
+def _out_hw(out_size, h, w):
+    """out_size as transforms.Resize takes it here: None (the source size), an int (square) or (h, w)."""
+    if out_size is None:
+        return h, w
+    if isinstance(out_size, int):
+        return out_size, out_size
+    oh, ow = out_size
+    return int(oh), int(ow)
+
+
+_OUT_TABLES = {}      # (device, source size, output size) -> the bilinear table of that axis on the device
+
+
+def _out_table(insz, outsz, device):
+    if insz == outsz:
+        return None                                  # ImagingResample skips an axis that keeps its size
+    key = (str(device), insz, outsz)
+    if key not in _OUT_TABLES:
+        _OUT_TABLES[key] = torch.from_numpy(resample_table(insz, outsz, "bilinear")).to(device)
+    return _OUT_TABLES[key]
+
+
+def draw(n, seed, offset, mode="train", lo=0, hi=36, flip=True, size=112, device="cuda", atlas=None, out_size=None):
+    """Per-image occlusion / flip / light descriptors (msml_occ_draw[_tex]), int32 [n, 64] on the device.  out_size:
+    the size the light is added at (msml_occ_draw_out: the light centre is uniform over the OUTPUT image)."""
     desc = torch.empty(n, DESC_WORDS, dtype=torch.int32, device=device)
     if MODES[mode] >= 5:
         if atlas is None:
             raise ValueError("mode %r needs an OccluderAtlas (texture occluders come from the caller's assets)" % mode)
         if atlas.size != size:
             raise ValueError("OccluderAtlas was built for %d-pixel images" % atlas.size)
+    if out_size is not None:
+        oh, ow = _out_hw(out_size, size, size)
+        tex = MODES[mode] >= 5
+        call("msml_occ_draw_out", int(seed), int(offset), n, size, size, oh, ow, MODES[mode], lo, hi, int(flip),
+             atlas.meta if tex else None, atlas.nsets if tex else 0, desc)
+    elif MODES[mode] >= 5:
         call("msml_occ_draw_tex", int(seed), int(offset), n, size, size, MODES[mode], lo, hi, int(flip), atlas.meta,
              atlas.nsets, desc)
     else:
@@ -170,11 +214,27 @@ def draw(n, seed, offset, mode="train", lo=0, hi=36, flip=True, size=112, device
     return desc
 
 
-def apply(src, desc, light=True, want_ori=True, atlas=None):
+def apply(src, desc, light=True, want_ori=True, atlas=None, gray=False, out_size=None, use_norm=True):
     """src: (N, H, W, 3) uint8 on the device -> img (N,3,H,W) f32, msk (N,H,W) int64, ori or None.  atlas: the
-    OccluderAtlas the descriptors were drawn with (texture kinds are resampled per sample, then pasted)."""
+    OccluderAtlas the descriptors were drawn with (texture kinds are resampled per sample, then pasted).
+    gray / out_size / use_norm: the reference's is_gray / out_size / use_norm (msml_occ_apply_out) -- img and ori
+    (N, 1 or 3, oh, ow), in [0, 1] without the normalisation, msk (N, oh, ow); desc drawn with the same out_size."""
     n, h, w, c = src.shape
     assert c == 3 and src.dtype == torch.uint8 and src.is_cuda and src.is_contiguous()
+    if gray or out_size is not None or not use_norm:
+        oh, ow = _out_hw(out_size, h, w)
+        ch = 1 if gray else 3
+        img = torch.empty(n, ch, oh, ow, dtype=torch.float32, device=src.device)
+        ori = torch.empty(n, ch, oh, ow, dtype=torch.float32, device=src.device) if want_ori else None
+        msk = torch.empty(n, oh, ow, dtype=torch.int64, device=src.device)
+        patch, stride = None, 0
+        if atlas is not None:
+            patch, stride = torch.empty(n, atlas.patch_bytes, dtype=torch.uint8, device=src.device), atlas.patch_bytes
+            call("msml_occ_resize", atlas.atlas, atlas.meta, atlas.dir, atlas.rtab, desc, patch, stride, n,
+                 atlas.lds_bytes)
+        call("msml_occ_apply_out", src, desc, patch, stride, _out_table(w, ow, src.device),
+             _out_table(h, oh, src.device), img, msk, ori, n, h, w, oh, ow, int(gray), int(use_norm), int(light))
+        return img, msk, ori
     img = torch.empty(n, 3, h, w, dtype=torch.float32, device=src.device)
     ori = torch.empty(n, 3, h, w, dtype=torch.float32, device=src.device) if want_ori else None
     msk = torch.empty(n, h, w, dtype=torch.int64, device=src.device)
@@ -188,9 +248,10 @@ def apply(src, desc, light=True, want_ori=True, atlas=None):
     return img, msk, ori
 
 
-def augment(src, seed, offset, mode="train", lo=0, hi=36, flip=True, light=True, want_ori=True, atlas=None):
-    desc = draw(src.shape[0], seed, offset, mode, lo, hi, flip, src.shape[1], src.device, atlas)
-    return apply(src, desc, light, want_ori, atlas if MODES[mode] >= 5 else None) + (desc,)
+def augment(src, seed, offset, mode="train", lo=0, hi=36, flip=True, light=True, want_ori=True, atlas=None, gray=False,
+            out_size=None, use_norm=True):
+    desc = draw(src.shape[0], seed, offset, mode, lo, hi, flip, src.shape[1], src.device, atlas, out_size)
+    return apply(src, desc, light, want_ori, atlas if MODES[mode] >= 5 else None, gray, out_size, use_norm) + (desc,)
 
 
 class SynthFaceSource:
@@ -247,11 +308,12 @@ class DeviceLoaderX:
     reproducible whatever the timing."""
 
     def __init__(self, source, local_rank=0, seed=1, mode="train", lo=0, hi=36, flip=True, light=True,
-                 want_ori=True, max_prefetch=6, atlas=None):
+                 want_ori=True, max_prefetch=6, atlas=None, gray=False, out_size=None, use_norm=True):
         self.source, self.local_rank = source, local_rank
         self.stream = torch.cuda.Stream(local_rank)
         self.atlas = atlas                   # OccluderAtlas for the "ms1m" / "casia" mixes (texture occluders)
         self.cfg = (seed, mode, lo, hi, flip, light, want_ori)
+        self.out = (gray, out_size, use_norm)   # the reference's is_gray / out_size / use_norm (LightCNN: True, 128, False)
         self.max_prefetch = max_prefetch
         self.count = 0
         self.batch = None
@@ -274,7 +336,7 @@ class DeviceLoaderX:
             src = faces.to(device=self.local_rank, non_blocking=True)
             lab = label.to(device=self.local_rank, non_blocking=True)
             img, msk, ori, _ = augment(src, seed, self.count * faces.shape[0], mode, lo, hi, flip, light, want_ori,
-                                       self.atlas)
+                                       self.atlas, *self.out)
         self.count += 1
         self.batch = (img, msk, ori, lab, src)
 
