@@ -681,6 +681,31 @@ int msml_pair_cosdist_f64(const double* emb, int n_pairs, int E, double* dist, v
  * (strict != 0) or <= q[j]; sorted ascending [n], q [m]. */
 int msml_rank_count(const double* sorted, int n, const double* q, int m, int strict, int* out, void* stream);
 
+/* ---------------------------------------------------------------- face alignment of the template evaluation ---
+ * The per-image work of Embedding.get (eval/qeval_ijbc.py:145-187) after the transform estimate, for N decoded
+ * sources of any size in one launch.
+ *
+ * msml_align_warp: cv2.warpAffine(rimg, M, (out_w, out_h), borderValue=0.0) (eval/qeval_ijbc.py:161-163) followed by
+ *   cv2.cvtColor(BGR2RGB) (:164) when swap_rb != 0.  src: every source back to back, H x W x 3 uint8 with a row
+ *   pitch; meta [N][4] int64 = {byte offset in src, H, W, pitch in bytes}, H and W in 1..32767 (the CALLER checks
+ *   that every image lies inside src: the library cannot).  minv [N][6] f64: the INVERSE map (dst -> src), inverted
+ *   on the host in OpenCV's order of operations.  dst [N][out_h][out_w][3] uint8, 4-byte aligned.  The arithmetic is
+ *   that of OpenCV's classic warpAffine + remap (INTER_LINEAR, BORDER_CONSTANT 0), written out: adelta[x] =
+ *   sat(rint(minv0 x 1024)), bdelta[x] with minv3; per row X0 = sat(rint((minv1 y + minv2) 1024)) + 16, Y0 with
+ *   minv4, minv5; X = (X0 + adelta[x]) >> 5, Y likewise; source pixel (X >> 5, Y >> 5) clamped to int16, fractions
+ *   X & 31, Y & 31; weights (32-fx)(32-fy)32, fx(32-fy)32, (32-fx)fy 32, fx fy 32 (sum 32768); a tap outside the
+ *   image counts 0; result (sum + 16384) >> 15.  rint rounds half to even, sat clamps to int32 in f64 before the
+ *   conversion, the integer additions wrap in 32 bits.  MSML_ERR_UNSUPPORTED before any launch for out_w % 4 != 0,
+ *   out_h or out_w outside 4..256, N < 1.
+ * msml_align_pairs: faces [N][H][W][3] uint8 RGB -> out [2N][3][H][W] f32: row 2i = (v / 255 - 0.5) / 0.5 in the three
+ *   f32 steps of forward_db (eval/qeval_ijbc.py:192) of face i with the block of its descriptor painted black
+ *   (RandomBlock, :166-173), row 2i + 1 its horizontal mirror (np.fliplr, :181-187).  desc: msml_occ_draw's 64-word
+ *   descriptors or NULL; kind 0 (none) and kind 3 (block, words 1-4 = x0, y0, w, h) are accepted, any other kind
+ *   fills the image's two rows with NaN.  W a multiple of 4. */
+int msml_align_warp(const unsigned char* src, const long* meta, const double* minv, unsigned char* dst, int N,
+                    int out_h, int out_w, int swap_rb, void* stream);
+int msml_align_pairs(const unsigned char* faces, const int* desc, float* out, int N, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,12 @@ def try_call(name, *args):
     return rc
 
 
+def call_status(name, *args):
+    """Like call(), but returns the status code whatever it is and never raises: for checking an entry point's refusals."""
+    rc, _ = _invoke(name, args)
+    return rc
+
+
 def value(name, *args):
     """Call a pure query function (tile sizes, workspace sizes) and return its result."""
     lib = load()

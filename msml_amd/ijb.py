@@ -7,6 +7,10 @@
 * `pair_scores(...)`: cosine of every listed template pair (`verification`, :343-369).
 * `roc_table(scores, labels)`: the TPR @ FPR table and the AUC (:565-585) of `roc_curve(label, score)`.
 * `evaluate_templates(...)` chains them.
+* `align_matrices` / `pack_images` / `align_faces` / `pair_inputs` / `eval_inputs` / `align_and_embed`: the step in
+  front of them, `Embedding.get` and `get_image_feature` (:145-187, :242-297): the 5-point similarity estimate on the
+  host, then warp, colour swap, block occlusion, mirror and normalisation on the device (csrc/align.hip), from decoded
+  images and landmarks to the `[N][2E]` features.
 
 Inputs may be numpy arrays or CUDA tensors; features and scores stay on the device, the small tables come back as
 numpy.  Sums are f64 in a fixed order: two runs give the same bits.
@@ -249,4 +253,212 @@ def evaluate_templates(img_feats, templates, medias, p1, p2, label, faceness=Non
         raise ValueError("evaluate_templates: no scores")
     out["scores"] = _mean_scores(scores)
     out["tprs"], out["auc"] = roc_table(out["scores"], label, fprs)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Step 2 of the script, Embedding.get + the staging of get_image_feature (qeval_ijbc.py:145-187, 257-293): transform
+# estimate on the host, warp / colour swap / block occlusion / mirror / normalisation on the device (csrc/align.hip).
+
+def _dst_points():
+    """The `src` table of qeval_ijbc.py:90-96 as the script builds it: float32, +8 on x in float32."""
+    p = np.array([[30.2946, 51.6963], [65.5318, 51.5014], [48.0252, 71.7366], [33.5493, 92.3655], [62.7299, 92.2041]],
+                 dtype=np.float32)
+    p[:, 0] += 8.0
+    return p.astype(np.float64)
+
+
+def align_matrices(landmarks, out_size=112):
+    """Host side (numpy f64, no GPU): the 2 x 3 matrix tform.params[0:2] of SimilarityTransform.estimate(landmark5,
+    src) (qeval_ijbc.py:158-160) of every image, [N][2][3] float64.
+
+    landmarks [N][5][2] or [N][68][2] (one image: [5][2] / [68][2]); 68 points are reduced as :149-155 do, in the
+    dtype they come in.  The estimate is skimage's _umeyama with scale, batched: covariance dst_demean.T @ src_demean
+    / n, SVD, the det < 0 sign fix, the rank cases, scale = (S . d) / src_demean.var(0).sum().  The destination points
+    are those of a 112 x 112 crop; out_size scales them (112 leaves them as they are).  ValueError naming the row for
+    non-finite landmarks and for points that all coincide (rank 0, where skimage returns NaN)."""
+    lm = np.asarray(landmarks)
+    if lm.ndim == 2:
+        lm = lm[None]
+    if lm.ndim != 3 or lm.shape[1] not in (5, 68) or lm.shape[2] != 2 or lm.shape[0] == 0:
+        raise ValueError("landmarks %s are not [N][5][2] or [N][68][2]" % (tuple(lm.shape),))
+    if not np.issubdtype(lm.dtype, np.floating):
+        lm = lm.astype(np.float64)
+    if lm.shape[1] == 68:
+        lm = np.stack([(lm[:, 36] + lm[:, 39]) / 2, (lm[:, 42] + lm[:, 45]) / 2, lm[:, 30], lm[:, 48], lm[:, 54]], 1)
+    src = lm.astype(np.float64)
+    bad = np.flatnonzero(~np.isfinite(src).all((1, 2)))
+    if bad.size:
+        raise ValueError("landmarks of row %d are not finite" % bad[0])
+    dst = _dst_points() * (float(out_size) / 112.0)
+    n, num = src.shape[0], src.shape[1]
+    src_mean, dst_mean = src.mean(1), dst.mean(0)
+    sd, dd = src - src_mean[:, None], dst - dst_mean
+    a = np.matmul(dd.T[None], sd) / num                          # [N][2][2]
+    u, s, vt = np.linalg.svd(a)
+    rank = (s > s.max(1, keepdims=True) * (2 * np.finfo(np.float64).eps)).sum(1)
+    bad = np.flatnonzero(rank == 0)
+    if bad.size:
+        raise ValueError("landmarks of row %d coincide: no similarity transform (rank 0)" % bad[0])
+    d = np.ones((n, 2))
+    d[np.linalg.det(a) < 0, 1] = -1.0
+    # rank 1: U @ V when det(U) det(V) > 0, else the last sign is -1 for the rotation (the scale keeps d)
+    dr = d.copy()
+    low = rank == 1
+    if low.any():
+        pos = np.linalg.det(u) * np.linalg.det(vt) > 0
+        dr[low & pos] = 1.0
+        dr[low & ~pos, 1] = -1.0
+    rot = np.matmul(u * dr[:, None, :], vt)
+    scale = (s * d).sum(1) / sd.var(1).sum(1)
+    m = np.empty((n, 2, 3))
+    m[:, :, 2] = dst_mean - scale[:, None] * np.matmul(rot, src_mean[:, :, None])[:, :, 0]
+    m[:, :, :2] = rot * scale[:, None, None]
+    return m
+
+
+def pack_images(images):
+    """images: a list of H x W x 3 uint8 arrays as cv2.imread returns them (BGR, any sizes, any strides).  Returns
+    (buf, meta): one uint8 tensor holding them back to back (pinned when a GPU is present), and meta [N][4] int64 numpy =
+    byte offset (a multiple of 4), H, W, row pitch in bytes.  Refuses an empty list, other dtypes, a channel count
+    other than 3 and H or W outside 1..32767 (cv2 saturates source coordinates to int16; that is not emulated)."""
+    if not isinstance(images, (list, tuple)) or len(images) == 0:
+        raise ValueError("pack_images: needs a non-empty list of images")
+    meta = np.empty((len(images), 4), np.int64)
+    off = 0
+    for i, im in enumerate(images):
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8:
+            raise ValueError("pack_images: image %d is not a uint8 array" % i)
+        if im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError("pack_images: image %d has shape %s, not H x W x 3" % (i, tuple(im.shape)))
+        h, w = im.shape[:2]
+        if not (1 <= h <= 32767 and 1 <= w <= 32767):
+            raise ValueError("pack_images: image %d is %d x %d, outside 1..32767" % (i, h, w))
+        meta[i] = (off, h, w, 3 * w)
+        off += (h * w * 3 + 3) & ~3
+    buf = torch.empty(off, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    flat = buf.numpy()
+    for i, im in enumerate(images):
+        o, h, w, _ = meta[i]
+        flat[o:o + h * w * 3].reshape(h, w, 3)[...] = im
+    return buf, meta
+
+
+def invert_matrices(matrices):
+    """[N][2][3] forward maps (src -> dst) -> [N][6] f64 inverse maps, in cv2.warpAffine's order of operations."""
+    m = np.array(matrices, dtype=np.float64).reshape(-1, 6)
+    if not np.isfinite(m).all():
+        raise ValueError("transform %d is not finite" % np.flatnonzero(~np.isfinite(m).all(1))[0])
+    det = m[:, 0] * m[:, 4] - m[:, 1] * m[:, 3]
+    with np.errstate(divide="ignore"):
+        det = np.where(det != 0, 1.0 / det, 0.0)
+    a11, a22 = m[:, 4] * det, m[:, 0] * det
+    m[:, 0], m[:, 1], m[:, 3], m[:, 4] = a11, m[:, 1] * -det, m[:, 3] * -det, a22
+    b1 = -m[:, 0] * m[:, 2] - m[:, 1] * m[:, 5]
+    b2 = -m[:, 3] * m[:, 2] - m[:, 4] * m[:, 5]
+    m[:, 2], m[:, 5] = b1, b2
+    return m
+
+
+def _out_hw(out_size):
+    if isinstance(out_size, (int, np.integer)):
+        return int(out_size), int(out_size)
+    oh, ow = out_size
+    return int(oh), int(ow)
+
+
+@torch.no_grad()
+def align_faces(buf, meta, matrices, out_size=112, bgr=True):
+    """cv2.warpAffine(img, M, (s, s), borderValue=0.0) + cvtColor(BGR2RGB) (qeval_ijbc.py:161-164) of every packed
+    source in one launch (msml_align_warp) -> uint8 [N][s][s][3] on the device.  buf / meta: pack_images' result (buf
+    on the host or already on the device); matrices [N][2][3]: align_matrices' result; out_size: s or (h, w);
+    bgr=False leaves the channel order alone.  meta is checked on the host against buf.numel() before anything is
+    uploaded: offsets, pitch >= 3 W, sizes in 1..32767, the last byte of every image inside the buffer."""
+    if not (isinstance(buf, torch.Tensor) and buf.dtype == torch.uint8 and buf.dim() == 1 and buf.is_contiguous()):
+        raise ValueError("align_faces: buf must be a contiguous 1-D uint8 tensor")
+    mt = meta.cpu().numpy() if isinstance(meta, torch.Tensor) else np.asarray(meta)
+    if mt.ndim != 2 or mt.shape[1] != 4 or mt.shape[0] == 0 or not np.issubdtype(mt.dtype, np.integer):
+        raise ValueError("align_faces: meta must be [N][4] integers")
+    mt = np.ascontiguousarray(mt, dtype=np.int64)
+    n = mt.shape[0]
+    off, h, w, pitch = mt[:, 0], mt[:, 1], mt[:, 2], mt[:, 3]
+    size_ok = (h >= 1) & (h <= 32767) & (w >= 1) & (w <= 32767)
+    ok = size_ok & (off >= 0) & (off % 4 == 0) & (pitch >= 3 * w) & (pitch < 2 ** 31)
+    ok &= off + (h - 1) * pitch + 3 * w <= buf.numel()
+    if not ok.all():
+        i = int(np.flatnonzero(~ok)[0])
+        raise ValueError("align_faces: meta row %d (offset %d, %d x %d, pitch %d) does not describe an image inside "
+                         "the %d-byte buffer" % (i, off[i], h[i], w[i], pitch[i], buf.numel()))
+    minv = invert_matrices(matrices)
+    if minv.shape[0] != n:
+        raise ValueError("align_faces: %d matrices for %d images" % (minv.shape[0], n))
+    oh, ow = _out_hw(out_size)
+    src = buf if buf.is_cuda else buf.to("cuda", non_blocking=True)
+    dst = torch.empty(n, oh, ow, 3, dtype=torch.uint8, device=src.device)
+    call("msml_align_warp", src, _dev(mt, None, src.device), _dev(minv, None, src.device), dst, n, oh, ow,
+         1 if bgr else 0)
+    return dst
+
+
+@torch.no_grad()
+def pair_inputs(faces, desc=None):
+    """faces uint8 [N][H][W][3] RGB on the device, desc: data.draw's descriptors (kinds none / block) or None ->
+    f32 [2N][3][H][W]: row 2i the normalised face with its block painted black, row 2i + 1 its mirror
+    (msml_align_pairs): the batch Embedding.get and forward_db hand to the model (qeval_ijbc.py:181-192)."""
+    if not (isinstance(faces, torch.Tensor) and faces.is_cuda and faces.dtype == torch.uint8 and faces.dim() == 4
+            and faces.shape[3] == 3 and faces.is_contiguous()):
+        raise ValueError("pair_inputs: faces must be a contiguous uint8 [N][H][W][3] tensor on the device")
+    n, h, w, _ = faces.shape
+    if desc is not None:
+        if not (desc.is_cuda and desc.dtype == torch.int32 and tuple(desc.shape) == (n, 64) and desc.is_contiguous()):
+            raise ValueError("pair_inputs: desc must be int32 [%d][64] on the device" % n)
+        kind = desc[:, 0]
+        if bool(((kind != 0) & (kind != 3)).any()):
+            raise ValueError("pair_inputs: only block (3) and none (0) descriptors are supported")
+    out = torch.empty(2 * n, 3, h, w, dtype=torch.float32, device=faces.device)
+    call("msml_align_pairs", faces, desc, out, n, h, w)
+    return out
+
+
+@torch.no_grad()
+def eval_inputs(faces, seed=1, offset=0, lo=0, hi=1):
+    """RandomBlock(lo, hi) (the script's --lo / --hi, qeval_ijbc.py:166-173) on every aligned face, then pair_inputs.
+    lo = hi = None skips the occlusion.  The block's size and place come from the project's counter-based generator
+    (data.draw(mode="block"): a function of seed and offset + row, as in the training pipeline), NOT from numpy's
+    global RNG as in the reference: the same (seed, offset) gives the same blocks on any batch split, and no run
+    reproduces the reference's draws."""
+    if lo is None and hi is None:
+        return pair_inputs(faces, None)
+    from . import data
+    if faces.shape[1] != faces.shape[2]:
+        raise ValueError("eval_inputs: RandomBlock needs square faces, got %d x %d" % (faces.shape[1], faces.shape[2]))
+    desc = data.draw(faces.shape[0], seed, offset, mode="block", lo=int(lo), hi=int(hi), flip=False,
+                     size=faces.shape[1], device=faces.device)
+    return pair_inputs(faces, desc)
+
+
+@torch.no_grad()
+def align_and_embed(model, images, landmarks, batch=64, lo=0, hi=1, seed=1, out_size=112):
+    """get_image_feature (qeval_ijbc.py:242-297) without its per-image loop: images (a list of cv2.imread results) and
+    their landmarks ([N][5][2] or [N][68][2]) -> img_feats [N][2E] f32 on the device, embedding | embedding of the
+    mirrored face, which evaluate_templates takes as it is.  `batch` images per launch: packed, uploaded, warped,
+    occluded + mirrored + normalised, embedded.  Image i draws its block from (seed, i) whatever the batch size (the
+    project's counter-based generator, not numpy's global RNG: see eval_inputs)."""
+    n = len(images)
+    m = align_matrices(landmarks, out_size)
+    if m.shape[0] != n:
+        raise ValueError("align_and_embed: %d images but %d landmark sets" % (n, m.shape[0]))
+    batch = max(1, int(batch))
+    out = None
+    for i0 in range(0, n, batch):
+        i1 = min(n, i0 + batch)
+        buf, meta = pack_images(images[i0:i1])
+        faces = align_faces(buf, meta, m[i0:i1], out_size)
+        f = model(eval_inputs(faces, seed, i0, lo, hi))
+        if isinstance(f, (tuple, list)):
+            f = f[0]
+        f = f.float().reshape(i1 - i0, -1)
+        if out is None:
+            out = torch.empty(n, f.shape[1], dtype=torch.float32, device=f.device)
+        out[i0:i1] = f
     return out
