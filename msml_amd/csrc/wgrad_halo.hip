@@ -11,11 +11,13 @@
 // one strip row (16 pixels); tap (r, s) reads the X image r rows down and s pixels right, which
 // is a per-lane offset in the blocked image [row][32-channel group][16 px][64 B] (the layout
 // whose transposing ds_read_b64_tr_b16 blocks are conflict-free, see wgrad_fast.hip).
-// 8 waves: wave = (pair of 32-row Cout tiles, 32-column Cin half, tap group {0-4} / {5-8}): 10 or 8
-// accumulator tiles; per k-step 2 dY fragments + 5 (4) X fragments feed 10 (8) MFMAs -- 1.4 LDS
-// fragment reads per MFMA (one Cout tile x 9 taps per wave needed 2.2 and was LDS-read bound).
-// Waves w and w + 4 share a SIMD and carry one tap group each, so every SIMD runs 18 MFMAs per
-// k-step.
+// 8 waves.  128-row tile: wave = (one of four 32-row Cout tiles, 32-column Cin half) with all 9 taps: 9 accumulator
+// tiles; a k-step reads one dY fragment and the three X fragments (column shifts 0, 1, 2) of halo row j + 2 -- rows j
+// and j + 1 are still in registers from the two k-steps before -- for 9 MFMAs: 34 fragment reads per strip and wave.
+// 64-row tile: wave = (32-row Cout tile, Cin half, tap group {0-4} / {5-8}): 5 or 4 accumulator tiles, 1 dY + 5 (4) X
+// fragments per k-step.  Waves w and w + 4 share a SIMD; every SIMD runs 18 (64-row tile: 9) MFMAs per k-step.
+// The strips are double-buffered: strip s + 1 is requested (LDS-DMA) at the top of strip s and must land behind the
+// MFMAs of strip s, see wh_dma16.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -29,6 +31,27 @@ typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
 #define WH_OOB 0x78000000u
+
+// One 1-KB LDS-DMA block (16 B per lane).  Issued from an asm statement so that hipcc does not count it: after a
+// __builtin_amdgcn_raw_ptr_buffer_load_lds it cannot tell the ring slots apart and puts s_waitcnt vmcnt(0) in front of
+// the next ds_read -- the strip requested at the top of the loop then lands BEFORE the first fragment read of the
+// current strip instead of behind its MFMAs.  The kernel waits for these requests itself (wh_dma_wait) before the
+// barrier that publishes a slot.  M0 (the LDS destination) belongs to the compiler: saved and restored.
+typedef __attribute__((ext_vector_type(4))) unsigned int wh_rsrc_t;
+__device__ __forceinline__ void wh_dma16(const wh_rsrc_t& rs, unsigned int lds, unsigned int off) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  unsigned int keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(off), "s"(rs), "s"(lds)
+               : "memory");
+#endif
+}
+__device__ __forceinline__ void wh_dma_wait() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+}
 
 #define WH_MAXGROUP 8
 struct WgradHaloArgs {
@@ -58,7 +81,10 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   MSML_LDS_REGION(smem, 2 * STAGE + (XF ? 3 * 64 * 4 : 0));
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int mp = wave & 1, nh = (wave >> 1) & 1, tg = wave >> 2;   // Cout tile pair, Cin half, tap group
+  // 128-row tile: wave = (one of four 32-row Cout tiles, Cin half), all nine taps; the X fragments of a halo row are
+  // read once and serve three k-steps from registers.  64-row tile: wave = (Cout tile, Cin half, tap group).
+  constexpr bool R9 = CO == 128;
+  const int mp = R9 ? (wave & 3) : (wave & 1), nh = R9 ? (wave >> 2) : ((wave >> 1) & 1), tg = R9 ? 0 : (wave >> 2);
   // Several layers of one shape share a launch (grid.z = layers x zper): the split-K slab traffic per layer falls
   // with the number of workgroups a layer gets.  XCD-aware order: hardware deals consecutive workgroups round-robin
   // to the 8 XCDs; re-numbering them so that the gx * gy dW tiles of one z (same dY / X strips) sit on ONE XCD
@@ -80,8 +106,20 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   if (s_end > p.nstrips) s_end = p.nstrips;
   const int spi = p.spy * p.spx;
 
-  __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc((void*)p.u[layer], 0, (int)p.u_bytes, 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc((void*)p.v[layer], 0, (int)p.v_bytes, 0x00020000);
+  auto make_rsrc = [](const void* ptr, unsigned int bytes) -> wh_rsrc_t {
+    const unsigned long long a = (unsigned long long)ptr;
+    wh_rsrc_t r;
+    r[0] = __builtin_amdgcn_readfirstlane((unsigned int)a);
+    r[1] = __builtin_amdgcn_readfirstlane((unsigned int)(a >> 32) & 0xffffu);
+    r[2] = __builtin_amdgcn_readfirstlane(bytes);
+    r[3] = 0x00020000u;
+    return r;
+  };
+  const wh_rsrc_t rs_u = make_rsrc(p.u[layer], p.u_bytes), rs_v = make_rsrc(p.v[layer], p.v_bytes);
+  const unsigned int lds0 = __builtin_amdgcn_readfirstlane((unsigned int)(size_t)(lptr_t)smem);
+  auto dma = [&](const wh_rsrc_t& rs, const char* dst, unsigned int off) {
+    wh_dma16(rs, lds0 + (unsigned int)__builtin_amdgcn_readfirstlane((int)(dst - smem)), off);
+  };
 
   // DMA slot of a lane inside a 1-KB block [16 px][64 B]: pixel lane / 4, 16-B chunk lane % 4
   const int lp = lane >> 2, lc = lane & 3;
@@ -105,7 +143,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
           const unsigned int off = (img & (x < 7)) ? (unsigned int)((n * 7 + j) * 7 + x) * (unsigned int)(p.up * 2) +
                                                          (unsigned int)(a0 + g * 32 + lc * 8) * 2u
                                                    : WH_OOB;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_u, (lptr_t)(ub + blk * 1024), 16, off, 0, 0, 0);
+          dma(rs_u, ub + blk * 1024, off);
         } else {
           const int bb = blk - UBLK, hr = bb >> 1, g = bb & 1;
           const int y = hr - 1;                          // halo columns 0 and 8 (x == 0) are the zero padding
@@ -113,7 +151,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
           const unsigned int off = ok ? (unsigned int)((n * 7 + y) * 7 + x - 1) * (unsigned int)(p.vp * 2) +
                                             (unsigned int)(b0 + g * 32 + lc * 8) * 2u
                                       : WH_OOB;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_v, (lptr_t)(vb + bb * 1024), 16, off, 0, 0, 0);
+          dma(rs_v, vb + bb * 1024, off);
         }
       }
       return;
@@ -131,7 +169,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         const unsigned int off = ok ? (unsigned int)((n * p.H + y) * p.W + x) * (unsigned int)(p.up * 2) +
                                           (unsigned int)(a0 + g * 32 + lc * 8) * 2u
                                     : WH_OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_u, (lptr_t)(ub + blk * 1024), 16, off, 0, 0, 0);
+        dma(rs_u, ub + blk * 1024, off);
       } else {
         const int bb = blk - UBLK, hr = bb >> 1, g = bb & 1;
         const int y = y0 + hr - 1, x = x0 + lp - 1;
@@ -139,7 +177,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         const unsigned int off = ok ? (unsigned int)((n * p.H + y) * p.W + x) * (unsigned int)(p.vp * 2) +
                                           (unsigned int)(b0 + g * 32 + lc * 8) * 2u
                                     : WH_OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_v, (lptr_t)(vb + bb * 1024), 16, off, 0, 0, 0);
+        dma(rs_v, vb + bb * 1024, off);
       }
     }
   };
@@ -164,11 +202,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     }
   };
 
-  f32x16 acc[NI][5];                                   // [Cout tile of the wave][tap of the group]
+  constexpr int NA = R9 ? 1 : NI, NK = R9 ? 9 : 5;
+  f32x16 acc[NA][NK];                                  // [Cout tile of the wave][tap of the group]
 #pragma unroll
-  for (int i = 0; i < NI; i++)
+  for (int i = 0; i < NA; i++)
 #pragma unroll
-    for (int k = 0; k < 5; k++)
+    for (int k = 0; k < NK; k++)
 #pragma unroll
       for (int e = 0; e < 16; e++) acc[i][k][e] = 0.f;
 
@@ -177,7 +216,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   const int g4 = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, pp = i16 & 3;
   const int px = 8 * (g4 >> 1) + q4;
   const int chan = (2 * (g4 & 1) + (pp >> 1)) * 16 + (pp & 1) * 8;
-  const int aofs = mp * NI * 1024 + px * 64 + chan;    // + row * GU KB, + 1024 for a pair's second tile (+ 256: second read)
+  const int aofs = mp * NA * 1024 + px * 64 + chan;    // + row * GU KB, + 1024 for a pair's second tile (+ 256: second read)
   // X: pixel px + s of halo row (row + r); past pixel 15 it continues in the next row's block
   int vlo[3], vhi[3];
 #pragma unroll
@@ -187,7 +226,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     vhi[s] = nh * 1024 + (p1 >> 4) * 2048 + (p1 & 15) * 64 + chan;
   }
   // offsets of this wave's taps (wave-uniform choice among the three column shifts, row shift folded in)
-  const int ntaps = tg == 0 ? 5 : 4, tap0 = tg * 5;
+  const int ntaps = R9 ? 9 : (tg == 0 ? 5 : 4), tap0 = tg * 5;
   int vlok[5], vhik[5];
 #pragma unroll
   for (int k = 0; k < 5; k++) {
@@ -207,23 +246,60 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 
   if (s_begin < s_end) issue(s_begin, 0);
   if (XF) bn_in_fill(p.xin, xtab, b0, 64, t, 512);
+  wh_dma_wait();
   __syncthreads();
   if (XF) {
     if (s_begin < s_end) xform(s_begin, 0);
     __syncthreads();
   }
   int cur = 0;
-  s16x8 fa[2][NI], fb5[2][5];
+  s16x8 fa[2][NA], fb5[2][5], xr[4][3];
   for (int strip = s_begin; strip < s_end; strip++) {
     if (strip + 1 < s_end) issue(strip + 1, cur ^ 1);
     const char* ub = smem + cur * STAGE + aofs;
     const char* vb = smem + cur * STAGE + UB;
+    if constexpr (R9) {
+      // k-step j multiplies dY row j with X halo rows j, j + 1, j + 2 at the three column shifts; rows j and j + 1
+      // are the registers read one and two k-steps ago (xr[row & 3], the loop is unrolled: renaming, no moves).
+      // dY row j + 1 and X row j + 3 are requested before the MFMAs of k-step j.
+      auto fetch_a = [&](int j) { fa[j & 1][0] = tr2(ub + j * (GU * 1024), ub + j * (GU * 1024) + 256); };
+      auto fetch_x = [&](int row) {
+#pragma unroll
+        for (int sft = 0; sft < 3; sft++) xr[row & 3][sft] = tr2(vb + row * 2048 + vlo[sft], vb + row * 2048 + vhi[sft]);
+      };
+      fetch_a(0);
+      fetch_x(0);
+      fetch_x(1);
+      fetch_x(2);
+#pragma unroll
+      for (int j = 0; j < 7; j++) {
+        if (j + 1 < 7) {
+          fetch_a(j + 1);
+          fetch_x(j + 3);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < 9; k++)
+          acc[0][k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[j & 1][0]),
+                                                              __builtin_bit_cast(bf16x8, xr[(j + k / 3) & 3][k % 3]),
+                                                              acc[0][k], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (XF && j == 6 && strip + 1 < s_end) {         // (as below: the next strip's own X chunks, normalised in LDS)
+          wh_dma_wait();
+          xform(strip + 1, cur ^ 1);
+        }
+      }
+      wh_dma_wait();
+      __syncthreads();
+      cur ^= 1;
+      continue;
+    }
     // taps tap0 + k, k < ntaps, of this wave's group.  All fragments of k-step j + 1 are requested
     // before the MFMAs of k-step j (register double buffer); the fences keep hipcc from sinking the
     // reads next to their MFMAs.
     auto fetch = [&](int j, int fb) {
 #pragma unroll
-      for (int i = 0; i < NI; i++)
+      for (int i = 0; i < NA; i++)
         fa[fb][i] = tr2(ub + j * (GU * 1024) + i * 1024, ub + j * (GU * 1024) + i * 1024 + 256);
 #pragma unroll
       for (int k = 0; k < 5; k++)
@@ -239,7 +315,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
       for (int k = 0; k < 5; k++)
         if (k < ntaps) {
 #pragma unroll
-          for (int i = 0; i < NI; i++)
+          for (int i = 0; i < NA; i++)
             acc[i][k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[fb][i]),
                                                                 __builtin_bit_cast(bf16x8, fb5[fb][k]), acc[i][k], 0, 0, 0);
         }
@@ -252,6 +328,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         xform(strip + 1, cur ^ 1);
       }
     }
+    wh_dma_wait();
     __syncthreads();
     cur ^= 1;
   }
@@ -260,13 +337,13 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   const int h = lane >> 5, c32 = lane & 31;
   const int b = b0 + nh * 32 + c32;
 #pragma unroll
-  for (int i = 0; i < NI; i++)
+  for (int i = 0; i < NA; i++)
 #pragma unroll
-    for (int k = 0; k < 5; k++) {
+    for (int k = 0; k < NK; k++) {
       if (k >= ntaps) continue;
 #pragma unroll
       for (int e = 0; e < 16; e++) {
-        const int a = a0 + (mp * NI + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int a = a0 + (mp * NA + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
         p.ws[(((long)bz * p.up + a) * 9 + tap0 + k) * p.vp + b] = acc[i][k][e];
       }
     }
