@@ -706,6 +706,37 @@ int msml_align_warp(const unsigned char* src, const long* meta, const double* mi
                     int out_h, int out_w, int swap_rb, void* stream);
 int msml_align_pairs(const unsigned char* faces, const int* desc, float* out, int N, int H, int W, void* stream);
 
+/* ---------------------------------------------------------------- test.py evaluation inputs ------------------
+ * msml_eval_pairs: the per-image loop of _load_one_input (eval/qeval_mxnet.py:173-189, run 2 x num times per
+ *   extraction by start_extract, :302-312) and the normalisation of :319-324 for N decoded faces in one launch.
+ *   src [N][H][W][3] uint8 RGB (one size per call), out [2N][C][out_h][out_w] f32 with C = 1 when gray, else 3: row 2i
+ *   is image i, row 2i + 1 its mirrored copy.  Per row, in the reference's order:
+ *   1. rows 2i + 1 only: transpose(FLIP_LEFT_RIGHT) of the SOURCE, before any crop (:175-176);
+ *   2. CenterCrop((out_h, out_w)) (:178-180) with the arithmetic of torchvision's center_crop: an axis shorter than
+ *      the output is first padded with zeros, (out - in) / 2 on the left / top and (out - in + 1) / 2 on the right /
+ *      bottom; the crop origin of the other axes is int(round((in - out) / 2.0)) with Python's round (half to even:
+ *      a difference of 1 gives 0, 3 gives 2, 5 gives 2), so mirror-then-crop is not crop-then-mirror;
+ *   3. gray != 0: Grayscale() (:97-101), L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16;
+ *   4. RandomBlock (:544-547, datasets/augment/rand_occ.py:43-72) from the row's descriptor desc[2i + f] (msml_occ_draw's
+ *      64 words: kind 0 = none, kind 3 = block with words 1-4 = x0, y0, w, h in OUTPUT coordinates, cropped at the
+ *      border as Image.paste crops; any other kind fills that row with NaN).  protocol 0 (BB): every row; protocol 1
+ *      (NB, :184-187): rows of images with an odd global index index0 + i skip this step, descriptor unread.
+ *      desc = NULL: no occlusion.  fill 0 black, 1 white (255), 2 gauss: every block pixel (every channel for RGB)
+ *      draws a standard normal z = sqrt(-2 ln u1) cos(2 pi u2) in f64, u1 = (hi32(r) + 1) / 2^32, u2 = lo32(r) / 2^32,
+ *      r = mix(mix(mix(seed + 0x6761757373) + 2 (index0 + i) + f) + ((y - y0) 256 + (x - x0)) 4 + channel) with
+ *      mix = the splitmix64 step of msml_occ_draw.  The byte follows rand_occ.py:56-64.  RGB: (z * 255).astype(uint8),
+ *      DEFINED here as truncation toward zero, then wrap modulo 256 (what numpy does on x86-64; the cast of a
+ *      negative or out-of-range float to uint8 is otherwise undefined).  Gray: Image.paste of the mode-F block into
+ *      the L image, which Pillow converts as: round z * 255 to f32; <= 0 gives 0, >= 255 gives 255, else truncate;
+ *   5. ToTensor: v / 255 as one f32 division;
+ *   6. norm != 0: sub_(0.5) then div_(0.5), two f32 steps (:319-324).
+ *   No atomics, one writer per element: two runs give the same bits.  MSML_ERR_SHAPE for null src / out, misaligned
+ *   pointers (src, desc 4 bytes, out 16) or index0 < 0; MSML_ERR_UNSUPPORTED before any launch for N < 1,
+ *   out_w % 4 != 0, H, W, out_h or out_w outside 4..256, fill outside 0..2, protocol outside 0..1, and NB with gray
+ *   (the reference's own NB path puts a 3-channel tensor into the 1-channel batch and raises). */
+int msml_eval_pairs(const unsigned char* src, int N, int H, int W, const int* desc, float* out, int out_h, int out_w,
+                    int gray, int norm, int fill, int protocol, long seed, long index0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,9 @@ eval/qeval_mxnet.py:326-390 uses the same orig + flip sum).
   pairs in numpy; here ONE kernel computes the f64 pair distances and ONE builds a [fold][same][threshold]
   histogram (integer atomics, deterministic), from which every confusion-matrix entry of every threshold
   and fold is a prefix sum -- the remaining arithmetic is on a table of a few thousand integers.
+* `eval_pairs` / `extract_sum` / `occlusion_sweep`: test.py itself (eval/qeval_mxnet.py:486-600) -- the model inputs
+  of one extraction in one launch (msml_eval_pairs), the orig + mirror feature sum, and the loop over occlusion
+  levels and repeats that prints the paper's table.
 """
 import numpy as np
 import torch
@@ -196,3 +199,128 @@ def roc_accuracy_tarfar(emb, issame):
     thr = neg_sorted[torch.tensor(thr_idx, device=dist.device)].contiguous()
     tarfar[:4] = _rank(pos_sorted, thr, False) / cnt
     return acc, tarfar
+
+
+# ---------------------------------------------------------------------------------------------- test.py
+FILLS = {"black": 0, "white": 1, "gauss": 2}        # --fill_type (rand_occ.py:25-72)
+PROTOCOLS = {"BB": 0, "NB": 1}                      # _load_one_input's protocol (qeval_mxnet.py:184-187)
+LEVELS = tuple((lo, lo + 1) for lo in range(0, 100, 10))      # lo_list / hi_list of qeval_mxnet.py:528-529
+
+
+def _no_block(lo, hi):
+    return (lo is None and hi is None) or (lo == 0 and hi == 1)
+
+
+@torch.no_grad()
+def eval_pairs(src, seed=1, index0=0, lo=0, hi=1, fill="black", protocol="BB", out_size=None, gray=False,
+               use_norm=True):
+    """The 2N model inputs of N decoded faces as test.py builds them (_load_one_input, qeval_mxnet.py:173-189, and the
+    normalisation of :319-324), in one launch (msml_eval_pairs).  src: uint8 [N][H][W][3] RGB on the device, one size
+    per call -> f32 [2N][1 or 3][oh][ow]: row 2i is image i, row 2i + 1 its mirrored copy, each: mirror, CenterCrop
+    to out_size (None: the source size, an int, or (h, w) -- the reference's cfg.out_size is (w, h)) with torchvision's
+    zero padding and half-to-even origin, Grayscale when `gray`, RandomBlock(lo, hi, fill), ToTensor, and
+    sub_(0.5).div_(0.5) when `use_norm`.  protocol "NB" occludes only images whose global index index0 + i is even.
+    lo = hi = None, or (0, 1), gives no block.
+
+    Deliberate difference from the reference, as in ijb.eval_inputs: the block's size and place come from the
+    project's counter-based generator (data.draw(mode="block", size=ow)), the row of image g = index0 + i with mirror
+    bit f at counter 2 g + f -- the mirrored copy draws a block of its own, as test.py's second pass does -- and the
+    gauss fill's normals from the same generator keyed by (seed, 2 g + f, block row, block column, channel), NOT from
+    numpy's global RNG: a batch split does not change the result, and no run reproduces test.py's draws."""
+    if fill not in FILLS:
+        raise ValueError("eval_pairs: fill %r is not one of %s" % (fill, sorted(FILLS)))
+    if protocol not in PROTOCOLS:
+        raise ValueError("eval_pairs: protocol %r is not one of %s" % (protocol, sorted(PROTOCOLS)))
+    if protocol == "NB" and gray:
+        raise ValueError("eval_pairs: the NB protocol has no gray form (the reference puts a 3-channel tensor into "
+                         "the 1-channel batch there and raises)")
+    if (lo is None) != (hi is None):
+        raise ValueError("eval_pairs: lo and hi are both None or both integers")
+    if not _no_block(lo, hi) and not 0 <= int(lo) < int(hi) <= 101:
+        raise ValueError("eval_pairs: block range [%r, %r) outside 0..101" % (lo, hi))
+    if int(index0) < 0:
+        raise ValueError("eval_pairs: index0 = %r" % (index0,))
+    if not (isinstance(src, torch.Tensor) and src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3
+            and src.shape[0] >= 1):
+        raise ValueError("eval_pairs: src must be a uint8 [N][H][W][3] tensor")
+    if not src.is_contiguous():
+        raise ValueError("eval_pairs: src must be contiguous")
+    from . import data
+    n, h, w, _ = src.shape
+    oh, ow = data._out_hw(out_size, h, w)
+    if ow % 4 or not (4 <= h <= 256 and 4 <= w <= 256 and 4 <= oh <= 256 and 4 <= ow <= 256):
+        raise ValueError("eval_pairs: source %d x %d -> output %d x %d: sizes 4..256, output width a multiple of 4"
+                         % (h, w, oh, ow))
+    if not src.is_cuda:
+        raise ValueError("eval_pairs: src must be on the device")
+    desc = None
+    if not _no_block(lo, hi):
+        desc = data.draw(2 * n, seed, 2 * int(index0), mode="block", lo=int(lo), hi=int(hi), flip=False, size=ow,
+                         device=src.device)
+    out = torch.empty(2 * n, 1 if gray else 3, oh, ow, dtype=torch.float32, device=src.device)
+    call("msml_eval_pairs", src, n, h, w, desc, out, oh, ow, int(bool(gray)), int(bool(use_norm)), FILLS[fill],
+         PROTOCOLS[protocol], int(seed), int(index0))
+    return out
+
+
+@torch.no_grad()
+def extract_sum(model, src, batch=256, index0=0, **eval_pairs_kwargs):
+    """start_extract (qeval_mxnet.py:285-397) without its per-image loops: [N][E] f32 on the device, embedding of
+    eval_pairs' row 2i + embedding of row 2i + 1 (features_flip + features, :390).  `batch` images (2 * batch model
+    rows) per step; a model that returns a tuple gives its first entry (:333).  Nothing here waits for the device."""
+    n = src.shape[0]
+    batch = max(1, int(batch))
+    out = None
+    for i0 in range(0, n, batch):
+        i1 = min(n, i0 + batch)
+        f = model(eval_pairs(src[i0:i1], index0=int(index0) + i0, **eval_pairs_kwargs))
+        if isinstance(f, (tuple, list)):
+            f = f[0]
+        f = f.float().reshape(2 * (i1 - i0), -1)
+        if out is None:
+            out = torch.empty(n, f.shape[1], dtype=torch.float32, device=f.device)
+        torch.add(f[0::2], f[1::2], out=out[i0:i1])
+    return out
+
+
+def sweep_seed(seed, level, repeat):
+    """The generator seed of repeat `repeat` of level number `level` (its position in `levels`) of a sweep started with
+    `seed`: (seed + 0x9E3779B97F4A7C15 * (1024 * level + repeat + 1)) mod 2^63 -- a function of the three alone, so a
+    level's draws do not depend on which other levels, or how many repeats, the sweep runs."""
+    return (int(seed) + 0x9E3779B97F4A7C15 * (1024 * int(level) + int(repeat) + 1)) % (1 << 63)
+
+
+def occlusion_sweep(model, src, issame, levels=LEVELS, repeats=10, seed=1, batch=256, fill="black", protocol="BB",
+                    out_size=None, gray=False, use_norm=True, nrof_folds=10):
+    """The loop of test.py (qeval_mxnet.py:539-600) over block-occlusion levels: per level `repeats` extractions with
+    fresh blocks (one for the levels (0, 1) and (100, 101), :556), each through `evaluate` (mean of the 10-fold
+    accuracies, :566-569) and `roc_accuracy_tarfar` (:571-573), averaged over the repeats in f64 in the reference's
+    order of additions (:569, :573-576).  src: uint8 [2 * n_pairs][H][W][3] on the device (load_bin's images in order),
+    issame: n_pairs booleans.  Returns {"levels", "avg_acc" [L], "tarfar" [L][5]} -- the three rows test.py prints --
+    and the per-repeat values "acc" (L lists), "roc_acc" (L lists), "tarfar_runs" (L arrays [repeats][5]).
+
+    Repeat r of level number k draws with sweep_seed(seed, k, r).  As in eval_pairs the draws come from the project's
+    counter-based generator, not numpy's global RNG (np.random.seed(1), :499): no run reproduces test.py's blocks."""
+    levels = [(int(lo), int(hi)) for lo, hi in levels]
+    res = {"levels": levels, "avg_acc": [], "tarfar": np.zeros((len(levels), 5)), "acc": [], "roc_acc": [],
+           "tarfar_runs": []}
+    for k, (lo, hi) in enumerate(levels):
+        reps = 1 if (lo, hi) in ((0, 1), (100, 101)) else int(repeats)
+        avg_acc, accs, rocs, runs = 0.0, [], [], []
+        for r in range(reps):
+            emb = extract_sum(model, src, batch=batch, seed=sweep_seed(seed, k, r), lo=lo, hi=hi, fill=fill,
+                              protocol=protocol, out_size=out_size, gray=gray, use_norm=use_norm)
+            accuracy = evaluate(emb, issame, nrof_folds)[2]
+            acc2 = float(np.mean(accuracy))
+            roc_acc, tarfar = roc_accuracy_tarfar(emb, issame)
+            avg_acc += acc2
+            res["tarfar"][k] += tarfar
+            accs.append(acc2)
+            rocs.append(roc_acc)
+            runs.append(tarfar)
+        res["avg_acc"].append(avg_acc / reps)
+        res["tarfar"][k] /= reps
+        res["acc"].append(accs)
+        res["roc_acc"].append(rocs)
+        res["tarfar_runs"].append(np.stack(runs))
+    return res
