@@ -17,7 +17,7 @@
  *     activations / packed weights: MSML_F32 (exact-f32 MFMA path, parity mode) or MSML_BF16
  *     (bf16 operands, f32 accumulate).  Parameters, statistics and gradients of parameters
  *     are always f32 in the reference's own layouts (OIHW etc.).
- *   - reentrant: no global mutable state besides the thread-local error string.
+ *   - reentrant: no global mutable state besides the thread-local error string and the option table below.
  */
 #ifndef MSML_HIP_H
 #define MSML_HIP_H
@@ -57,6 +57,17 @@ long msml_stream_capture_id(void* stream);
  * side stream, backbones/msml.py has no counterpart: the reference runs one stream) through one re-recorded hipEvent per
  * calling thread.  Valid inside a graph capture (the waiter joins the capture). */
 int msml_stream_wait_stream(void* waiter, void* src);
+
+/* Switches (the MSML_* variables of the README's table; the list lives in msml_amd/csrc/options.h).  The environment is
+ * read ONCE, at the library's first use of any switch; a later setenv changes nothing -- later changes go through
+ * msml_set_option.  `name` is the environment name, `value` the PARSED value: 0 / 1 for the switches that only test
+ * whether the variable exists (MSML_NO_*, ...), the number otherwise.  A set is visible to every thread's next launch
+ * (relaxed atomics: setting while another thread launches is allowed, the launch sees the old or the new value).
+ * MSML_ERR_UNSUPPORTED for an unknown name (named in msml_last_error()), MSML_ERR_SHAPE for a null pointer.
+ * msml_option_name(index) enumerates the table: NULL past the end. */
+int msml_set_option(const char* name, long value);
+int msml_get_option(const char* name, long* value);
+const char* msml_option_name(int index);
 
 /* ---------------------------------------------------------------- layout (boundary) ------
  * The reference keeps NCHW f32 tensors end to end (backbones/msml.py:150); the HIP path

@@ -4,6 +4,7 @@ The header is the single source of truth: every prototype in it is parsed and bo
 symbol declared there but missing from the library fails at load time (loudly), and the
 product has no other compute path -- there is no CPU or torch fallback.
 """
+import contextlib
 import ctypes
 import os
 import re
@@ -73,6 +74,33 @@ def load():
 def exported_symbols():
     load()
     return sorted(_protos)
+
+
+def set_option(name, value):
+    """Set a library switch by its environment name to its PARSED value (msml_set_option: the library reads the environment
+    once, at its first use of a switch; later changes go through here).  Plain ctypes: not a launch."""
+    lib = load()
+    if lib.msml_set_option(name.encode(), int(value)) != 0:
+        raise KeyError(lib.msml_last_error().decode())
+
+
+def get_option(name):
+    lib = load()
+    v = ctypes.c_long()
+    if lib.msml_get_option(name.encode(), ctypes.byref(v)) != 0:
+        raise KeyError(lib.msml_last_error().decode())
+    return v.value
+
+
+@contextlib.contextmanager
+def option(name, value):
+    """`with option("MSML_NO_R32_CONV", 1): ...` -- the switch holds `value` inside the block and its previous value after."""
+    old = get_option(name)
+    set_option(name, value)
+    try:
+        yield
+    finally:
+        set_option(name, old)
 
 
 _DEV = None

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "options.h"
 
 #define RED_ROWS_MAX 1024      // partial rows produced by the standalone reduction kernels
 
@@ -74,7 +75,7 @@ __device__ __forceinline__ void slab_reduce(long M, int C, float* __restrict__ p
 
 static inline int red_rows(long M, int C) {
   int py = 256 / (C / 8) > 0 ? 256 / (C / 8) : 1;
-  static const long ppt = getenv("MSML_RED_PPT") ? atol(getenv("MSML_RED_PPT")) : 16;
+  const long ppt = msml_opt().red_ppt;
   long rows = (M + (long)py * ppt - 1) / ((long)py * ppt);     // >= ppt pixels per thread (4 / 8 measured
   // slower end to end: more partial rows for the finalize)
   if (rows < 1) rows = 1;
@@ -314,7 +315,7 @@ __global__ void __launch_bounds__(256) k_bn_act_fwd(const T* __restrict__ x, con
 }
 
 static inline int ew_grid(long n8) {
-  static const long cap = getenv("MSML_EW_GRID") ? atol(getenv("MSML_EW_GRID")) : 768;     // 3 per CU: with the accumulator fold in every
+  const long cap = msml_opt().ew_grid;     // 3 per CU: with the accumulator fold in every
   // workgroup's prologue 768 beats 1024 by 0.25 ms per step (640 / 896 equal, 512 / 1536 / 2048 slower)
   long b = (n8 + 255) / 256;
   return (int)(b < cap ? b : cap);

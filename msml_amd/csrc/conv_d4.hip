@@ -15,6 +15,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -153,7 +154,7 @@ __global__ void __launch_bounds__(512) k_deconv4_fwd(const ConvD4Args p) {
 
 bool msml_deconv4_applies(int c0p, int c1p, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
                           int pad_h, int pad_w, int transposed) {
-  static const bool off = getenv("MSML_NO_D4_CONV") != nullptr;
+  const bool off = msml_opt().no_d4_conv;
   if (off || !transposed || R != 4 || S != 4 || stride != 2 || pad_h != 1 || pad_w != 1) return false;
   if (c0p != 32 || c1p != 32 || coutp != 32 || H != W || P != 2 * H || Q != 2 * W) return false;
   if (!(H == 56 || H == 28 || H == 14)) return false;
@@ -293,7 +294,7 @@ __global__ void __launch_bounds__(512) k_deconv4_bwd(const ConvD4BwdArgs p) {
 
 extern "C" int msml_deconv4_bwd_data(const void* dy, const void* wp0, const void* wp1, void* dx0, void* dx1, int N, int H,
                                      void* stream) {
-  static const bool off = getenv("MSML_NO_D4_CONV") != nullptr;
+  const bool off = msml_opt().no_d4_conv;
   MSML_CHECK(dy && wp0 && wp1 && dx0 && dx1 && N > 0, MSML_ERR_SHAPE, "deconv4_bwd_data: bad arguments");
   if (off || !(H == 56 || H == 28 || H == 14) || (long)N * 4 * H * H * 64 >= 0x70000000L) {
     msml_set_error("deconv4_bwd_data: shape not covered (H=%d)", H);

@@ -21,6 +21,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 struct ConvFastArgs {
   const unsigned short* in[2];
@@ -539,7 +540,7 @@ static void launch_fast(ConvFastArgs& a, hipStream_t st) {
   // K of one stage (1x1 convs over <= 64 channels, the im2col'd stems): the ring never advances, so only
   // one buffer is needed -- 2 - 3 workgroups fit a CU instead of 1 - 2 and their load / epilogue phases
   // overlap (these launches are pure streaming: X in, Y out)
-  static const bool one_stage_ok = getenv("MSML_CONV_NO_ONE_STAGE") == nullptr;
+  const bool one_stage_ok = !msml_opt().conv_no_one_stage;
   a.lds_stages = NST;
   if (one_stage_ok && NST == 2 && a.ksplits <= 1 && (a.nsub[0] + a.nsub[1] + 1) / 2 <= 1) {
     a.lds_stages = 1;
@@ -697,7 +698,7 @@ bool msml_conv_fast_dispatch(const void* in0, int c0p, const void* in1, int c1p,
   a.split_stride = 0;
   // stride-2 transposed gather by output parity class (needs stage-aligned segment switches)
   a.parity = 0;
-  if (transposed && stride == 2 && !getenv("MSML_CONV_NO_PARITY") && stats == nullptr) {
+  if (transposed && stride == 2 && !msml_opt().conv_no_parity && stats == nullptr) {
     bool ok = true;
     if (a.nseg == 2)
       for (int c = 0; c < 4 && ok; c++) {
@@ -708,22 +709,22 @@ bool msml_conv_fast_dispatch(const void* in0, int c0p, const void* in1, int c1p,
     a.parity = ok ? 1 : 0;
   }
   // big tile only when it still fills the 256 CUs
-  static const int use_big = getenv("MSML_CONV_BIG_TILE") ? atoi(getenv("MSML_CONV_BIG_TILE")) : 0;
+  const int use_big = msml_opt().conv_big_tile;
   const bool big = use_big && bn == 128 && (long)cdiv(a.M, 256) * cdiv(coutp, 128) >= 256;
   // Small maps (7x7 / 4x4 stages, the OSB's deepest levels): the default 128- / 256-row tile leaves the chip half
   // empty (512 -> 512 @ 4x4: 128 workgroups, 512 -> 8 @ 4x4: 16), a 64-row tile doubles / quadruples the workgroup
   // count.  Statistics / fused BatchNorm sums only in accumulator mode (the partial-row formats are sized by the
   // default tile), no split-K, bf16 output.
-  static const bool small_ok = getenv("MSML_CONV_NO_SMALL_M") == nullptr;
+  const bool small_ok = !msml_opt().conv_no_small_m;
   const long def_wgs = (long)cdiv(a.parity ? (long)N * ((P + 1) / 2) * ((Q + 1) / 2) : a.M, bn == 128 ? 128 : 256) *
                        cdiv(coutp, bn) * (a.parity ? 4 : 1);
-  static const long small_wgs = getenv("MSML_CONV_SMALL_M_WGS") ? atol(getenv("MSML_CONV_SMALL_M_WGS")) : 200;
+  const long small_wgs = msml_opt().conv_small_m_wgs;
   const bool small_m = small_ok && !x3 && out_dtype == MSML_BF16 && def_wgs <= small_wgs && a.M >= 2048 &&
                        (!stats || a.stats_acc) && (!bnb || bnb->acc);
   // split-bf16 inference on the small maps (7x7 / 4x4: the deep OSB levels and their GCMs, the 256- / 128-channel 7x7
   // layers): 64-row tiles whatever the batch -- the kernel choice of this mode must not depend on N (conv_halo2.hip) -- a
   // 512 -> 32 @ 4x4 line conv is 16 workgroups of 256 rows x a K of 10 752 otherwise
-  static const bool x3_small = getenv("MSML_NO_X3_SMALL_M") == nullptr;
+  const bool x3_small = !msml_opt().no_x3_small_m;
   if (x3 && x3_small && !a.parity && P * Q <= 64 && !transposed) {
     if (bn == 128) launch_fast<unsigned short, 64, 128, 2, 2, 2, false, true>(a, st);
     else if (bn == 64) launch_fast<unsigned short, 64, 64, 2, 2, 2, false, true>(a, st);

@@ -24,6 +24,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 struct ConvHaloArgs {
   const unsigned short* in;
@@ -952,16 +953,15 @@ static int halo_num_cus() {
 // Shapes of the persistent 128-channel tile (k_conv_halo_p): 128 output channels, 64 k input channels (ONE 64-channel slab
 // included: 64 -> 128 @ 56x56, conv1 of the first block of layer2, backbones/frb/iresnet.py:166-170 -- the nine-stage K loop
 // whose prologue and epilogue ruled the one-tile kernel out runs back to back there), at least two rounds of tiles.
-// MSML_HALO_PERSIST=0 / MSML_HALO_NO_ONE_SLAB=1 (read per call: the tests compare): off / 128 input channels and more only.
+// MSML_HALO_PERSIST=0 / MSML_HALO_NO_ONE_SLAB=1: off / 128 input channels and more only.
 int msml_conv_halo_persist_shape(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
                                  int pad_h, int pad_w) {
-  const char* pe = getenv("MSML_HALO_PERSIST");
-  if (pe != nullptr && atoi(pe) == 0) return 0;
-  if (getenv("MSML_NO_HALO_CONV") != nullptr || getenv("MSML_HALO_WIDE_ONLY") != nullptr) return 0;   // (the halo conv's own
+  if (!msml_opt().halo_persist) return 0;
+  if (msml_opt().no_halo_conv || msml_opt().halo_wide_only) return 0;   // (the halo conv's own
   // off-switches cover this 128-channel instantiation too)
   if (R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || P != H || Q != W) return 0;
   if (coutp != 128 || kop < coutp || c0p % 64 != 0 || c0p < 64) return 0;
-  if (c0p == 64 && getenv("MSML_HALO_NO_ONE_SLAB") != nullptr) return 0;
+  if (c0p == 64 && msml_opt().halo_no_one_slab) return 0;
   const long tiles = (long)N * cdiv(H, 14) * cdiv(W, 14);
   if (tiles < 2L * halo_num_cus() || (long)N * H * W * 10 < tiles * 224 * 7) return 0;
   if ((long)N * H * W * c0p * 2 >= 0x70000000L || (long)N * H * W * 128 * 2 >= 0x70000000L || (long)kop * 9 * c0p * 2 >= 0x70000000L)
@@ -972,9 +972,9 @@ int msml_conv_halo_persist_shape(int c0p, int kop, int coutp, int N, int H, int 
 // Shape test shared by the dispatch and by msml_conv2d_kernel (the name query).
 bool msml_conv_halo_applies(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S,
                             int stride, int pad_h, int pad_w, bool want_stats) {
-  static const bool off = getenv("MSML_NO_HALO_CONV") != nullptr;
+  const bool off = msml_opt().no_halo_conv;
   if (off) return false;
-  static const bool wide_only = getenv("MSML_HALO_WIDE_ONLY") != nullptr;    // A/B switch
+  const bool wide_only = msml_opt().halo_wide_only;    // A/B switch
   if (wide_only && coutp % 256 != 0) return false;
   if (R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || P != H || Q != W) return false;
   if (c0p % 64 != 0 || c0p < 128 || coutp % 128 != 0 || kop < coutp) return false;   // (one 64-channel
@@ -994,10 +994,13 @@ bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, 
                              int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
                              const float* scale, const float* alpha, const void* residual, int res_first,
                              const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin, int x3) {
-  static const int m16_ = getenv("MSML_HALO_M16") ? atoi(getenv("MSML_HALO_M16")) : 2;
-  static const bool xfp_ = !(getenv("MSML_BNIN_ACC_PERSIST") && atoi(getenv("MSML_BNIN_ACC_PERSIST")) == 0);
-  const bool pshape = m16_ >= 2 && !x3 && !bias && !scale && !alpha && !residual &&
-                      (!xin || (xfp_ && xin->acc && !transposed && !bnb && stats && c0p <= 1024)) &&
+  // the 16x16x32 MFMA variant serves the plain forward / FUSE launches (round 4: +4...8 % on every shape, interleaved
+  // A/B on one box, LDS conflicts 0.7 %; DESIGN section 5).  MSML_HALO_M16=0 restores the 32x32x16 kernels, 1 limits
+  // the variant to the 256-channel tile.
+  const int m16 = msml_opt().halo_m16;
+  const bool xfp = msml_opt().bnin_acc_persist;
+  const bool pshape = m16 >= 2 && !x3 && !bias && !scale && !alpha && !residual &&
+                      (!xin || (xfp && xin->acc && !transposed && !bnb && stats && c0p <= 1024)) &&
                       (!stats || msml_tl_stats_acc) && (!bnb || bnb->acc) &&
                       msml_conv_halo_persist_shape(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w) != 0;
   if (!pshape && !msml_conv_halo_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, stats != nullptr))
@@ -1025,10 +1028,6 @@ bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, 
   if (xin) a.xin = *xin;
   if (bnb_rows) *bnb_rows = (int)tiles;
   const bool wide = coutp % 256 == 0;
-  // the 16x16x32 MFMA variant serves the plain forward / FUSE launches (round 4: +4...8 % on every shape, interleaved
-  // A/B on one box, LDS conflicts 0.7 %; DESIGN section 5).  MSML_HALO_M16=0 restores the 32x32x16 kernels, 1 limits
-  // the variant to the 256-channel tile.
-  static const int m16 = getenv("MSML_HALO_M16") ? atoi(getenv("MSML_HALO_M16")) : 2;
   // 128-channel tile, several rounds of tiles per launch (128 -> 128 @ 28x28, 64 -> 128 @ 56x56): the persistent kernel
   if (pshape) {
     const size_t lds = 2 * (size_t)256 * 128 + 8 * 8192;

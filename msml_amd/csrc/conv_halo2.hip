@@ -23,6 +23,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 struct ConvHalo2Args {
   const unsigned short* in;
@@ -540,7 +541,7 @@ static void launch_halo2(ConvHalo2Args& a, hipStream_t st) {
 // 2 mosaic of four 7 x 7 images, 3 mosaic of six 4 x 4 images) this family takes the shape with.
 int msml_conv_halo2_tiling(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
                            int pad_h, int pad_w, int transposed, int x3) {
-  static const bool off = getenv("MSML_NO_HALO2_CONV") != nullptr;
+  const bool off = msml_opt().no_halo2_conv;
   if (off) return 0;
   if (R != 3 || S != 3 || pad_h != 1 || pad_w != 1) return 0;
   if (c0p % 64 != 0 || c0p < 128 || coutp % 128 != 0 || kop < coutp) return 0;
@@ -551,8 +552,8 @@ int msml_conv_halo2_tiling(int c0p, int kop, int coutp, int N, int H, int W, int
   else return 0;
   const long in_bytes = (long)N * H * W * c0p * 2, w_bytes = (long)kop * 9 * c0p * 2;
   if (in_bytes >= 0x70000000L || w_bytes >= 0x70000000L || (long)N * P * Q * coutp * 2 >= 0x7fffffffL * 2) return 0;
-  static const bool no_mos = getenv("MSML_NO_HALO2_MOSAIC") != nullptr;
-  static const bool no_s2 = getenv("MSML_NO_HALO2_S2") != nullptr;
+  const bool no_mos = msml_opt().no_halo2_mosaic;
+  const bool no_s2 = msml_opt().no_halo2_s2;
   // mosaics run 128-channel tiles: below ~160 workgroups (256 -> 256 @ 7x7: 128, 128 -> 128 @ 7x7: 64, the forward of
   // 256 @ 14 -> 7: 128) the im2col kernel's 64-row tiles fill the chip better (tools/bench_small.py: 37.4 -> 34.9 us,
   // 17.6 -> 19.7 us, 36.1 -> 37.7 us); a backward-data launch has four slices per tile
@@ -578,7 +579,7 @@ bool msml_conv_halo2_dispatch(const void* in0, int c0p, const void* wp, int kop,
   if (!tiling) return false;
   // split-bf16 inference (c0p = 3 x the logical channels): forward launches, no statistics; MSML_NO_HALO2_X3=1 (read per
   // call) leaves them on the im2col kernel
-  if (x3 && (transposed || bnb || stats || getenv("MSML_NO_HALO2_X3") != nullptr)) return false;
+  if (x3 && (transposed || bnb || stats || msml_opt().no_halo2_x3)) return false;
   if (x3 && (long)N * P * Q * coutp * 6 >= 0x7fffffffL * 2) return false;
   if (msml_tl_bias9 && !(x3 && stride == 1)) return false;
   if (!x3 && (alpha || res_first)) return false;

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "options.h"
 
 struct ConvArgs {
   const void* in[2];
@@ -414,20 +415,20 @@ extern "C" int msml_conv2d(const void* in0, int c0p, const void* in1, int c1p, c
              "conv2d: packed weight has %d rows, need %d", kop, cdiv(coutp, bn) * bn);
   hipStream_t st = (hipStream_t)stream;
   // 7x1 / 1x7 line convs of the OSB's Global-Convolution modules (and their backward-data convs): conv_line.hip
-  if (in_dtype == MSML_BF16 && out_dtype == MSML_BF16 && !in1 && !stats && !getenv("MSML_NO_FAST_CONV") &&
+  if (in_dtype == MSML_BF16 && out_dtype == MSML_BF16 && !in1 && !stats && !msml_opt().no_fast_conv &&
       msml_conv_line_applies(c0p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w) &&
       msml_conv_line_dispatch(in0, c0p, wp, kop, bias, out, coutp, N, H, W, R, S, transposed, st)) {
     MSML_LAUNCH_OK("conv2d(line)");
     return MSML_OK;
   }
   // 4x4 / stride-2 transposed convs of the OSB decoder on cat(seg, gcm): conv_d4.hip
-  if (in_dtype == MSML_BF16 && out_dtype == MSML_BF16 && in1 && !stats && !getenv("MSML_NO_FAST_CONV") &&
+  if (in_dtype == MSML_BF16 && out_dtype == MSML_BF16 && in1 && !stats && !msml_opt().no_fast_conv &&
       msml_deconv4_applies(c0p, c1p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed) &&
       msml_deconv4_dispatch(in0, in1, wp, kop, bias, out, N, H, st)) {
     MSML_LAUNCH_OK("conv2d(deconv4)");
     return MSML_OK;
   }
-  if ((out_dtype == MSML_BF16 || out_dtype == MSML_F32) && !getenv("MSML_NO_FAST_CONV") &&
+  if ((out_dtype == MSML_BF16 || out_dtype == MSML_F32) && !msml_opt().no_fast_conv &&
       msml_conv_fast_dispatch(in0, c0p, in1, c1p, wp, kop, bias, out, coutp, stats, N, H, W, P, Q, R,
                               S, stride, pad_h, pad_w, transposed, in_dtype, out_dtype, bn, st, nullptr, nullptr,
                               nullptr, 0, nullptr, nullptr)) {
@@ -479,7 +480,7 @@ extern "C" int msml_conv2d_fused(const void* in0, int c0p, const void* in1, int 
   MSML_CHECK(kop >= cdiv(coutp, bn) * bn, MSML_ERR_SHAPE, "conv2d_fused: packed weight rows");
   // 7x1 / 1x7 line convs (the OSB's Global-Convolution modules: the backward-data conv of conv_l1 takes conv_r1's input
   // gradient as its residual, functional.py _ConvTee): conv_line.hip with scale / shift / residual in its epilogue
-  if (!in1 && !alpha && !(residual && res_first) && !getenv("MSML_NO_FAST_CONV") &&
+  if (!in1 && !alpha && !(residual && res_first) && !msml_opt().no_fast_conv &&
       msml_conv_line_applies(c0p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w) &&
       msml_conv_line_dispatch(in0, c0p, wp, kop, shift, out, coutp, N, H, W, R, S, transposed, (hipStream_t)stream, scale,
                               residual)) {
@@ -610,7 +611,7 @@ bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, 
 
 extern "C" int msml_conv2d_bnin_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S,
                                         int stride, int pad_h, int pad_w, int want_stats) {
-  if (getenv("MSML_NO_FAST_CONV") || c0p > 1024 || (long)N * P * Q >= (1L << 24)) return 0;
+  if (msml_opt().no_fast_conv || c0p > 1024 || (long)N * P * Q >= (1L << 24)) return 0;
   const int bn = msml_conv_tile_n(coutp), kop = cdiv(coutp, bn) * bn;
   return msml_conv_halo_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, want_stats != 0) ? 1 : 0;
 }
@@ -638,13 +639,11 @@ extern "C" int msml_conv2d_bnin(const void* in0, int c0p, const float* in_scale,
 // 1 when msml_conv2d_bnin_acc serves the shape on the halo-tile conv, 3 on the persistent 128-channel halo tile, 0 otherwise.
 extern "C" int msml_conv2d_bnin_acc_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S,
                                             int stride, int pad_h, int pad_w) {
-  if (getenv("MSML_NO_FAST_CONV") || c0p > 1024 || c0p % 8 || 256 % (c0p / 8) || (long)N * P * Q >= (1L << 24)) return 0;
+  if (msml_opt().no_fast_conv || c0p > 1024 || c0p % 8 || 256 % (c0p / 8) || (long)N * P * Q >= (1L << 24)) return 0;
   const int bn = msml_conv_tile_n(coutp), kop = cdiv(coutp, bn) * bn;
   // 3: the persistent 128-channel tile takes the launch (round 6: its prologue transform pays from 64 input channels on --
   // the one-slab shape 64 -> 128 @ 56x56, conv1 of a stage's first block, has no one-round kernel to fall back to)
-  static const bool xfp = !(getenv("MSML_BNIN_ACC_PERSIST") && atoi(getenv("MSML_BNIN_ACC_PERSIST")) == 0);
-  const char* m16e = getenv("MSML_HALO_M16");
-  if (xfp && (!m16e || atoi(m16e) >= 2) &&
+  if (msml_opt().bnin_acc_persist && msml_opt().halo_m16 >= 2 &&
       msml_conv_halo_persist_shape(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w))
     return 3;
   return msml_conv_halo_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, true) ? 1 : 0;
@@ -696,7 +695,7 @@ extern "C" const char* msml_conv2d_kernel(int c0p, int c1p, int coutp, int N, in
     return bm == 128 ? "k_conv_igemm<mfm, bf16, 128 x 128>" : (bm == 64 ? "k_conv_igemm<mfm, bf16, 256 x 64>" : "k_conv_igemm<mfm, bf16, 256 x 32>");
   }
   const int bn = msml_conv_tile_n(coutp);
-  const bool fast = in_dtype == MSML_BF16 && !getenv("MSML_NO_FAST_CONV") && c0p % 32 == 0 && c1p % 32 == 0 &&
+  const bool fast = in_dtype == MSML_BF16 && !msml_opt().no_fast_conv && c0p % 32 == 0 && c1p % 32 == 0 &&
                     (c1p == 0 || ((R * S * (c0p / 32)) & 1) == 0) && (long)N * P * Q < (1L << 24);
   if (fast && out_dtype == MSML_BF16 && !want_stats &&
       msml_deconv4_applies(c0p, c1p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed))

@@ -15,6 +15,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -181,7 +182,7 @@ __global__ void __launch_bounds__(512) k_conv_line(const ConvLineArgs p) {
 
 bool msml_conv_line_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
                             int pad_w) {
-  static const bool off = getenv("MSML_NO_LINE_CONV") != nullptr;
+  const bool off = msml_opt().no_line_conv;
   if (off) return false;
   if (!((R == 7 && S == 1 && pad_h == 3 && pad_w == 0) || (R == 1 && S == 7 && pad_h == 0 && pad_w == 3))) return false;
   if (stride != 1 || H != W || P != H || Q != W) return false;

@@ -28,6 +28,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 struct ConvPwArgs {
   const unsigned short* in;        // [M][CIN]
@@ -315,14 +316,14 @@ static void pw_launch(const ConvPwArgs& a, hipStream_t st) {
   }
   // persistent workers: up to 4 workgroups of 4 waves per CU (the register / LDS footprint of the instantiation may
   // allow fewer -- the rest queue behind them); never more workers than units
-  static const int per_cu = getenv("MSML_PW_WGS_PER_CU") ? atoi(getenv("MSML_PW_WGS_PER_CU")) : 4;
+  const int per_cu = msml_opt().pw_wgs_per_cu;
   long grid = (long)cus * per_cu;
   const long ngrp = (a.nblk + NB - 1) / NB;
   const long need = (ngrp * NCG + 3) / 4;
   if (grid > need) grid = need;
   // (knob: at least `upw` units per worker for STATS / BNB launches, whose sums leave every workgroup as f64 atomics at
   // the end of the kernel; measured neutral once the in-wave reduction ran on DPP -- default 1 = as many workers as fit)
-  static const int upw = getenv("MSML_PW_UPW") ? atoi(getenv("MSML_PW_UPW")) : 1;
+  const int upw = msml_opt().pw_upw;
   if (MODE == PW_STATS || MODE == PW_BNB) {
     long g2 = need / upw;
     if (g2 < cus) g2 = cus;
@@ -352,9 +353,8 @@ bool msml_conv_pw_dispatch(const void* in0, int c0p, const void* wp, int kop, in
   // 38 -> 29, the 28x28 layers 28 -> 25-29; backward-data 64 -> 32 @ 56x56 41 -> 29, 32 -> 64 33 -> 27 (5.6 TB/s),
   // 128 -> 64 @ 28x28 24 -> 17.  (The first version loaded and stored in MFMA operand layout -- adjacent lanes = different
   // pixels, every 16-B access a memory request of its own -- and only won on the 112x112 stem; see DESIGN section 8 g.)
-  // MSML_PW_CONV=0: the general kernel everywhere (read per call: the tests compare both kernels in one process).
-  const char* pol = getenv("MSML_PW_CONV");
-  if (pol && pol[0] == '0') return false;
+  // MSML_PW_CONV=0: the general kernel everywhere.
+  if (!msml_opt().pw_conv) return false;
   if (R != 1 || S != 1 || stride != 1 || pad_h != 0 || pad_w != 0 || P != H || Q != W) return false;
   if (alpha || (residual && res_first)) return false;
   if (stats && !stats_acc) return false;                // partial-row statistics stay on the general kernel

@@ -18,6 +18,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 struct ConvR32Args {
   const unsigned short* in;        // [N][H][W][32]
@@ -267,7 +268,7 @@ static void r32_launch(ConvR32Args& a, hipStream_t st) {
     cus = n;
   }
   // strips: at least ~8 workers per CU, at most 14 rows each (two halo rows are re-read per strip)
-  static const int rows_env = getenv("MSML_R32_ROWS") ? atoi(getenv("MSML_R32_ROWS")) : 0;
+  const int rows_env = msml_opt().r32_rows;
   int rs = 14;
   while (rs > 4 && (long)a.N * ((a.H + rs - 1) / rs) < 8L * cus) rs = (rs + 1) / 2;
   if (rows_env > 0) rs = rows_env;
@@ -292,7 +293,7 @@ bool msml_conv_r32_dispatch(const void* in0, int c0p, const void* wp, int kop, i
                             int coutp, float* stats, int stats_acc, int N, int H, int W, int P, int Q, int R, int S,
                             int stride, int pad_h, int pad_w, int transposed, hipStream_t st, const float* scale,
                             const float* alpha, const void* residual, const BnBwdFuse* bnb) {
-  if (getenv("MSML_NO_R32_CONV")) return false;           // (read per call: the test compares both kernels in one process)
+  if (msml_opt().no_r32_conv) return false;
   if (c0p != 32 || coutp != 32 || R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || P != H || Q != W) return false;
   if (bias || scale || alpha || residual) return false;
   if (stats && !stats_acc) return false;

@@ -21,6 +21,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 struct ConvS2rArgs {
   const unsigned short* in;
@@ -573,13 +574,13 @@ static int s2r_num_cus() {
 // 1 when k_conv_s2r takes the shape: 64 -> 64 channels, 3x3, stride 2, pad 1, even maps, enough real GEMM rows.
 int msml_conv_s2r_applies(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
                           int pad_w, int transposed) {
-  static const bool off = getenv("MSML_NO_S2R_CONV") != nullptr;
+  const bool off = msml_opt().no_s2r_conv;
   if (off || R != 3 || S != 3 || pad_h != 1 || pad_w != 1 || c0p != 64 || coutp != 64 || kop < 64) return 0;
   // stride 1 (the layers of conv_ws.hip): forward + statistics and plain backward-data measured faster here (round 5, one box:
   // 64 -> 64 @ 112x112 389 -> 350 us, @ 56x56 87 -> 81 us; backward-data 350 -> 312 / 83 -> 71 us), the fused-BatchNorm
   // backward-data slower (92.6 -> 100.7 us: 16-channel waves touch 32 B per pixel) -- the dispatcher keeps that one on
   // k_conv_ws.  MSML_NO_S2R_STRIDE1=1: stride-2 layers only.
-  static const bool s1 = getenv("MSML_NO_S2R_STRIDE1") == nullptr;
+  const bool s1 = !msml_opt().no_s2r_stride1;
   if (stride != 2 && !(stride == 1 && s1)) return 0;
   int gh, gw;
   if (stride == 1) { if (P != H || Q != W) return 0; gh = H; gw = W; }
@@ -637,11 +638,11 @@ bool msml_conv_s2r_dispatch(const void* in0, int c0p, const void* wp, int kop, c
 }
 
 // Split-bf16 inference (msml_conv2d_x3): 64 -> 64 channel 3x3 / stride-1 / pad-1 forward layers; c0p = 3 x 64 as the fast
-// dispatcher sees it.  MSML_NO_S2R_X3=1 (read per call: the tests compare with the general kernel) leaves them on k_conv_fast.
+// dispatcher sees it.  MSML_NO_S2R_X3=1 leaves them on k_conv_fast.
 bool msml_conv_s2r_x3_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out, int coutp, int N,
                                int H, int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w, int transposed,
                                hipStream_t st, const float* scale, const float* alpha, const void* residual, int res_first) {
-  if (getenv("MSML_NO_S2R_CONV") != nullptr || getenv("MSML_NO_S2R_X3") != nullptr) return false;
+  if (msml_opt().no_s2r_conv || msml_opt().no_s2r_x3) return false;
   if (R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || transposed || c0p != 192 || coutp != 64 || kop < 64) return false;
   if (P != H || Q != W) return false;
   const long tiles = (long)N * cdiv(H, 14) * cdiv(W, 14);

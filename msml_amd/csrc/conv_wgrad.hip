@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "options.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -361,10 +362,10 @@ bool msml_wgrad_line_launch(const void* u, const void* v, int vp, float* ws, int
 
 // taps handled by one workgroup of the bf16 fast kernel (narrow V operands share the U tile)
 static int wgrad_ntw(int vp, int taps) {
-  static const bool off = getenv("MSML_WGRAD_NO_MULTITAP") != nullptr;
+  const bool off = msml_opt().wgrad_no_multitap;
   // 128-channel layers: 3 taps x one 64-channel chunk per workgroup (125 -> 93 us at 128->128@28x28);
   // neutral from 256 channels on (the wider tile's slab traffic eats the fill saving)
-  static const int wide = getenv("MSML_WGRAD_MULTITAP_WIDE") ? atoi(getenv("MSML_WGRAD_MULTITAP_WIDE")) : 128;
+  const int wide = msml_opt().wgrad_multitap_wide;
   if (off || taps < 3) return 1;
   if (vp <= 64) return 3;
   return (wide && vp % 64 == 0 && vp <= wide) ? 3 : 1;     // 3 taps x one 64-channel chunk per workgroup
@@ -378,8 +379,8 @@ static int pick_tile(int c) { return c > 64 ? 128 : 64; }
 // |dW| of a few hundred KB) half as many workgroups win, with many tiles (512 channels) 768;
 // measured per shape with tools/bench_conv.py (MSML_WGRAD_WGS overrides).
 static int pick_splits(long mpix, int out_tiles) {
-  static const long forced = getenv("MSML_WGRAD_WGS") ? atol(getenv("MSML_WGRAD_WGS")) : 0;
-  static const long minchunk = getenv("MSML_WGRAD_MINCHUNK") ? atol(getenv("MSML_WGRAD_MINCHUNK")) : 256;
+  const long forced = msml_opt().wgrad_wgs;
+  const long minchunk = msml_opt().wgrad_minchunk;
   long target = 1024;
   if (out_tiles <= 9 && mpix <= (1L << 20)) target = 512;
   else if (out_tiles > 48) target = 768;
@@ -478,7 +479,7 @@ extern "C" int msml_conv_wgrad(const void* u, int up, const void* v, int vp, flo
       return MSML_OK;
     }
   }
-  if (dtype == MSML_BF16 && !getenv("MSML_NO_FAST_WGRAD") &&
+  if (dtype == MSML_BF16 && !msml_opt().no_fast_wgrad &&
       msml_wgrad_fast_launch(u, up, v, vp, a.ws, N, H, W, P, Q, R, S, stride, pad_h, pad_w, ba, bb, ntw,
                              splits, a.chunk, st, dw, A, Breal, Btot, boff, accumulate)) {
     MSML_LAUNCH_OK("conv_wgrad(fast)");
@@ -530,7 +531,7 @@ extern "C" int msml_conv_wgrad_group_max(int up, int vp, int A, int Breal, int N
   }
   // im2col kernel (small maps, the shapes the strip / halo kernel leaves): grouping pays while a layer still has
   // split-K slabs to shed, i.e. up to the split count of the one-layer launch
-  static const bool off = getenv("MSML_NO_FAST_WGRAD_GROUP") != nullptr;
+  const bool off = msml_opt().no_fast_wgrad_group;
   if (off || R != 3 || S != 3 || stride != 1 || up % 8 || vp % 8) return 1;
   if (msml_wgrad_n32_splits(up, vp, N, H, W, P, Q, R, S, stride, pad_h, pad_w) > 0) return 1;
   const int ba = pick_tile(up), bb = pick_tile(vp), taps = R * S, ntw = wgrad_ntw(vp, taps);

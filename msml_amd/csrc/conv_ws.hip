@@ -17,6 +17,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 struct ConvWsArgs {
   const unsigned short* in;
@@ -469,7 +470,7 @@ static int ws_num_cus() {
 
 bool msml_conv_ws_applies(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S,
                           int stride, int pad_h, int pad_w, bool want_stats) {
-  static const bool off = getenv("MSML_NO_WS_CONV") != nullptr;
+  const bool off = msml_opt().no_ws_conv;
   if (off) return false;
   if (R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || P != H || Q != W) return false;
   if (c0p != 64 || coutp != 64 || kop < 64) return false;
@@ -520,7 +521,7 @@ bool msml_conv_ws_dispatch(const void* in0, int c0p, const void* wp, int kop, co
   // Round 5: with the direct stores (no LDS transpose, one barrier per tile) the 16x16x32 variant is the faster one -- 64 -> 64 @
   // 112x112 forward 431 -> 385 us, @ 56x56 100 -> 93 us, the step 29.38 -> 29.17 / 29.26 ms (one box, twice): default;
   // MSML_WS_M16=0 restores the 32x32x16 kernels.
-  static const bool m16 = !(getenv("MSML_WS_M16") && atoi(getenv("MSML_WS_M16")) == 0);
+  const bool m16 = msml_opt().ws_m16;
   if (bnb) { if (m16) launch_ws<true, true>(a, st); else launch_ws<true>(a, st); }
   else { if (m16) launch_ws<false, true>(a, st); else launch_ws<false>(a, st); }
   return true;

@@ -18,6 +18,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -151,7 +152,7 @@ __global__ void __launch_bounds__(512) k_fc_wgrad(const FcWgradArgs p) {
 int msml_fc_wgrad_launch(const void* u, int up, const void* v, int vp, float* dw, int A, int Breal, int Btot, int boff,
                          int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w,
                          int accumulate, hipStream_t st) {
-  static const bool off = getenv("MSML_NO_FC_WGRAD") != nullptr;
+  const bool off = msml_opt().no_fc_wgrad;
   const int T = R * S;
   if (off || P != 1 || Q != 1 || R != H || S != W || pad_h != 0 || pad_w != 0 || stride != 1) return 0;
   if (T < 2 || T > FCW_MAX_TAPS || up % 32 || vp % 32 || A != up || Breal != vp || N < 16) return 0;

@@ -1,5 +1,6 @@
 // Boundary layout kernels: NCHW f32 <-> NHWC (channel-padded) storage, weight packing.
 #include "common.h"
+#include "options.h"
 
 // One thread per (n, h, w, 8-channel chunk); reads are strided over C (small C at the
 // boundary: 3 input channels / 2 output channels), writes are 16 B (bf16) / 32 B (f32).
@@ -384,7 +385,7 @@ extern "C" int msml_stem_im2col(const float* x, void* out, int N, int C, int H, 
              R * S * C, KP);
   const long total = (long)N * P * Q * (KP / 8);
   const int grid = (int)((total + 255) / 256 < 32768 ? (total + 255) / 256 : 32768);
-  const bool no_lds = getenv("MSML_NO_STEM_LDS") != nullptr;      // A/B switch, read per call (the test compares both kernels)
+  const bool no_lds = msml_opt().no_stem_lds;      // A/B switch
   if (!no_lds && C == 3 && R == 3 && S == 3 && pad == 1 && KP == 32 && W <= 128 && (stride == 1 || stride == 2) &&
       P == (H + 2 - 3) / stride + 1 && Q == (W + 2 - 3) / stride + 1) {
     const int lgrid = N * ((P + 3) / 4);

@@ -25,6 +25,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -364,17 +365,17 @@ static int wh_cus() {
 // 128-row dW tiles halve the operand traffic per FLOP; 64-row tiles halve the split-K slab bytes
 // (measured at 256 -> 256 @ 14x14: 97 us with 128-row tiles, 104 us with 64-row tiles)
 static bool wh_wide(int up) {
-  static const int lim = getenv("MSML_WGRAD_HALO_WIDE_MIN") ? atoi(getenv("MSML_WGRAD_HALO_WIDE_MIN")) : 128;
+  const int lim = msml_opt().wgrad_halo_wide_min;
   return up % 128 == 0 && up >= lim;
 }
 
 int msml_wgrad_halo_splits(int up, int vp, int A, int Breal, int N, int H, int W, int P, int Q, int R, int S,
                            int stride, int pad_h, int pad_w) {
-  static const bool off = getenv("MSML_NO_HALO_WGRAD") != nullptr;
+  const bool off = msml_opt().no_halo_wgrad;
   if (off) return 0;
   if (R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || P != H || Q != W) return 0;
   if (up % 64 != 0 || vp % 64 != 0 || A != up || Breal != vp) return 0;
-  const bool pair7 = H == 7 && W == 7 && getenv("MSML_WGRAD_HALO_NO_PAIR7") == nullptr;   // two 7 x 7 images per strip
+  const bool pair7 = H == 7 && W == 7 && !msml_opt().wgrad_halo_no_pair7;   // two 7 x 7 images per strip
   const long strips = pair7 ? (N + 1) / 2 : (long)N * cdiv(H, 7) * cdiv(W, 14);
   if ((long)N * H * W * 10 < strips * 112 * 7) return 0;           // < 70 % real k-values
   if ((long)N * H * W * up * 2 >= 0x70000000L || (long)N * H * W * vp * 2 >= 0x70000000L) return 0;
@@ -412,7 +413,7 @@ int msml_wgrad_halo_group_splits(int up, int vp, int A, int Breal, int N, int H,
 // ws[(layer * splits + split)][up][9][vp]
 bool msml_wgrad_halo_launch_group(const void* const* u, int up, const void* const* v, int vp, float* ws, int N, int H,
                                   int W, int group, int splits, hipStream_t st, const BnIn* xin) {
-  static const bool no_remap = getenv("MSML_WGRAD_HALO_NO_REMAP") != nullptr;
+  const bool no_remap = msml_opt().wgrad_halo_no_remap;
   WgradHaloArgs a;
   for (int i = 0; i < WH_MAXGROUP; i++) {
     a.u[i] = (const unsigned short*)u[i < group ? i : 0];

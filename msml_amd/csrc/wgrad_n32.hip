@@ -17,6 +17,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "options.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -181,7 +182,7 @@ static int wn_cus() {
 // splits for a shape (0 = shape not covered by this kernel)
 int msml_wgrad_n32_splits(int up, int vp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
                           int pad_w) {
-  static const bool off = getenv("MSML_NO_N32_WGRAD") != nullptr;
+  const bool off = msml_opt().no_n32_wgrad;
   if (off || up != 32 || vp != 32 || R != S || pad_h != 1 || pad_w != 1) return 0;
   const bool d4 = R == 4 && stride == 2 && H == 2 * P && W == 2 * Q;
   const bool c3 = R == 3 && stride == 1 && H == P && W == Q;
@@ -336,7 +337,7 @@ __global__ void __launch_bounds__(512) k_wgrad_line(const WgradLineArgs p) {
 
 int msml_wgrad_line_splits(int up, int vp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
                            int pad_w) {
-  static const bool off = getenv("MSML_NO_N32_WGRAD") != nullptr;
+  const bool off = msml_opt().no_n32_wgrad;
   if (off || up != 32 || (vp != 32 && vp != 64) || stride != 1) return 0;
   if (!((R == 7 && S == 1 && pad_h == 3 && pad_w == 0) || (R == 1 && S == 7 && pad_h == 0 && pad_w == 3))) return 0;
   if (H != W || P != H || Q != W || !(H == 56 || H == 28)) return 0;

@@ -852,11 +852,10 @@ def test_pointwise_conv_kernel_matches_the_general_kernel(shape, monkeypatch):
     monkeypatch.setattr(ops, "ACC_STATS", True)
 
     def both(fn):
-        monkeypatch.setenv("MSML_PW_CONV", "all")      # every case the kernel supports (the default policy takes a few)
-        a = fn()
-        monkeypatch.setenv("MSML_PW_CONV", "0")
-        b = fn()
-        monkeypatch.delenv("MSML_PW_CONV", raising=False)
+        with _lib.option("MSML_PW_CONV", 1):      # every case the kernel supports
+            a = fn()
+        with _lib.option("MSML_PW_CONV", 0):
+            b = fn()
         return a, b
 
     # forward + statistics accumulator
@@ -928,11 +927,10 @@ def test_conv3x3_32_channel_row_kernel_matches_the_general_kernel(shape, monkeyp
     monkeypatch.setattr(ops, "ACC_STATS", True)
 
     def both(fn):
-        monkeypatch.delenv("MSML_NO_R32_CONV", raising=False)
-        a = fn()
-        monkeypatch.setenv("MSML_NO_R32_CONV", "1")
-        b = fn()
-        monkeypatch.delenv("MSML_NO_R32_CONV", raising=False)
+        with _lib.option("MSML_NO_R32_CONV", 0):
+            a = fn()
+        with _lib.option("MSML_NO_R32_CONV", 1):
+            b = fn()
         return a, b
 
     (o1, s1), (o2, s2) = both(lambda: ops.conv2d(x, None, wp, None, c, 3, 3, 1, 1, 1, False, want_stats=True))
@@ -1094,7 +1092,7 @@ def test_conv_s2r_64_channel_stride2(shape):
 # registers (N, H, W): one tile per workgroup, the persistent loop (more tiles than workgroups), ragged tiles, a non-square map
 @pytest.mark.parametrize("epi", ["plain", "bn_prelu", "bn_res_prelu", "bn_prelu_res", "bias"])
 @pytest.mark.parametrize("shape", [(3, 56, 56), (2, 112, 112), (5, 28, 28), (4, 27, 40), (40, 56, 56)])
-def test_conv_x3_64_channel_register_kernel(shape, epi, monkeypatch):
+def test_conv_x3_64_channel_register_kernel(shape, epi):
     """Split-bf16 conv + affine / PReLU / residual epilogue (functional.conv_x3 -> msml_conv2d_x3) on the register-weights
     kernel: against f64 torch on the values the split tensors hold (f32-class: 3e-5 of the output scale, where one bf16
     product is 4e-3), and against the general kernel (k_conv_fast X3), which differs only in the order of its f32 sums."""
@@ -1122,10 +1120,9 @@ def test_conv_x3_64_channel_register_kernel(shape, epi, monkeypatch):
 
     got = run()
     torch.cuda.synchronize()
-    monkeypatch.setenv("MSML_NO_S2R_X3", "1")
-    gen = run()
-    torch.cuda.synchronize()
-    monkeypatch.delenv("MSML_NO_S2R_X3")
+    with _lib.option("MSML_NO_S2R_X3", 1):
+        gen = run()
+        torch.cuda.synchronize()
     xv = Fh.x3_to_f32(xs).double().permute(0, 3, 1, 2)
     wh = conv.weight.detach().to(torch.bfloat16).float()
     wv = (wh + (conv.weight.detach() - wh).to(torch.bfloat16).float()).double()      # what [wh | wh | wl] holds
@@ -1239,7 +1236,7 @@ def test_conv_x3_batchnorm_fold_under_cancellation(ratio):
 @pytest.mark.parametrize("epi", ["bn_prelu", "bn_res", "bn_res_prelu"])
 @pytest.mark.parametrize("shape", [(6, 128, 56, 2), (5, 256, 28, 2), (4, 128, 26, 2), (161, 512, 14, 2), (164, 512, 7, 1),
                                    (243, 512, 4, 1)])
-def test_conv_x3_stride2_and_mosaics_on_the_halo_tile(shape, epi, monkeypatch):
+def test_conv_x3_stride2_and_mosaics_on_the_halo_tile(shape, epi):
     import torch.nn as nn
     from msml_amd import functional as Fh
     n, c, h, stride = shape
@@ -1262,10 +1259,9 @@ def test_conv_x3_stride2_and_mosaics_on_the_halo_tile(shape, epi, monkeypatch):
 
     got = run()
     torch.cuda.synchronize()
-    monkeypatch.setenv("MSML_NO_HALO2_X3", "1")
-    gen = run()
-    torch.cuda.synchronize()
-    monkeypatch.delenv("MSML_NO_HALO2_X3")
+    with _lib.option("MSML_NO_HALO2_X3", 1):
+        gen = run()
+        torch.cuda.synchronize()
     xv = Fh.x3_to_f32(xs).double().permute(0, 3, 1, 2)
     wh = conv.weight.detach().to(torch.bfloat16).float()
     wv = (wh + (conv.weight.detach() - wh).to(torch.bfloat16).float()).double()
@@ -1339,7 +1335,7 @@ def test_conv_x3_small_maps(shape):
 # k_conv_halo_p: the persistent 128-channel tile (several rounds of 14 x 14 tiles per launch): (N, H, W) with >= 512 tiles --
 # four tiles per image, ragged tiles (27 x 40: 6 per image), more tiles than twice the workgroups
 @pytest.mark.parametrize("shape", [(130, 28, 28), (90, 27, 40), (260, 28, 28), (40, 56, 56, 64), (140, 28, 28, 256)])
-def test_conv_halo_persistent_128_channel_tile(shape, monkeypatch):
+def test_conv_halo_persistent_128_channel_tile(shape):
     """Forward + accumulator-mode statistics and backward-data + fused BatchNorm sums on the persistent kernel: outputs
     bit-identical to the one-tile-per-workgroup kernel (same per-tile arithmetic), sums equal to f32 rounding (the tiles are
     added in another order), both against f64 torch (backbones/frb/iresnet.py:56-67, layer2's 128-channel blocks)."""
@@ -1370,9 +1366,8 @@ def test_conv_halo_persistent_128_channel_tile(shape, monkeypatch):
         return y, acc.clone(), dx, bacc.clone()
 
     y1, a1, dx1, b1 = run()
-    monkeypatch.setenv("MSML_HALO_PERSIST", "0")
-    y0, a0, dx0, b0 = run()
-    monkeypatch.delenv("MSML_HALO_PERSIST")
+    with _lib.option("MSML_HALO_PERSIST", 0):
+        y0, a0, dx0, b0 = run()
     assert torch.equal(y1, y0) and torch.equal(dx1, dx0)
     assert torch.allclose(a1.sum(0), a0.sum(0), rtol=1e-5, atol=1e-5 * a0.sum(0).abs().max().item())
     assert torch.allclose(b1.sum(0), b0.sum(0), rtol=1e-5, atol=1e-5 * b0.sum(0).abs().max().item())
@@ -1388,17 +1383,70 @@ def test_conv_halo_persistent_128_channel_tile(shape, monkeypatch):
 # the step (112 x 112, stride 1 and 2), ragged row groups (P % 4 != 0), odd widths, one image
 @pytest.mark.parametrize("dtype", ["bf16", "f32"])
 @pytest.mark.parametrize("shape", [(3, 112, 112, 1), (2, 112, 112, 2), (5, 30, 42, 1), (4, 30, 42, 2), (1, 7, 9, 1), (2, 13, 128, 2)])
-def test_stem_im2col_through_lds_is_the_gather(shape, dtype, monkeypatch):
+def test_stem_im2col_through_lds_is_the_gather(shape, dtype):
     n, h, w_, stride = shape
     g = torch.Generator().manual_seed(sum(shape))
     x = torch.randn(n, 3, h, w_, generator=g).cuda()
     dt = _lib.BF16 if dtype == "bf16" else _lib.F32
     got = ops.stem_im2col(x, 3, 3, stride, 1, dtype=dt)
-    monkeypatch.setenv("MSML_NO_STEM_LDS", "1")
-    ref = ops.stem_im2col(x, 3, 3, stride, 1, dtype=dt)
-    torch.cuda.synchronize()
+    with _lib.option("MSML_NO_STEM_LDS", 1):
+        ref = ops.stem_im2col(x, 3, 3, stride, 1, dtype=dt)
+        torch.cuda.synchronize()
     assert got.shape == ref.shape and torch.equal(got, ref)
     # and against unfold: k = (r * 3 + s) * 3 + c, zeros above k = 27
     cols = F.unfold(x, 3, padding=1, stride=stride).view(n, 3, 9, -1).permute(0, 3, 2, 1).reshape(n, got.shape[1], got.shape[2], 27)
     want = cols.bfloat16().float() if dtype == "bf16" else cols
     assert torch.equal(got[..., :27].float(), want) and float(got[..., 27:].float().abs().max()) == 0.0
+
+
+# The conv family switches, each compared on and off in ONE process (msml_set_option): the smallest shape of the family's own
+# test above.  (switch, name of the family's kernel, Cin1, Cin2, Cout, N, H, W, R, S, stride, pad_h, pad_w, transposed,
+# bias, want_stats -- the statistics as in the family's own test)
+FAMILY_SWITCHES = [
+    ("MSML_NO_HALO_CONV", "k_conv_halo<", 128, 0, 128, 40, 28, 28, 3, 3, 1, 1, 1, False, False, False),     # HALO
+    ("MSML_NO_WS_CONV", "k_conv_ws<", 64, 0, 64, 5, 28, 40, 3, 3, 1, 1, 1, False, False, False),            # HALO (ws rows)
+    ("MSML_NO_HALO2_CONV", "k_conv_halo2<", 128, 0, 128, 5, 28, 28, 3, 3, 2, 1, 1, False, False, True),     # HALO2
+    ("MSML_NO_LINE_CONV", "k_conv_line<", 18, 0, 18, 5, 28, 28, 1, 7, 1, 0, 3, False, True, False),         # test_conv_line
+    ("MSML_NO_D4_CONV", "k_deconv4_fwd<", 18, 18, 18, 2, 14, 14, 4, 4, 2, 1, 1, True, False, False),        # DECONVS
+    ("MSML_NO_S2R_CONV", "k_conv_s2r<", 64, 0, 64, 5, 28, 28, 3, 3, 2, 1, 1, False, False, True),           # test_conv_s2r_*
+]
+
+
+@pytest.mark.parametrize("case", FAMILY_SWITCHES, ids=[c[0] for c in FAMILY_SWITCHES])
+def test_conv_family_switch_on_and_off_in_one_process(case):
+    """The family's kernel and the next more general one on the same operands, both within the family test's own bound
+    (1.5e-2 of the output scale: bf16 operands, f32 sums) of f64 torch; the name query follows the switch.  (No bit
+    equality between the two: they sum in different orders.)"""
+    switch, family, c1, c2, cout, n, h, w_, r, s, stride, ph, pw, transposed, has_bias, want_stats = case
+    g = torch.Generator().manual_seed(sum(case[2:13]))
+    x1 = torch.randn(n, c1, h, w_, generator=g).bfloat16().float()
+    x2 = torch.randn(n, c2, h, w_, generator=g).bfloat16().float() if c2 else None
+    cin = c1 + c2
+    wshape = (cin, cout, r, s) if transposed else (cout, cin, r, s)
+    w = (torch.randn(wshape, generator=g) * (2.0 / (cin * r * s)) ** 0.5).bfloat16().float()
+    bias = torch.randn(cout, generator=g) if has_bias else None
+    xin = (x1 if x2 is None else torch.cat((x1, x2), 1)).double()
+    bd = None if bias is None else bias.double()
+    ref = F.conv_transpose2d(xin, w.double(), bd, stride, (ph, pw)) if transposed else F.conv2d(xin, w.double(), bd, stride, (ph, pw))
+    xs = [ops.to_nhwc(x1.cuda(), _lib.BF16), ops.to_nhwc(x2.cuda(), _lib.BF16) if c2 else None]
+    wp = ops.pack_weight(w.cuda(), transposed, c1, c2, _lib.BF16)
+    bp = None
+    if bias is not None:
+        bp = torch.zeros(ops.cpad(cout), device="cuda")
+        bp[:cout] = bias.cuda()
+    p, q = ref.shape[2:]
+
+    def run():
+        name = _lib.value("msml_conv2d_kernel", xs[0].shape[3], xs[1].shape[3] if c2 else 0, ops.cpad(cout), n, h, w_, p, q, r, s,
+                          stride, ph, pw, int(transposed), _lib.BF16, _lib.BF16, int(want_stats)).decode()
+        out, _ = ops.conv2d(xs[0], xs[1], wp, bp, ops.cpad(cout), r, s, stride, ph, pw, transposed, want_stats=want_stats)
+        return name, ops.to_nchw(out, cout).cpu().double()
+
+    with _lib.option(switch, 0):
+        name_on, got_on = run()
+    with _lib.option(switch, 1):
+        name_off, got_off = run()
+    assert name_on.startswith(family), name_on
+    assert name_off != name_on and not name_off.startswith(family), name_off
+    for got in (got_on, got_off):
+        assert (got - ref).abs().max().item() <= 1.5e-2 * ref.abs().max().item()

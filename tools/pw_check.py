@@ -3,9 +3,9 @@ import os, sys, torch
 sys.path.insert(0, os.getcwd())
 from msml_amd import _lib, ops
 def both(fn):
-    os.environ["MSML_PW_CONV"] = "1"; a = fn(); torch.cuda.synchronize()
-    os.environ["MSML_PW_CONV"] = "0"; b = fn(); torch.cuda.synchronize()
-    os.environ.pop("MSML_PW_CONV"); return a, b
+    with _lib.option("MSML_PW_CONV", 1): a = fn(); torch.cuda.synchronize()
+    with _lib.option("MSML_PW_CONV", 0): b = fn(); torch.cuda.synchronize()
+    return a, b
 for cin, cout, n, h in [(32, 64, 256, 112), (32, 64, 256, 56), (64, 32, 256, 56), (64, 128, 256, 28), (128, 64, 256, 28), (64, 64, 256, 28)]:
     g = torch.Generator().manual_seed(1)
     x = (torch.randn(n, h, h, cin, device="cuda")).bfloat16()
