@@ -31,7 +31,8 @@ extern "C" {
 
 #define MSML_ABI_VERSION 1
 
-enum { MSML_F32 = 0, MSML_BF16 = 1, MSML_BF16X3 = 2 };   /* BF16X3: split-bf16 planes, see msml_conv2d_x3 */
+enum { MSML_F32 = 0, MSML_BF16 = 1, MSML_BF16X3 = 2,     /* BF16X3: split-bf16 planes, see msml_conv2d_x3 */
+       MSML_F64 = 3 };                                   /* msml_search_topk only */
 
 enum {
   MSML_OK = 0,
@@ -747,6 +748,34 @@ int msml_align_pairs(const unsigned char* faces, const int* desc, float* out, in
  *   (the reference's own NB path puts a 3-channel tensor into the 1-channel batch and raises). */
 int msml_eval_pairs(const unsigned char* src, int N, int H, int W, const int* desc, float* out, int out_h, int out_w,
                     int gray, int norm, int fill, int protocol, long seed, long index0, void* stream);
+
+/* ---------------------------------------------------------------- 1:N identification: fused top-k search -----
+ * The search behind the identification lists the reference prepares and never evaluates: the MegaFace list
+ * (datasets/benchmarks/get_list.py:138-208: 1 000 000 distractors under label 9999 plus FaceScrub probe / mate pairs),
+ * the AR list (datasets/benchmarks/get_list.py:100-135) and the 1:N part of IJB-C on the pooled template features of
+ * msml_template_pool.
+ *
+ * msml_search_topk: probe [P][E] and gallery [G][E], both row-major in `dtype` (MSML_F32 or MSML_F64), 16-byte aligned.
+ *   For every probe row the k largest inner products with the gallery rows: scores [P][k] in `dtype`, index [P][k] the
+ *   gallery rows, in descending score with ties by ascending gallery row (-0.0 and 0.0 are equal and tie): the order of
+ *   np.lexsort((arange(G), -s)).  One workgroup owns 64 probe rows and one of `splits` ranges of gallery columns, runs
+ *   the reduction over E on the 16x16x4 MFMA of the dtype and keeps per-row sorted lists of k entries in LDS; the
+ *   P x G score matrix is never written.  splits > 1: every split writes its partial lists ((-inf, -1) fillers where it
+ *   has fewer than k columns) to `workspace` ([splits][P][k] scores, then indices) and a second kernel merges them;
+ *   splits == 1 writes the result directly, workspace may be NULL.  Every dot product is summed over the channels in
+ *   ascending order by the same instructions whatever the split; no floating-point atomics, no workgroup waits for
+ *   another: the result has the same bits for every `splits` and in every run.
+ *   Limits: E % 4 == 0, 1 <= k <= 32, k <= G, 1 <= splits <= 65535, P and G below 2^31.  Every violation, a null
+ *   pointer, a misaligned pointer, another dtype and a workspace smaller than msml_search_topk_workspace return
+ *   MSML_ERR_SHAPE before any launch.  NaN scores are never listed: the caller checks its inputs.
+ * msml_search_topk_splits: the default split count: enough workgroups to fill the part, never more than 64-column
+ *   tiles, no empty split.  0 for P or G outside their limits.
+ * msml_search_topk_workspace: bytes of `workspace` (8-byte aligned) for any dtype: splits * P * k * 12, 0 for one
+ *   split. */
+int msml_search_topk_splits(long P, long G, int k);
+size_t msml_search_topk_workspace(long P, int k, int splits);
+int msml_search_topk(const void* probe, long P, const void* gallery, long G, int E, int k, int splits, int dtype,
+                     void* scores, int* index, void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "msml_hip.h")
 LIBPATH = os.environ.get("MSML_LIB", os.path.join(_HERE, "libmsml_hip.so"))   # (override: another build, e.g. the LDS-guard build)
 
 F32, BF16 = 0, 1
+F64 = 3                   # MSML_F64: msml_search_topk only
 UNSUPPORTED = -4          # MSML_ERR_UNSUPPORTED
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16}
 DTYPE_OF = {torch.float32: F32, torch.bfloat16: BF16}
@@ -34,7 +35,7 @@ def parse_header(path=HEADER):
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     src = re.sub(r"//[^\n]*", "", src)
     protos = {}
-    for m in re.finditer(r"\b(int|long|const char\s*\*)\s+(msml_\w+)\s*\(([^)]*)\)\s*;", src):
+    for m in re.finditer(r"\b(int|long|size_t|const char\s*\*)\s+(msml_\w+)\s*\(([^)]*)\)\s*;", src):
         ret, name, args = m.group(1), m.group(2), m.group(3).strip()
         params = []
         if args and args != "void":
@@ -45,7 +46,7 @@ def parse_header(path=HEADER):
                 else:
                     ty, pn = a.rsplit(" ", 1)
                     params.append((_CT[ty.replace("const ", "").strip()], pn))
-        rt = {"int": ctypes.c_int, "long": ctypes.c_long}.get(ret, ctypes.c_char_p)
+        rt = {"int": ctypes.c_int, "long": ctypes.c_long, "size_t": ctypes.c_size_t}.get(ret, ctypes.c_char_p)
         protos[name] = (rt, params)
     return protos
 
