@@ -32,7 +32,7 @@ extern "C" {
 #define MSML_ABI_VERSION 1
 
 enum { MSML_F32 = 0, MSML_BF16 = 1, MSML_BF16X3 = 2,     /* BF16X3: split-bf16 planes, see msml_conv2d_x3 */
-       MSML_F64 = 3 };                                   /* msml_search_topk only */
+       MSML_F64 = 3 };                                   /* msml_search_topk, msml_allpairs_pass */
 
 enum {
   MSML_OK = 0,
@@ -776,6 +776,45 @@ int msml_search_topk_splits(long P, long G, int k);
 size_t msml_search_topk_workspace(long P, int k, int splits);
 int msml_search_topk(const void* probe, long P, const void* gallery, long G, int E, int k, int splits, int dtype,
                      void* scores, int* index, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- all-pairs verification: TAR @ FAR ------------
+ * The second protocol of the MegaFace list (datasets/benchmarks/get_list.py:138-208): TAR at a FAR target over EVERY
+ * probe x gallery comparison, which the reference prepares and never evaluates.  The threshold of a target is an order
+ * statistic of the impostor scores; msml_amd/allpairs.py finds it by a radix select on order-preserving keys, one
+ * msml_allpairs_pass per level, and the P x G score matrix is never written.
+ *
+ * msml_allpairs_pass: probe [P][E] and gallery [G][E], row-major in `dtype` (MSML_F32 or MSML_F64), 16-byte aligned;
+ *   probe_code [P] / gallery_code [G]: one non-negative int32 subject code per row.  The score of pair (p, g) is the
+ *   inner product of the two rows with the bits msml_search_topk gives it (the same MFMA chain from a zero accumulator,
+ *   channels ascending), -0.0 counted as 0.0; the pair is genuine when the codes are equal, an impostor otherwise.
+ *   symmetric = 1: gallery and gallery_code are probe and probe_code themselves (G == P) and only the pairs p < g
+ *   exist.  The key of a score has W = 32 (f32) or 64 (f64) bits: all bits of a negative flipped, the sign bit of a
+ *   non-negative set, so keys order as scores do.  A range (prefix, bits) holds the keys with key >> (W - bits) ==
+ *   prefix (bits = 0: all keys).  By `mode`:
+ *   MSML_ALLPAIRS_HIST     for each of the n_ranges <= 16 ranges (range_prefix, range_bits: HOST arrays) the impostor
+ *                          keys inside it are counted by their next bins_log2 bits into hist [n_ranges][1 << bins_log2]
+ *                          (u64); range_bits[r] + bins_log2 <= W and n_ranges << bins_log2 <= 8192 (the workgroup's
+ *                          LDS histogram, u32, flushed before a bin could overflow).
+ *   MSML_ALLPAIRS_COLLECT  the impostor SCORES (in `dtype`) inside range r of the n_ranges <= 16 are appended to row r
+ *                          of cand [n_ranges][cand_cap] in the order they arrive; cand_count [n_ranges] (u64) counts
+ *                          every one of them, also those beyond cand_cap, which are not stored.
+ *   MSML_ALLPAIRS_COUNT    counts [2][n_thr] (u64): the genuine, then the impostor pairs whose score widened to f64
+ *                          is > thresholds[t] (HOST array of n_thr <= 16 doubles, no NaN).
+ *   hist, cand_count and counts are ADDED to: the caller zeroes them.  Arguments of another mode are ignored and may
+ *   be NULL / 0.  One workgroup owns 64 probe rows and one of `splits` ranges of gallery columns; rows beyond P,
+ *   columns beyond G and channels beyond E are not counted.  All results are integer counts (or a set of scores), so
+ *   the order of the atomics cannot change them: the same result for every `splits` and in every run.
+ *   Limits: E % 4 == 0, 1 <= splits <= 65535, P and G below 2^31.  Every violation, a null or misaligned pointer
+ *   (rows 16 bytes, codes 4, hist / cand / cand_count / counts 8) and another dtype or mode return MSML_ERR_SHAPE before
+ *   any launch.  NaN scores are not defined: the caller checks its inputs.
+ * msml_allpairs_splits: the default split count, as msml_search_topk_splits.  0 for P or G outside their limits. */
+enum { MSML_ALLPAIRS_HIST = 0, MSML_ALLPAIRS_COLLECT = 1, MSML_ALLPAIRS_COUNT = 2 };
+int msml_allpairs_splits(long P, long G);
+int msml_allpairs_pass(const void* probe, long P, const int* probe_code, const void* gallery, long G,
+                       const int* gallery_code, int E, int dtype, int symmetric, int mode, int n_ranges,
+                       const unsigned long long* range_prefix, const int* range_bits, int bins_log2,
+                       unsigned long long* hist, void* cand, unsigned long long* cand_count, long cand_cap,
+                       const double* thresholds, int n_thr, unsigned long long* counts, int splits, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "msml_hip.h")
 LIBPATH = os.environ.get("MSML_LIB", os.path.join(_HERE, "libmsml_hip.so"))   # (override: another build, e.g. the LDS-guard build)
 
 F32, BF16 = 0, 1
-F64 = 3                   # MSML_F64: msml_search_topk only
+F64 = 3                   # MSML_F64: msml_search_topk, msml_allpairs_pass
 UNSUPPORTED = -4          # MSML_ERR_UNSUPPORTED
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16}
 DTYPE_OF = {torch.float32: F32, torch.bfloat16: BF16}
