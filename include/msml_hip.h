@@ -489,6 +489,38 @@ int msml_occ_apply_out(const unsigned char* src, const int* desc, const unsigned
                        const int* tabw, const int* tabh, float* img, long* msk, float* ori, int N, int H, int W,
                        int out_h, int out_w, int gray, int norm, int light, void* stream);
 
+/* The facial-mask branch of the training mix: FaceByRandOccMask.__getitem__ with mask_flag (datasets/load_dataset.py:113,
+ * 167-177: the face comes from mask_out.rec, the segmentation target from mask.rec) and _add_gauss_to_mask (:203-280).
+ * The renders are the caller's; what is done with them runs here.
+ * msml_occ_draw_mask: msml_occ_draw_out with one more draw per image: occ_unif(draw 46) < p_mask makes the image a MASK
+ *   sample (kind 8; p_mask = 0.2 is the reference's 2 / 10, :113).  An image that is not flagged gets msml_occ_draw_out's
+ *   descriptor word for word; a flagged one gets a descriptor that does not depend on p_mask: words 1-7 and 12-15 zero,
+ *   8-11 flip and light as always, 16 type (0 Gaussian light, 1 Gaussian noise, 2 block: trans_type = randint(0, 11)
+ *   >= 7, 5-6, <= 4, :219), 17-20 the rectangle lx, ly, rx, ry in OUTPUT pixels (:222-223, :251-252), 21 sign (+1 / -1,
+ *   :238, :255), 22-24 the colour-jitter bits (:261), 25-27 the f32 bits of the light's centre x, y (absolute, as
+ *   _get_gauss :307-308 draws them) and radius (:316), 28-29 the low / high half of the sample's noise key
+ *   mix(mix(seed + 0x6D61736B) + offset + n).  p_mask > 0 needs out_h >= 111 and out_w >= 110 (the reference's
+ *   rectangle is not scaled with the size and does not fit below).
+ * msml_occ_apply_mask: an overlay launched AFTER msml_occ_apply[_tex | _out] on the same desc / img / msk: one workgroup
+ *   per image, which returns at once unless the image is a mask sample whose row r = rows[n] (rows == NULL: r = n) lies
+ *   in 0 .. M - 1.  Otherwise it rewrites img[n] and msk[n] from masked[r] ([M][H][W][3] uint8 RGB) and mask[r]
+ *   ([M][H][W] uint8, the 'L' plane): convert('L') of the face when gray, Image.resize(BILINEAR) of face and mask as
+ *   msml_occ_apply_out, flip, ToTensor, light at the output size and / max (:183-201), then :209-280: mask <= 128 -> 0
+ *   (occluded) else 1; on occluded pixels inside the rectangle a float16 offset -- (exp(-0.5 d^2 / r^2) - 0.5) * 2 * 0.4
+ *   * sign with the int16-truncated offsets of _get_gauss (relative coordinate minus absolute centre, as written), a
+ *   standard normal, or +-1 for the block -- times the jitter bit of the channel (light and noise), folded to gray as
+ *   (0.2989 l0 + 0.5870 l1 + 0.1140 l2) / 3 in float16 when gray; img = face - offset in f32, not clamped; Normalize
+ *   only when norm != 0.  The normal variate of output pixel (x, y): r = mix(key + y * 65536 + x) with the key of words
+ *   28-29 (mix = the splitmix64 step of msml_occ_draw), u1 = ((r >> 40) + 1) / 2^24, u2 = ((r >> 8) & 0xFFFFFF) /
+ *   2^24, z = sqrt(-2 ln u1) cos(2 pi u2) in f32, rounded to float16: independent of launch geometry, batch split and
+ *   p_mask.  ori is not touched (the clean face msml_occ_apply* wrote).  Same refusals as msml_occ_apply_out:
+ *   MSML_ERR_UNSUPPORTED before any launch for out_w % 4 != 0 or more than 160 KB of LDS. */
+int msml_occ_draw_mask(long seed, long offset, int N, int H, int W, int out_h, int out_w, int mode, int lo, int hi,
+                       int flip, const int* meta, int nsets, float p_mask, int* desc, void* stream);
+int msml_occ_apply_mask(const unsigned char* masked, const unsigned char* mask, const int* rows, int M, const int* desc,
+                        const int* tabw, const int* tabh, float* img, long* msk, int N, int H, int W, int out_h,
+                        int out_w, int gray, int norm, int light, void* stream);
+
 /* Backward-data of the OSB decoder's ConvTranspose2d(36 -> 18, k 4, s 2, p 1) on cat(seg, gcm) (backbones/osb/unet.py:
  * 140-156, autograd of deconv2..5) for BOTH input segments from one pass over dY (bf16):
  *   dxS[n, i, j, ci] = sum_{r, s, co} dy[n, 2i - 1 + r, 2j - 1 + s, co] * w[S * 18 + ci][co][r][s]

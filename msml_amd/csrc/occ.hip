@@ -15,7 +15,10 @@
 //                                   per sample: random entry, random rescale with PIL's bicubic resampling restated
 //                                   bit for bit (premultiplied alpha, two fixed-point passes, coefficient tables built
 //                                   on the host), placement rule of each class, alpha-keyed paste and mask
-// Facial-mask records (mask_out.rec) need the dataset's 3D-mask renders and are not synthesised.
+// Facial-mask samples (load_dataset.py:113,167-177 + _add_gauss_to_mask :203-280): the 3D-mask renders (mask_out.rec /
+// mask.rec) are the caller's, as the occluder PNGs are; what is done with them runs here (k_occ_apply_mask below): Resize,
+// flip, light, the <= 128 binarisation and the Gaussian light / Gaussian noise / block on the mask pixels.  Only the
+// renderer itself is not part of this pipeline.
 //
 // Random draws come from a counter-based generator (splitmix64 of seed, image index, draw index): the
 // same (seed, offset) gives the same batch on any launch geometry, and the CPU oracle regenerates it.
@@ -29,10 +32,18 @@
 
 #define OCC_DESC 64      // int32 words per image
 #define OCC_MAXV 24      // polygon vertices (at most 1 + 2 * 10)
-enum { OCC_NONE = 0, OCC_RECT = 1, OCC_ELLIPSE = 2, OCC_BLOCK = 3, OCC_POLY = 4, OCC_GLASSES = 5, OCC_SCARF = 6, OCC_OBJECT = 7 };
+enum { OCC_NONE = 0, OCC_RECT = 1, OCC_ELLIPSE = 2, OCC_BLOCK = 3, OCC_POLY = 4, OCC_GLASSES = 5, OCC_SCARF = 6, OCC_OBJECT = 7, OCC_MASK = 8 };
 // desc: 0 kind | 1 x0 / cx | 2 y0 / cy | 3 w / aw | 4 h / ah | 5,6,7 r g b | 8 flip | 9 light cx (f32 bits)
 //       10 light cy (f32 bits) | 11 light scale (f32 bits) | 12 polygon vertex count | 13 texture set | 14 texture entry
 //       15 reserved | 16 + 2 v, 17 + 2 v: polygon vertex v (x, y)
+// Mask samples (kind 8, msml_occ_draw_mask): words 1-7 and 12-15 stay 0 -- the apply kernels above the overlay index the
+//   patch buffer with words 1-4 and treat such a descriptor as a clean sample -- and everything of the mask sits where a
+//   polygon's vertices would: 16 type (0 Gaussian light, 1 Gaussian noise, 2 block) | 17 lx | 18 ly | 19 rx | 20 ry (the
+//   rectangle in OUTPUT pixels, after the flip) | 21 sign (+1 / -1) | 22, 23, 24 colour-jitter bit of r, g, b | 25 light
+//   centre x | 26 light centre y | 27 light radius (f32 bits) | 28, 29 the low and high half of the sample's noise key.
+//   Draw indices: 46 flag, 47 type, 48-51 the rectangle's four offsets, 52 sign, 53 / 54 centre, 55 radius, 56-58 jitter
+//   (0-13 and 16-45 belong to the other kinds).  Per-pixel normal variates come from a key domain of their own
+//   (occ_mask_normal: seed + 0x6D61736B): img * 64 + k has no room.
 // Texture kinds (5-7): 1, 2 = top-left corner of the paste, 3, 4 = resampled width / height of the occluder.
 // Occluder sets: meta[set][OCC_META] int32 = 0 byte offset of the set in the atlas | 1 entries | 2 h0 | 3 w0 | 4 kind
 //   | 5 wmin | 6 wmax | 7 hmin | 8 hmax (resampled sizes the tables cover) | 9 wdir | 10 hdir: dir[wdir + w' - wmin] is
@@ -49,6 +60,10 @@ __host__ __device__ inline unsigned long long occ_mix(unsigned long long z) {
 }
 __host__ __device__ inline unsigned int occ_u32(unsigned long long seed, unsigned long long img, int k) {
   return (unsigned int)(occ_mix(occ_mix(seed) + img * 64ULL + (unsigned long long)k) >> 32);
+}
+// a mask sample's key of the per-pixel normal variates (occ_mask_normal below): a domain of its own, seed + "mask"
+__host__ __device__ inline unsigned long long occ_mask_key(unsigned long long seed, unsigned long long img) {
+  return occ_mix(occ_mix(seed + 0x6D61736BULL) + img);
 }
 // integer in [a, b) (np.random.randint(a, b)): multiply-shift, no rejection
 __host__ __device__ inline int occ_randint(unsigned int u, int a, int b) {
@@ -93,14 +108,38 @@ __device__ inline int occ_pick_set(const int* meta, int nsets, int kind, unsigne
 
 __global__ void k_occ_draw(unsigned long long seed, unsigned long long offset, int N, int H, int W, int mode, int lo,
                            int hi, int flip_on, const int* __restrict__ meta, int nsets, int* __restrict__ desc,
-                           int LH, int LW) {
+                           int LH, int LW, float p_mask) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const unsigned long long img = offset + (unsigned long long)i;
   int d[OCC_DESC];
   for (int k = 0; k < OCC_DESC; k++) d[k] = 0;
   int kind = OCC_NONE;
-  if (mode == 0) {
+  // load_dataset.py:113: a mask sample takes no occluder; its descriptor does not depend on p_mask
+  const bool masked = p_mask > 0.f && occ_unif(occ_u32(seed, img, 46)) < p_mask;
+  if (masked) {                                 // _add_gauss_to_mask :219-261, _get_gauss :302-316
+    kind = OCC_MASK;
+    const int tt = occ_randint(occ_u32(seed, img, 47), 0, 11);
+    const int type = tt >= 7 ? 0 : (tt >= 5 ? 1 : 2);
+    const int lx = 40 + occ_randint(occ_u32(seed, img, 48), -20, 21);
+    const int rx = 100 + occ_randint(occ_u32(seed, img, 49), -20, 11);
+    int ly = 1, ry = 111;
+    if (type == 2) {
+      ly = 40 + occ_randint(occ_u32(seed, img, 50), -20, 20);
+      ry = 100 + occ_randint(occ_u32(seed, img, 51), -20, 10);
+    }
+    d[16] = type; d[17] = lx; d[18] = ly; d[19] = rx; d[20] = ry;
+    d[21] = occ_randint(occ_u32(seed, img, 52), 0, 2) * 2 - 1;
+    for (int c = 0; c < 3; c++) d[22 + c] = occ_randint(occ_u32(seed, img, 56 + c), 0, 2);
+    const int rw = rx - lx, rh = ry - ly, edge = rw > rh ? rw : rh;
+    const int rlo = (int)((double)edge / 1.5), rhi = (int)((double)edge * 1.5);
+    d[25] = __float_as_int((float)lx + (float)rw * occ_unif(occ_u32(seed, img, 53)));
+    d[26] = __float_as_int((float)ly + (float)rh * occ_unif(occ_u32(seed, img, 54)));
+    d[27] = __float_as_int((float)rlo + (float)(rhi - rlo) * occ_unif(occ_u32(seed, img, 55)));
+    const unsigned long long nk = occ_mask_key(seed, img);        // the sample's key of occ_mask_normal
+    d[28] = (int)(unsigned int)(nk & 0xFFFFFFFFULL);
+    d[29] = (int)(unsigned int)(nk >> 32);
+  } else if (mode == 0) {
     const int pick = occ_randint(occ_u32(seed, img, 0), 0, 4);
     kind = pick == 0 ? OCC_RECT : (pick == 1 ? OCC_ELLIPSE : (pick == 2 ? OCC_POLY : OCC_NONE));
   } else if (mode == 1) kind = OCC_RECT;
@@ -112,7 +151,7 @@ __global__ void k_occ_draw(unsigned long long seed, unsigned long long offset, i
     kind = six == 0 ? OCC_RECT : six == 1 ? OCC_ELLIPSE : six == 2 ? OCC_POLY : six == 3 ? OCC_GLASSES
          : six == 4 ? OCC_SCARF : six == 5 ? OCC_OBJECT : OCC_NONE;
   } else if (mode >= 7 && mode <= 9) kind = OCC_GLASSES + (mode - 7);
-  if (kind >= OCC_GLASSES) {
+  if (kind >= OCC_GLASSES && kind <= OCC_OBJECT) {
     const int set = occ_pick_set(meta, nsets, kind, occ_u32(seed, img, 1));
     if (set < 0) kind = OCC_NONE;
     else {
@@ -255,7 +294,7 @@ __global__ void __launch_bounds__(256) k_occ_resize(const unsigned char* __restr
   extern __shared__ unsigned char sm[];
   const int n = blockIdx.x, t = threadIdx.x;
   const int* d = desc + n * OCC_DESC;
-  if (d[0] < OCC_GLASSES) return;
+  if (d[0] < OCC_GLASSES || d[0] > OCC_OBJECT) return;      // (a mask sample, kind 8, has no texture)
   const int* m = meta + d[13] * OCC_META;
   const int h0 = m[2], w0 = m[3], ow = d[3], oh = d[4];
   const unsigned char* e = atlas + (long)m[0] + (long)d[14] * h0 * w0 * 4;
@@ -402,7 +441,7 @@ extern "C" int msml_occ_draw(long seed, long offset, int N, int H, int W, int mo
                              int flip, int* desc, void* stream) {
   MSML_CHECK(desc && N > 0 && H >= 32 && W >= 32 && mode >= 0 && mode <= 4 && lo >= 0 && hi > lo && hi <= 101,
              MSML_ERR_SHAPE, "occ_draw: bad arguments N=%d H=%d W=%d mode=%d lo=%d hi=%d", N, H, W, mode, lo, hi);
-  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, nullptr, 0, desc, H, W);
+  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, nullptr, 0, desc, H, W, 0.f);
   MSML_LAUNCH_OK("occ_draw");
   return MSML_OK;
 }
@@ -413,7 +452,7 @@ extern "C" int msml_occ_draw_tex(long seed, long offset, int N, int H, int W, in
              MSML_ERR_SHAPE, "occ_draw_tex: bad arguments N=%d H=%d W=%d mode=%d lo=%d hi=%d", N, H, W, mode, lo, hi);
   MSML_CHECK(mode < 5 || (meta && nsets > 0 && nsets <= 16), MSML_ERR_SHAPE,
              "occ_draw_tex: modes 5-9 need 1..16 occluder sets (got %d)", nsets);
-  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, meta, nsets, desc, H, W);
+  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, meta, nsets, desc, H, W, 0.f);
   MSML_LAUNCH_OK("occ_draw_tex");
   return MSML_OK;
 }
@@ -691,7 +730,7 @@ extern "C" int msml_occ_draw_out(long seed, long offset, int N, int H, int W, in
              "occ_draw_out: bad arguments N=%d H=%d W=%d out=%dx%d mode=%d lo=%d hi=%d", N, H, W, out_h, out_w, mode, lo, hi);
   MSML_CHECK(mode < 5 || (meta && nsets > 0 && nsets <= 16), MSML_ERR_SHAPE,
              "occ_draw_out: modes 5-9 need 1..16 occluder sets (got %d)", nsets);
-  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, mode < 5 ? nullptr : meta, mode < 5 ? 0 : nsets, desc, out_h, out_w);
+  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, mode < 5 ? nullptr : meta, mode < 5 ? 0 : nsets, desc, out_h, out_w, 0.f);
   MSML_LAUNCH_OK("occ_draw_out");
   return MSML_OK;
 }
@@ -718,5 +757,303 @@ extern "C" int msml_occ_apply_out(const unsigned char* src, const int* desc, con
   }
   k_occ_apply_out<<<N, OCC_OUT_T, (size_t)L.total, (hipStream_t)stream>>>(src, desc, patch, patch_stride, tabw, tabh, img, msk, ori, H, W, out_h, out_w, gray, norm, light);
   MSML_LAUNCH_OK("occ_apply_out");
+  return MSML_OK;
+}
+
+// ---------------------------------------------------------------- facial-mask samples
+// FaceByRandOccMask.__getitem__ with mask_flag (datasets/load_dataset.py:113-139,167-177) and _add_gauss_to_mask
+// (:203-280) as an OVERLAY: launched after k_occ_apply / k_occ_apply_out, which wrote every sample -- a mask sample (kind 8,
+// words 1-4 zero) as a clean one, and ori, the clean src face, for good.  A workgroup whose image is not a mask sample, or
+// whose row is not one of the M the caller holds, returns before it reads anything else; the others rewrite img and msk:
+//   masked[row] -> convert('L') when gray -> Resize (the two fixed-point passes of k_occ_apply_out) -> flip -> ToTensor
+//   -> light at the output size, / max  (_add_gauss_to_face, unchanged)
+//   mask[row]   -> Resize -> flip -> value <= 128 ? 0 (occluded) : 1  (:210-212, :278; NOT the != 255 of the occluders)
+//   msk_light   =  float16 offset on the occluded pixels inside the rectangle (words 17-20, output pixels):
+//       type 0  (exp(-0.5 d^2 / r^2) - 0.5) * 2 * 0.4 * sign, d from the int16-truncated  (x - lx) - cx,  (y - ly) - cy
+//               (_get_gauss :319-323 subtracts the ABSOLUTE centre from the RELATIVE coordinate; restated as written),
+//               r^2 = f32(r * r in f64) as numpy divides an f32 array by a Python float
+//       type 1  a standard normal (occ_mask_normal)
+//       type 2  sign (black or white block)
+//     types 0 / 1: times the channel's jitter bit (:261); gray: (0.2989 l0 + 0.5870 l1 + 0.1140 l2) / 3 with every
+//     operation rounded to float16 (:265-267)
+//   img = face - msk_light in f32, not clamped (:271) -> Normalize only when asked.
+// LDS as k_occ_apply_out without the clean planes, plus MB [oh][ow], the binarised mask the last pass reads.
+struct OccMaskLds {
+  long tabw, tabh, raw, mk, s, bh, o, mb, total;
+};
+__host__ __device__ inline OccMaskLds occ_mask_lds(int H, int W, int oh, int ow, int C) {
+  OccMaskLds L;
+  long off = OCC_OUT_HDR;
+  L.tabw = off; off += ow != W ? occ_r16((long)ow * OCC_RT * 4) : 0;
+  L.tabh = off; off += oh != H ? occ_r16((long)oh * OCC_RT * 4) : 0;
+  L.raw = off;  off += occ_r16((long)H * W * 3);
+  L.mk = off;   off += occ_r16((long)H * W);
+  L.s = off;    off += occ_r16((long)H * W);
+  L.bh = off;   off += ow != W ? occ_r16((long)H * ow) : 0;
+  L.o = off;    off += occ_r16((long)C * oh * ow);
+  L.mb = off;   off += occ_r16((long)oh * ow);
+  L.total = off;
+  return L;
+}
+// The standard normal of output pixel (x, y) of image `img` (= offset + n), as a float16: a key domain of its own
+// (seed + "mask"), keyed by the absolute pixel, so it depends on nothing else: r = mix(key + y * 65536 + x) with the image's
+// key = mix(mix(seed + 0x6D61736B) + img), which k_occ_draw leaves in words 28 (low half) and 29 (high half).  Box-Muller
+// in f32 from two 24-bit uniforms, the first in (0, 1]: u1 = ((r >> 40) + 1) / 2^24, u2 = ((r >> 8) & 0xFFFFFF) / 2^24,
+// z = sqrt(-2 ln u1) * cos(2 pi u2).
+__device__ __forceinline__ __half occ_mask_normal(unsigned long long key, int x, int y) {
+  const unsigned long long r = occ_mix(key + (unsigned long long)(y * 65536 + x));
+  const float u1 = (float)((unsigned int)(r >> 40) + 1u) * (1.0f / 16777216.0f);
+  const float u2 = (float)((unsigned int)(r >> 8) & 0xFFFFFFu) * (1.0f / 16777216.0f);
+  const float rad = sqrtf(-2.0f * logf(u1));
+  const float ang = 6.2831854820251465f * u2;
+  return __float2half(rad * cosf(ang));
+}
+__device__ __forceinline__ __half occ_hmul(__half a, __half b) { return __float2half(__half2float(a) * __half2float(b)); }
+__device__ __forceinline__ __half occ_hadd(__half a, __half b) { return __float2half(__half2float(a) + __half2float(b)); }
+
+__global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_mask(
+    const unsigned char* __restrict__ masked, const unsigned char* __restrict__ mask, const int* __restrict__ rows, int M,
+    const int* __restrict__ desc, const int* __restrict__ tabw, const int* __restrict__ tabh, float* __restrict__ img,
+    long* __restrict__ msk, int H, int W, int oh, int ow, int gray, int norm, int light) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smm[];
+  const int n = blockIdx.x, t = threadIdx.x;
+  // both tests are uniform over the workgroup and come before the first barrier
+  if (desc[n * OCC_DESC] != OCC_MASK) return;
+  const int row = rows ? rows[n] : n;
+  if (row < 0 || row >= M) return;               // no render for this sample: it stays the clean one
+  const int C = gray ? 1 : 3, HW = H * W, ohow = oh * ow;
+  const OccMaskLds L = occ_mask_lds(H, W, oh, ow, C);
+  int* d = reinterpret_cast<int*>(smm);
+  float* red = reinterpret_cast<float*>(smm + OCC_DESC * 4);
+  const int* tw = ow != W ? reinterpret_cast<const int*>(smm + L.tabw) : nullptr;
+  const int* th = oh != H ? reinterpret_cast<const int*>(smm + L.tabh) : nullptr;
+  unsigned char* raw = smm + L.raw;
+  unsigned char* Mk = smm + L.mk;
+  unsigned char* S = smm + L.s;
+  unsigned char* Bh = smm + L.bh;
+  unsigned char* O = smm + L.o;
+  unsigned char* MB = smm + L.mb;
+  MSML_LDS_REGION(MB, (long)ohow);
+  if (t < OCC_DESC) d[t] = desc[n * OCC_DESC + t];
+  if (tw) for (int i = t; i < ow * OCC_RT; i += OCC_OUT_T) reinterpret_cast<int*>(smm + L.tabw)[i] = tabw[i];
+  if (th) for (int i = t; i < oh * OCC_RT; i += OCC_OUT_T) reinterpret_cast<int*>(smm + L.tabh)[i] = tabh[i];
+  {
+    const unsigned char* s = masked + (long)row * HW * 3;
+    if ((HW * 3) % 16 == 0 && (reinterpret_cast<uintptr_t>(masked) & 15) == 0) {
+      for (int i = t; i < HW * 3 / 16; i += OCC_OUT_T)
+        reinterpret_cast<u32x4*>(raw)[i] = reinterpret_cast<const u32x4*>(s)[i];
+    } else {
+      for (int i = t; i < HW * 3; i += OCC_OUT_T) raw[i] = s[i];
+    }
+    const unsigned char* m = mask + (long)row * HW;
+    if (HW % 16 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0) {
+      for (int i = t; i < HW / 16; i += OCC_OUT_T)
+        reinterpret_cast<u32x4*>(Mk)[i] = reinterpret_cast<const u32x4*>(m)[i];
+    } else {
+      for (int i = t; i < HW; i += OCC_OUT_T) Mk[i] = m[i];
+    }
+  }
+  __syncthreads();
+  const bool flip = d[8] != 0;
+  // planes: 0 = mask, 1 .. C = rendered face
+  for (int pl = 0; pl <= C; pl++) {
+    const int c = pl == 0 ? 0 : pl - 1;
+    const unsigned char* P = Mk;
+    if (pl > 0) {
+      for (int p = t; p < HW; p += OCC_OUT_T) {
+        const unsigned char* q = raw + p * 3;
+        S[p] = (unsigned char)(gray ? occ_luma(q[0], q[1], q[2]) : q[c]);
+      }
+      __syncthreads();
+      P = S;
+    }
+    const unsigned char* Q = P;                       // [H][ow]
+    if (tw) {                                         // horizontal pass, four outputs per lane
+      for (int i = t; i < H * ow / 4; i += OCC_OUT_T) {
+        const int y = (i * 4) / ow, xx = i * 4 - y * ow;
+        unsigned int pack = 0;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          const int* k = tw + (xx + e) * OCC_RT;
+          const unsigned char* rw = P + y * W + k[0];
+          int ss = 1 << 21;
+          for (int j = 0; j < k[1]; j++) ss += (int)rw[j] * k[2 + j];
+          pack |= (unsigned int)occ_clip8(ss >> 22) << (8 * e);
+        }
+        reinterpret_cast<unsigned int*>(Bh)[i] = pack;
+      }
+      __syncthreads();
+      Q = Bh;
+    }
+    // vertical pass + flip, four outputs per lane: the mask goes to HBM and, binarised, to MB; the face to O
+    for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
+      const int p = i * 4, yy = p / ow, x = p - yy * ow;
+      const int base = flip ? ow - 4 - x : x;
+      int v[4];
+      if (th) {
+        const int* k = th + yy * OCC_RT;
+        int ss[4] = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
+        for (int j = 0; j < k[1]; j++) {
+          const unsigned int wd = *reinterpret_cast<const unsigned int*>(Q + (k[0] + j) * ow + base);
+          const int kk = k[2 + j];
+#pragma unroll
+          for (int e = 0; e < 4; e++) ss[e] += (int)((wd >> (8 * e)) & 255u) * kk;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; e++) v[e] = occ_clip8(ss[e] >> 22);
+      } else {
+        const unsigned int wd = *reinterpret_cast<const unsigned int*>(Q + yy * ow + base);
+#pragma unroll
+        for (int e = 0; e < 4; e++) v[e] = (int)((wd >> (8 * e)) & 255u);
+      }
+      if (flip) {
+        int s0 = v[0], s1 = v[1];
+        v[0] = v[3]; v[1] = v[2]; v[2] = s1; v[3] = s0;
+      }
+      if (pl == 0) {                                  // :212: <= 128 -> 0 (occluded), else 255; :278: // 255
+        longlong2 a, b;
+        a.x = v[0] > 128; a.y = v[1] > 128; b.x = v[2] > 128; b.y = v[3] > 128;
+        longlong2* o = reinterpret_cast<longlong2*>(msk + (long)n * ohow + p);
+        o[0] = a;
+        o[1] = b;
+        reinterpret_cast<unsigned int*>(MB)[i] = (unsigned int)(v[0] > 128) | ((unsigned int)(v[1] > 128) << 8) |
+                                                 ((unsigned int)(v[2] > 128) << 16) | ((unsigned int)(v[3] > 128) << 24);
+      } else {
+        reinterpret_cast<unsigned int*>(O + (long)c * ohow)[i] =
+            (unsigned int)v[0] | ((unsigned int)v[1] << 8) | ((unsigned int)v[2] << 16) | ((unsigned int)v[3] << 24);
+      }
+    }
+    __syncthreads();                                  // S / Bh are rebuilt for the next plane; O and MB are complete after the last
+  }
+  const float lcx = __int_as_float(d[9]), lcy = __int_as_float(d[10]), lscale = __int_as_float(d[11]);
+  auto lightmap = [&](int x, int y) -> float {        // as k_occ_apply
+    const int ix = (int)((float)x - lcx), iy = (int)((float)y - lcy);
+    const float dist = sqrtf((float)(ix * ix + iy * iy));
+    const float g = expf(-0.5f * (dist * dist) / 16384.0f);
+    const __half g16 = __float2half(g);
+    const __half l16 = __float2half(__half2float(g16) * __half2float(__float2half(lscale)));
+    return __half2float(l16);
+  };
+  float vmax = 0.f;
+  if (light) {
+    for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
+      const int p = i * 4, y = p / ow, x = p - y * ow;
+      float l[4];
+#pragma unroll
+      for (int e = 0; e < 4; e++) l[e] = lightmap(x + e, y);
+      for (int c = 0; c < C; c++) {
+        const unsigned int wd = reinterpret_cast<const unsigned int*>(O + (long)c * ohow)[i];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          float v = (float)((wd >> (8 * e)) & 255u) / 255.0f;
+          v *= l[e];
+          vmax = fmaxf(vmax, v);
+        }
+      }
+    }
+    vmax = wave_max(vmax);
+    if ((t & 63) == 0) red[t >> 6] = vmax;
+    __syncthreads();
+    vmax = red[0];
+#pragma unroll
+    for (int w = 1; w < OCC_OUT_T / 64; w++) vmax = fmaxf(vmax, red[w]);
+  }
+  const int type = d[16], lx = d[17], ly = d[18], rx = d[19], ry = d[20];
+  const float sgn = (float)d[21];
+  const double mcx = (double)__int_as_float(d[25]), mcy = (double)__int_as_float(d[26]);
+  const float mrad = __int_as_float(d[27]);
+  const float r2 = (float)((double)mrad * (double)mrad);
+  const unsigned long long nkey = ((unsigned long long)(unsigned int)d[29] << 32) | (unsigned long long)(unsigned int)d[28];
+  const __half hzero = __float2half(0.f);
+  // float16(0.2989), float16(0.5870), float16(0.1140), float16(3)
+  const __half k0 = __float2half(0.298828125f), k1 = __float2half(0.5869140625f), k2 = __float2half(0.114013671875f);
+  for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
+    const int p = i * 4, y = p / ow, x = p - y * ow;
+    const unsigned int mb = reinterpret_cast<const unsigned int*>(MB)[i];
+    float l[4];
+    __half m16[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      l[e] = light ? lightmap(x + e, y) : 1.f;
+      const int X = x + e;
+      m16[e] = hzero;
+      if (((mb >> (8 * e)) & 255u) == 0u && X >= lx && X < rx && y >= ly && y < ry) {
+        if (type == 0) {
+          const int ix = (int)((double)(X - lx) - mcx), iy = (int)((double)(y - ly) - mcy);
+          const float dist = sqrtf((float)(ix * ix + iy * iy));
+          const float g = expf(-0.5f * (dist * dist) / r2);
+          m16[e] = __float2half((g - 0.5f) * 2.0f * 0.4f * sgn);
+        } else if (type == 1) {
+          m16[e] = occ_mask_normal(nkey, X, y);
+        } else {
+          m16[e] = __float2half(sgn);
+        }
+      }
+    }
+    __half off[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+      for (int e = 0; e < 4; e++) off[c][e] = (type == 2 || d[22 + c] != 0) ? m16[e] : hzero;
+    if (gray) {
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const __half s = occ_hadd(occ_hadd(occ_hmul(k0, off[0][e]), occ_hmul(k1, off[1][e])), occ_hmul(k2, off[2][e]));
+        off[0][e] = __float2half(__half2float(s) / 3.0f);
+      }
+    }
+    for (int c = 0; c < C; c++) {
+      const unsigned int wd = reinterpret_cast<const unsigned int*>(O + (long)c * ohow)[i];
+      f32x4 r;
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        float v = (float)((wd >> (8 * e)) & 255u) / 255.0f;
+        v *= l[e];
+        if (light) v = v / vmax;                      // out_img / out_img.max()  (load_dataset.py:199)
+        v = v - __half2float(c == 0 ? off[0][e] : (c == 1 ? off[1][e] : off[2][e]));      // :271
+        r[e] = norm ? (v - 0.5f) / 0.5f : v;
+      }
+      *reinterpret_cast<f32x4*>(img + ((long)n * C + c) * ohow + p) = r;
+    }
+  }
+}
+
+extern "C" int msml_occ_draw_mask(long seed, long offset, int N, int H, int W, int out_h, int out_w, int mode, int lo,
+                                  int hi, int flip, const int* meta, int nsets, float p_mask, int* desc, void* stream) {
+  MSML_CHECK(desc && N > 0 && H >= 32 && W >= 32 && out_h > 0 && out_w > 0 && mode >= 0 && mode <= 9 && lo >= 0 &&
+                 hi > lo && hi <= 101 && p_mask >= 0.f && p_mask <= 1.f, MSML_ERR_SHAPE,
+             "occ_draw_mask: bad arguments N=%d H=%d W=%d out=%dx%d mode=%d lo=%d hi=%d p_mask=%g", N, H, W, out_h, out_w,
+             mode, lo, hi, (double)p_mask);
+  MSML_CHECK(mode < 5 || (meta && nsets > 0 && nsets <= 16), MSML_ERR_SHAPE,
+             "occ_draw_mask: modes 5-9 need 1..16 occluder sets (got %d)", nsets);
+  MSML_CHECK(p_mask == 0.f || (out_h >= 111 && out_w >= 110), MSML_ERR_SHAPE,
+             "occ_draw_mask: the mask rectangle (up to x 110, y 111) does not fit an output of %dx%d", out_h, out_w);
+  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, mode < 5 ? nullptr : meta, mode < 5 ? 0 : nsets, desc, out_h, out_w, p_mask);
+  MSML_LAUNCH_OK("occ_draw_mask");
+  return MSML_OK;
+}
+
+extern "C" int msml_occ_apply_mask(const unsigned char* masked, const unsigned char* mask, const int* rows, int M,
+                                   const int* desc, const int* tabw, const int* tabh, float* img, long* msk, int N,
+                                   int H, int W, int out_h, int out_w, int gray, int norm, int light, void* stream) {
+  MSML_CHECK(masked && mask && desc && img && msk && N > 0 && M > 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0 &&
+                 H <= 4096 && W <= 4096 && out_h <= 4096 && out_w <= 4096 && (rows || M >= N),
+             MSML_ERR_SHAPE, "occ_apply_mask: bad arguments N=%d M=%d H=%d W=%d out=%dx%d", N, M, H, W, out_h, out_w);
+  MSML_CHECK((out_w == W || tabw) && (out_h == H || tabh), MSML_ERR_SHAPE,
+             "occ_apply_mask: %dx%d -> %dx%d needs the resampling table of every axis that changes", H, W, out_h, out_w);
+  MSML_CHECK(out_w % 4 == 0, MSML_ERR_UNSUPPORTED,
+             "occ_apply_mask: output width %d is not a multiple of 4 (16-byte stores)", out_w);
+  const OccMaskLds L = occ_mask_lds(H, W, out_h, out_w, gray ? 1 : 3);
+  MSML_CHECK(L.total <= 160 * 1024, MSML_ERR_UNSUPPORTED,
+             "occ_apply_mask: %dx%d -> %dx%d %s needs %ld bytes of LDS (163840 available)", H, W, out_h, out_w,
+             gray ? "gray" : "RGB", L.total);
+  static int attr_lds = 0;
+  if ((int)L.total > attr_lds) {                // (monotonic; racing callers set the same or a larger value)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_occ_apply_mask), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)L.total);
+    attr_lds = (int)L.total;
+  }
+  k_occ_apply_mask<<<N, OCC_OUT_T, (size_t)L.total, (hipStream_t)stream>>>(masked, mask, rows, M, desc, tabw, tabh, img, msk, H, W, out_h, out_w, gray, norm, light);
+  MSML_LAUNCH_OK("occ_apply_mask");
   return MSML_OK;
 }

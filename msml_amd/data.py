@@ -14,6 +14,11 @@ bottleneck: here the host only hands over decoded uint8 faces (37.6 KB per image
   use_norm switches (load_dataset.py:86-139,179; the LightCNN recipe, config.py:99-102): occlusion at the source size,
   convert('L'), bilinear Resize of face, mask and clean face, flip, light at the output size, no Normalize -- one
   kernel, bit for bit in the integer part (msml_occ_apply_out).
+* `p_mask=0.2` on `draw` / `augment` / `DeviceLoaderX` with `masked=`, `mask=` (and `rows=`) -- the facial-mask branch of
+  the mix (load_dataset.py:113,167-177 and _add_gauss_to_mask :203-280): flagged samples take the caller's rendered face
+  and mask plane through Resize, flip and light, binarise the mask at <= 128 and change the mask pixels by Gaussian
+  light, Gaussian noise or a block (msml_occ_draw_mask + the overlay msml_occ_apply_mask).  `mask_flags` is the same
+  draw on the host, for the record reader.  With p_mask = 0 (the default) nothing is launched that was not before.
 * `SynthFaceSource`                        -- stand-in for the record reader: a pool of random uint8 faces in
   pinned host memory (no dataset travels with this repo).
 """
@@ -192,16 +197,82 @@ def _out_table(insz, outsz, device):
     return _OUT_TABLES[key]
 
 
-def draw(n, seed, offset, mode="train", lo=0, hi=36, flip=True, size=112, device="cuda", atlas=None, out_size=None):
+_M64 = (1 << 64) - 1
+MASK_FLAG_DRAW = 46       # the draw index of the mask flag (csrc/occ.hip: 0-13 and 16-45 belong to the occluders)
+MASK_MIN_HW = (111, 110)  # the reference's rectangle (y < 111, x < 110) is in output pixels and is not scaled
+
+
+def _mix(z):
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def mask_flags(seed, offset, n, p_mask):
+    """Which of the images offset .. offset + n - 1 are facial-mask samples under `seed`: bool [n], the draw of
+    msml_occ_draw_mask on the host (occ_unif(occ_u32(seed, image, 46)) < p_mask in f32).  A record reader fetches the
+    mask_out / mask records of these indices only and builds `rows` from them."""
+    import numpy as np
+    out = np.zeros(n, bool)
+    if p_mask <= 0:
+        return out
+    base = _mix(int(seed) & _M64)
+    pm = np.float32(p_mask)
+    for i in range(n):
+        u = (_mix((base + (int(offset) + i) * 64 + MASK_FLAG_DRAW) & _M64) >> 32) & 0xFFFFFFFF
+        out[i] = np.float32(u >> 8) * np.float32(1.0 / 16777216.0) < pm
+    return out
+
+
+def _check_mask_args(p_mask, masked, mask, rows, n, h, w, oh, ow):
+    """The host-side refusals of the facial-mask branch, before any launch."""
+    if not 0.0 <= p_mask <= 1.0:
+        raise ValueError("p_mask = %r is not a probability" % (p_mask,))
+    if (masked is None) != (mask is None):
+        raise ValueError("masked and mask come together")
+    if p_mask > 0 and masked is None:
+        raise ValueError("p_mask > 0 needs the rendered faces (masked) and their masks (mask)")
+    if p_mask > 0 and (oh < MASK_MIN_HW[0] or ow < MASK_MIN_HW[1]):
+        raise ValueError("the facial-mask branch needs an output of at least %d x %d (got %d x %d): the reference's "
+                         "rectangle is not scaled with the size" % (MASK_MIN_HW + (oh, ow)))
+    if masked is None:
+        return
+    m = masked.shape[0]
+    if masked.dtype != torch.uint8 or tuple(masked.shape) != (m, h, w, 3):
+        raise ValueError("masked must be uint8 [M, %d, %d, 3], got %s %s" % (h, w, masked.dtype, tuple(masked.shape)))
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (m, h, w):
+        raise ValueError("mask must be uint8 [%d, %d, %d], got %s %s" % (m, h, w, mask.dtype, tuple(mask.shape)))
+    if rows is None:
+        if m != n:
+            raise ValueError("without rows, masked / mask hold one render per sample (%d), got %d" % (n, m))
+    elif rows.dtype != torch.int32 or tuple(rows.shape) != (n,):
+        raise ValueError("rows must be int32 [%d], got %s %s" % (n, rows.dtype, tuple(rows.shape)))
+
+
+def draw(n, seed, offset, mode="train", lo=0, hi=36, flip=True, size=112, device="cuda", atlas=None, out_size=None,
+         p_mask=0.0):
     """Per-image occlusion / flip / light descriptors (msml_occ_draw[_tex]), int32 [n, 64] on the device.  out_size:
-    the size the light is added at (msml_occ_draw_out: the light centre is uniform over the OUTPUT image)."""
+    the size the light is added at (msml_occ_draw_out: the light centre is uniform over the OUTPUT image).  p_mask > 0:
+    msml_occ_draw_mask -- an image is a facial-mask sample (kind 8) with that probability (the reference: 0.2)."""
+    if p_mask > 0:
+        oh, ow = _out_hw(out_size, size, size)
+        if p_mask > 1.0:
+            raise ValueError("p_mask = %r is not a probability" % (p_mask,))
+        if oh < MASK_MIN_HW[0] or ow < MASK_MIN_HW[1]:
+            raise ValueError("the facial-mask branch needs an output of at least %d x %d (got %d x %d)"
+                             % (MASK_MIN_HW + (oh, ow)))
     desc = torch.empty(n, DESC_WORDS, dtype=torch.int32, device=device)
     if MODES[mode] >= 5:
         if atlas is None:
             raise ValueError("mode %r needs an OccluderAtlas (texture occluders come from the caller's assets)" % mode)
         if atlas.size != size:
             raise ValueError("OccluderAtlas was built for %d-pixel images" % atlas.size)
-    if out_size is not None:
+    if p_mask > 0:
+        tex = MODES[mode] >= 5
+        call("msml_occ_draw_mask", int(seed), int(offset), n, size, size, oh, ow, MODES[mode], lo, hi, int(flip),
+             atlas.meta if tex else None, atlas.nsets if tex else 0, float(p_mask), desc)
+    elif out_size is not None:
         oh, ow = _out_hw(out_size, size, size)
         tex = MODES[mode] >= 5
         call("msml_occ_draw_out", int(seed), int(offset), n, size, size, oh, ow, MODES[mode], lo, hi, int(flip),
@@ -214,15 +285,24 @@ def draw(n, seed, offset, mode="train", lo=0, hi=36, flip=True, size=112, device
     return desc
 
 
-def apply(src, desc, light=True, want_ori=True, atlas=None, gray=False, out_size=None, use_norm=True):
+def apply(src, desc, light=True, want_ori=True, atlas=None, gray=False, out_size=None, use_norm=True, masked=None,
+          mask=None, rows=None):
     """src: (N, H, W, 3) uint8 on the device -> img (N,3,H,W) f32, msk (N,H,W) int64, ori or None.  atlas: the
     OccluderAtlas the descriptors were drawn with (texture kinds are resampled per sample, then pasted).
     gray / out_size / use_norm: the reference's is_gray / out_size / use_norm (msml_occ_apply_out) -- img and ori
-    (N, 1 or 3, oh, ow), in [0, 1] without the normalisation, msk (N, oh, ow); desc drawn with the same out_size."""
+    (N, 1 or 3, oh, ow), in [0, 1] without the normalisation, msk (N, oh, ow); desc drawn with the same out_size.
+    masked (M, H, W, 3) uint8, mask (M, H, W) uint8 (any gray value; <= 128 after the resize is the mask), rows int32
+    (N) or None (M == N): the renders of the facial-mask samples (kind 8 of draw(..., p_mask=...)); sample n takes row
+    rows[n], and a row outside 0 .. M - 1 leaves it the clean sample (msml_occ_apply_mask, an overlay on img and msk)."""
     n, h, w, c = src.shape
     assert c == 3 and src.dtype == torch.uint8 and src.is_cuda and src.is_contiguous()
-    if gray or out_size is not None or not use_norm:
-        oh, ow = _out_hw(out_size, h, w)
+    oh, ow = _out_hw(out_size, h, w)
+    if masked is not None or mask is not None:
+        _check_mask_args(1.0, masked, mask, rows, n, h, w, oh, ow)      # (the overlay may run: the size check applies)
+        assert masked.is_cuda and mask.is_cuda and masked.is_contiguous() and mask.is_contiguous()
+        assert rows is None or (rows.is_cuda and rows.is_contiguous())
+    out_form = gray or out_size is not None or not use_norm
+    if out_form:
         ch = 1 if gray else 3
         img = torch.empty(n, ch, oh, ow, dtype=torch.float32, device=src.device)
         ori = torch.empty(n, ch, oh, ow, dtype=torch.float32, device=src.device) if want_ori else None
@@ -234,40 +314,70 @@ def apply(src, desc, light=True, want_ori=True, atlas=None, gray=False, out_size
                  atlas.lds_bytes)
         call("msml_occ_apply_out", src, desc, patch, stride, _out_table(w, ow, src.device),
              _out_table(h, oh, src.device), img, msk, ori, n, h, w, oh, ow, int(gray), int(use_norm), int(light))
-        return img, msk, ori
-    img = torch.empty(n, 3, h, w, dtype=torch.float32, device=src.device)
-    ori = torch.empty(n, 3, h, w, dtype=torch.float32, device=src.device) if want_ori else None
-    msk = torch.empty(n, h, w, dtype=torch.int64, device=src.device)
-    if atlas is not None:
-        patch = torch.empty(n, atlas.patch_bytes, dtype=torch.uint8, device=src.device)
-        call("msml_occ_resize", atlas.atlas, atlas.meta, atlas.dir, atlas.rtab, desc, patch, atlas.patch_bytes, n,
-             atlas.lds_bytes)
-        call("msml_occ_apply_tex", src, desc, patch, atlas.patch_bytes, img, msk, ori, n, h, w, int(light))
     else:
-        call("msml_occ_apply", src, desc, img, msk, ori, n, h, w, int(light))
+        img = torch.empty(n, 3, h, w, dtype=torch.float32, device=src.device)
+        ori = torch.empty(n, 3, h, w, dtype=torch.float32, device=src.device) if want_ori else None
+        msk = torch.empty(n, h, w, dtype=torch.int64, device=src.device)
+        if atlas is not None:
+            patch = torch.empty(n, atlas.patch_bytes, dtype=torch.uint8, device=src.device)
+            call("msml_occ_resize", atlas.atlas, atlas.meta, atlas.dir, atlas.rtab, desc, patch, atlas.patch_bytes, n,
+                 atlas.lds_bytes)
+            call("msml_occ_apply_tex", src, desc, patch, atlas.patch_bytes, img, msk, ori, n, h, w, int(light))
+        else:
+            call("msml_occ_apply", src, desc, img, msk, ori, n, h, w, int(light))
+    if masked is not None:
+        call("msml_occ_apply_mask", masked, mask, rows, masked.shape[0], desc, _out_table(w, ow, src.device),
+             _out_table(h, oh, src.device), img, msk, n, h, w, oh, ow, int(gray), int(use_norm), int(light))
     return img, msk, ori
 
 
 def augment(src, seed, offset, mode="train", lo=0, hi=36, flip=True, light=True, want_ori=True, atlas=None, gray=False,
-            out_size=None, use_norm=True):
-    desc = draw(src.shape[0], seed, offset, mode, lo, hi, flip, src.shape[1], src.device, atlas, out_size)
-    return apply(src, desc, light, want_ori, atlas if MODES[mode] >= 5 else None, gray, out_size, use_norm) + (desc,)
+            out_size=None, use_norm=True, p_mask=0.0, masked=None, mask=None, rows=None):
+    """draw + apply.  p_mask > 0 needs masked / mask (and takes rows); with p_mask = 0 they are not looked at and the
+    launches are those of a call without them."""
+    n, h, w, _ = src.shape
+    _check_mask_args(p_mask, masked, mask, rows, n, h, w, *_out_hw(out_size, h, w))
+    if p_mask <= 0:
+        masked = mask = rows = None
+    desc = draw(n, seed, offset, mode, lo, hi, flip, h, src.device, atlas, out_size, p_mask)
+    return apply(src, desc, light, want_ori, atlas if MODES[mode] >= 5 else None, gray, out_size, use_norm, masked, mask,
+                 rows) + (desc,)
 
 
 class SynthFaceSource:
     """Endless host-side source of (uint8 faces [B,112,112,3] in pinned memory, int64 labels [B]): `pool`
-    distinct batches are generated once and cycled, as a record reader with a warm page cache would."""
+    distinct batches are generated once and cycled, as a record reader with a warm page cache would.
+    masks=True: (faces, masked, mask, labels) -- stand-ins for the mask_out / mask records of every face: the lower face
+    recoloured in one colour per sample, and a mask plane that is 0 there and 255 on the face with a three-pixel ramp
+    between them, so that values on both sides of 128 meet the binarisation."""
 
-    def __init__(self, batch, num_classes, steps=None, pool=4, seed=1, size=112):
+    def __init__(self, batch, num_classes, steps=None, pool=4, seed=1, size=112, masks=False):
         self.batch, self.steps = batch, steps
         self.pool = []
         for i in range(pool):
             g = torch.Generator().manual_seed(seed + 977 * i)
             faces = torch.randint(0, 256, (batch, size, size, 3), generator=g, dtype=torch.uint8)
             labels = torch.randint(0, num_classes, (batch,), generator=g)
+            item = (faces, labels)
+            if masks:
+                item = (faces,) + self._renders(faces, g) + (labels,)
             if torch.cuda.is_available():
-                faces, labels = faces.pin_memory(), labels.pin_memory()
-            self.pool.append((faces, labels))
+                item = tuple(t.pin_memory() for t in item)
+            self.pool.append(item)
+
+    @staticmethod
+    def _renders(faces, g):
+        b, size = faces.shape[0], faces.shape[1]
+        top = torch.randint(size // 2, size // 2 + size // 8, (b, 1, 1), generator=g).float()
+        left = torch.randint(size // 6, size // 4, (b, 1, 1), generator=g).float()
+        y = torch.arange(size).float().view(1, size, 1)
+        x = torch.arange(size).float().view(1, 1, size)
+        depth = torch.minimum(torch.minimum(y - top, (size - 6.0) - y), torch.minimum(x - left, (size - left) - x))
+        alpha = (depth / 3.0).clamp(0.0, 1.0)                                  # 0 on the face, 1 well inside the mask
+        colour = torch.randint(0, 256, (b, 1, 1, 3), generator=g).float()
+        masked = (faces.float() * (1.0 - alpha[..., None]) + colour * alpha[..., None]).round().to(torch.uint8)
+        mask = (255.0 * (1.0 - alpha)).round().to(torch.uint8)
+        return masked.contiguous(), mask.contiguous()
 
     def __iter__(self):
         i = 0
@@ -305,15 +415,20 @@ class DeviceLoaderX:
     Batch k+1 is copied (non_blocking, pinned -> HBM) and augmented on `self.stream` while the caller
     trains on batch k; `__next__` first makes the current stream wait for `self.stream`
     (dataloaderx.py:60-66).  The random draws of batch k are keyed by (seed, k * batch + image index):
-    reproducible whatever the timing."""
+    reproducible whatever the timing.
+
+    p_mask > 0 (the reference: 0.2): the source yields (faces, masked, mask, label) or (faces, masked, mask, rows, label)
+    -- the renders of the facial-mask samples, one per face or packed with rows[n] the render of face n (-1: none; see
+    mask_flags) -- and they go over on the side stream with the faces."""
 
     def __init__(self, source, local_rank=0, seed=1, mode="train", lo=0, hi=36, flip=True, light=True,
-                 want_ori=True, max_prefetch=6, atlas=None, gray=False, out_size=None, use_norm=True):
+                 want_ori=True, max_prefetch=6, atlas=None, gray=False, out_size=None, use_norm=True, p_mask=0.0):
         self.source, self.local_rank = source, local_rank
         self.stream = torch.cuda.Stream(local_rank)
         self.atlas = atlas                   # OccluderAtlas for the "ms1m" / "casia" mixes (texture occluders)
         self.cfg = (seed, mode, lo, hi, flip, light, want_ori)
         self.out = (gray, out_size, use_norm)   # the reference's is_gray / out_size / use_norm (LightCNN: True, 128, False)
+        self.p_mask = p_mask
         self.max_prefetch = max_prefetch
         self.count = 0
         self.batch = None
@@ -332,13 +447,18 @@ class DeviceLoaderX:
             return
         seed, mode, lo, hi, flip, light, want_ori = self.cfg
         faces, label = host[0], host[-1]
+        if self.p_mask > 0 and len(host) not in (4, 5):
+            raise ValueError("p_mask > 0: the source must yield (faces, masked, mask[, rows], label)")
         with torch.cuda.stream(self.stream):
             src = faces.to(device=self.local_rank, non_blocking=True)
             lab = label.to(device=self.local_rank, non_blocking=True)
+            extra = ()
+            if self.p_mask > 0:                  # masked, mask and, when the renders are packed, rows
+                extra = tuple(t.to(device=self.local_rank, non_blocking=True) for t in host[1:-1])
             img, msk, ori, _ = augment(src, seed, self.count * faces.shape[0], mode, lo, hi, flip, light, want_ori,
-                                       self.atlas, *self.out)
+                                       self.atlas, *self.out, self.p_mask, *extra)
         self.count += 1
-        self.batch = (img, msk, ori, lab, src)
+        self.batch = (img, msk, ori, lab, src) + extra
 
     def __next__(self):
         cur = torch.cuda.current_stream()
@@ -350,5 +470,4 @@ class DeviceLoaderX:
             if t is not None:
                 t.record_stream(cur)
         self.preload()
-        img, msk, ori, lab, _ = batch
-        return img, msk, ori, lab
+        return batch[:4]
