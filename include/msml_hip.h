@@ -40,7 +40,8 @@ enum {
   MSML_ERR_DTYPE = -2,       /* unsupported dtype enum */
   MSML_ERR_LAUNCH = -3,      /* hipGetLastError() after launch */
   MSML_ERR_UNSUPPORTED = -4, /* valid request this build has no kernel for */
-  MSML_ERR_WORKSPACE = -5    /* workspace too small */
+  MSML_ERR_WORKSPACE = -5,   /* workspace too small */
+  MSML_ERR_CAPACITY = -6     /* more candidates than a fixed capacity holds (msml_det_nms) */
 };
 
 /* FM operator enums: backbones/fm/fmoperator.py:110-126 */
@@ -847,6 +848,67 @@ int msml_allpairs_pass(const void* probe, long P, const int* probe_code, const v
                        const unsigned long long* range_prefix, const int* range_bits, int bins_log2,
                        unsigned long long* hist, void* cand, unsigned long long* cand_count, long cand_cap,
                        const double* thresholds, int n_thr, unsigned long long* counts, int splits, void* stream);
+
+/* ---------------------------------------------------------------- face detection: MTCNN --------------------------
+ * The steps of MTCNN.detect_faces (eval/preprocess/mtcnn.py:160-274 with mtcnn_pytorch/src/first_stage.py, box_utils.py
+ * and get_nets.py) between the packed uint8 sources of msml_align_warp (src, meta [N][4] = byte offset, H, W, pitch) and
+ * the final boxes and landmarks; msml_amd/detect.py chains them.  A candidate is a ROW of 16 doubles:
+ *   x1 y1 x2 y2 score | image | box offsets [4] (stages 1, 2) or landmarks x0..x4 y0..y4 [10] (stage 3).
+ * All box arithmetic is f64 without contraction, in the reference's order of operations; the three nets are f32 FMA.
+ *
+ * msml_det_resample: jobs [njobs][8] (long, on the device) = image, x0, y0, w, h, out_w, out_h, output offset in floats.
+ *   PIL Image.resize((out_w, out_h), BILINEAR) of the w x h window at (x0, y0) of the image, pixels outside the image
+ *   black, bit for bit (Resample.c: triangle filter, support max(scale, 1), coefficients normalised in f64 and rounded
+ *   to 22 bits, computed in the kernel; horizontal pass, clip, vertical pass, clip), then (x - 127.5) * 0.0078125 in
+ *   f32, planar [3][out_h][out_w] at out + offset.  A job with w < 1 or h < 1 gives a black crop.  max_out_px: the
+ *   largest out_w * out_h of the jobs (the launch grid).
+ * msml_det_pnet: levels [L][6] (long) = input offset in floats, H, W, output offset in floats, oh, ow with
+ *   oh = (H - 1) / 2 - 4; tiles [ntiles][3] (int) = level, tile row, tile column of msml_det_pnet_tile() square output
+ *   tiles.  in: planar levels as msml_det_resample writes them; params: msml_det_pnet_params() floats, conv1 w b a,
+ *   conv2 w b a, conv3 w b a, heads w [6][32] b [6] (conv4_1 then conv4_2).  out: planar [6][oh][ow] per level, the two
+ *   class LOGITS then the four box offsets.  One fused launch, intermediates in LDS.
+ * msml_det_candidates: rowtab [nrows][2] (int) = level, map row; scales [L] f64; images [L] (long).  The reference's
+ *   softmax over the WIDTH of the class map (F.softmax(dim=-1) on [1][2][h][w]), channel 1 > threshold in f32.
+ *   write = 0: counts [nrows] (long); write = 1: the candidates' rows at offsets [nrows] (the exclusive sum of counts),
+ *   x ascending: np.where's order.  Boxes round((2 i + 1) / s), round((2 i + 13) / s), half to even.
+ * msml_det_nms: box_utils.nms on every segment [seg_off[s], seg_off[s + 1]) of rows: descending score, among equal
+ *   scores the HIGHER index first (np.argsort read from the end), overlap inter / (a + b - inter) or, mode_min = 1,
+ *   inter / min(a, b), areas with the reference's + 1.0.  valid (may be NULL): rows with 0 take no part.  keep [n] (int)
+ *   receives the picked global row indices of a segment in pick order at seg_off[s], -1 behind them; keep_cnt [nseg].
+ *   order [n] (int) is scratch.  max_n: the longest segment, known to the caller from the stage's one count copy;
+ *   max_n > capacity returns MSML_ERR_CAPACITY before any launch (capacity <= msml_det_nms_capacity()).
+ * msml_det_compact: out[new_off[s] + k] = rows[keep[seg_off[s] + k]], k < keep_cnt[s].
+ * msml_det_refine: calibrate_box with the row's offsets, convert_to_square (score := 0), np.round, correct_bboxes.
+ *   jobs [n][8] receive the crop windows (the unclipped rounded box) for msml_det_resample at size x size; the row
+ *   keeps the box CLIPPED to the image, which is what the reference's in-place views leave behind.  valid[i] = 0 and a
+ *   black crop for a box with no pixel inside the image (the reference raises there), with a side of 32768 pixels or
+ *   more, or with a coordinate that is not finite.
+ * msml_det_net: net 0 = R-Net on [n][3][24][24], net 1 = O-Net on [n][3][48][48] -> out [n][16] = class logits,
+ *   offsets [4], landmarks [10] (O-Net).  params: msml_det_net_params(net) floats in layer order, conv w b a, the FC
+ *   weight as [In][Out] with Flatten's transpose(3, 2) folded in, heads as [In][16].  ws: msml_det_net_workspace bytes.
+ * msml_det_select: valid[i] &= softmax(logits)[1] > threshold (f32); the row's score := that probability.
+ *   landmarks = 0: offsets into the row; 1: landmarks xmin + width * l (f64, rounded to f32) then calibrate_box. */
+int msml_det_pnet_tile(void);
+int msml_det_pnet_params(void);
+int msml_det_nms_capacity(void);
+long msml_det_net_params(int net);
+long msml_det_net_workspace(int net, long n);
+int msml_det_resample(const unsigned char* src, const long* meta, const long* jobs, float* out, long njobs,
+                      long max_out_px, void* stream);
+int msml_det_pnet(const float* in, const long* levels, const int* tiles, const float* params, float* out, long ntiles,
+                  void* stream);
+int msml_det_candidates(const float* maps, const long* levels, const double* scales, const long* images,
+                        const int* rowtab, long nrows, float threshold, int write, long* counts, const long* offsets,
+                        double* rows, void* stream);
+int msml_det_nms(const double* rows, const long* seg_off, const unsigned char* valid, long nseg, long max_n,
+                 long capacity, double threshold, int mode_min, int* order, int* keep, int* keep_cnt, void* stream);
+int msml_det_compact(const double* rows, const int* keep, const long* seg_off, const int* keep_cnt,
+                     const long* new_off, double* out, long nseg, void* stream);
+int msml_det_refine(double* rows, const long* meta, long n, int size, long* jobs, unsigned char* valid, void* stream);
+int msml_det_net(int net, const float* in, const float* params, long n, float* ws, long ws_bytes, float* out,
+                 void* stream);
+int msml_det_select(double* rows, const float* net, long n, float threshold, int landmarks, unsigned char* valid,
+                    void* stream);
 
 #ifdef __cplusplus
 }
