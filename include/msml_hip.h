@@ -910,6 +910,38 @@ int msml_det_net(int net, const float* in, const float* params, long n, float* w
 int msml_det_select(double* rows, const float* net, long n, float threshold, int landmarks, unsigned char* valid,
                     void* stream);
 
+/* ---------------------------------------------------------------- whole-photo uint8 operations ------------------
+ * The oriented and resized copies MTCNN.align_fully and MTCNN.get_landmarks make of a photo before they detect
+ * (eval/preprocess/mtcnn.py:41-158), for N packed images of any sizes in one call (msml_amd/mtcnn_align.py).  Source and
+ * destination are packed as msml_align_warp takes its sources: meta [N][4] int64 = {byte offset, H, W, row pitch}, 3
+ * bytes per pixel; the CALLER checks that every image lies inside its buffer.  In meta_out every offset and pitch is a
+ * multiple of 4; the bytes between 3 W and the pitch are written as 0.  Integer arithmetic, no atomics, one writer per
+ * output dword, dword stores only: two runs give the same bits.
+ *
+ * msml_img_orient: PIL Image.transpose(method), method[n] (int, on the device) = 0 FLIP_LEFT_RIGHT, 1 FLIP_TOP_BOTTOM,
+ *   2 ROTATE_90, 3 ROTATE_180, 4 ROTATE_270; meta_out holds W x H images for 2 and 4.  src_bytes: the length of src (the
+ *   source is read as aligned dwords, never past src_bytes).  plan [N][3] (long, on the HOST) = method, out_h, out_w,
+ *   which the library checks: MSML_ERR_UNSUPPORTED before the launch for N < 1 or N > 65535, a method outside 0..4 and
+ *   a size outside 1..32767; MSML_ERR_SHAPE for a null pointer and for src, dst, method not 4-byte or meta, meta_out not
+ *   8-byte aligned.
+ * msml_img_resize: PIL Image.resize((out_w, out_h), filter) on 3-channel uint8, filter 2 = BILINEAR, 3 = BICUBIC
+ *   (a = -0.5): ImagingResample's two passes, horizontal then vertical on the rounded uint8 intermediate, each
+ *   accumulator started at 2^21, shifted right by 22 and clipped to 0..255.  tables (int, device): per axis and per
+ *   output position a row {first tap, taps, coefficients [ksize]} in 22-bit fixed point, built on the host in double
+ *   (mtcnn_align.resample_rows, with the filter named here); jobs [N][5] (long, device) = offset of the horizontal table
+ *   in ints, its ksize, offset of the vertical table, its ksize, byte offset of the image's intermediate in ws.  An axis
+ *   of equal length takes the identity table (one tap of 2^22), which copies.  sizes [N][4] (long, HOST) = in_h, in_w,
+ *   out_h, out_w.  ws: msml_img_resize_workspace(sizes, N) bytes, the intermediates [in_h][pitch of out_w] back to back
+ *   (0 for a size outside 1..32767).  MSML_ERR_UNSUPPORTED before any launch for N < 1 or N > 65535, another filter,
+ *   a size outside 1..32767; MSML_ERR_SHAPE for null or misaligned pointers (dst, ws, tables 4 bytes, meta, meta_out,
+ *   jobs 8); MSML_ERR_WORKSPACE for a workspace that is too small. */
+int msml_img_orient(const unsigned char* src, long src_bytes, const long* meta, const int* method, unsigned char* dst,
+                    const long* meta_out, const long* plan, int N, void* stream);
+long msml_img_resize_workspace(const long* sizes, int N);
+int msml_img_resize(const unsigned char* src, const long* meta, unsigned char* dst, const long* meta_out,
+                    const int* tables, const long* jobs, const long* sizes, int N, int filter, unsigned char* ws,
+                    long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,7 +216,7 @@ class Detector:
         get_image_boxes raises on such a box, here it leaves the list -- or a side of 32 768 pixels or more (the reference
         would try to allocate that cut).  max_candidates: the PER-IMAGE capacity for P-Net
         candidates (default and upper limit: msml_det_nms_capacity()); an image with more raises CapacityError, however
-        many the batch holds in all."""
+        many the batch holds in all.  min_face_size: one number, or one per image ([B])."""
         from . import ijb
         if isinstance(images, tuple) and len(images) == 2 and isinstance(images[0], torch.Tensor):
             buf, meta = images
@@ -229,9 +229,18 @@ class Detector:
         empty = Detections([np.zeros((0, 5)) for _ in range(B)], [np.zeros((0, 10), np.float32) for _ in range(B)], 0)
 
         # the pyramid: one job and one P-Net level per (image, scale); the tables are built per DISTINCT image size
-        sizes, which = np.unique(meta[:, 1:3], axis=0, return_inverse=True)
+        if np.ndim(min_face_size) == 0:
+            sizes, which = np.unique(meta[:, 1:3], axis=0, return_inverse=True)
+            per_size = [pyramid_scales(int(h), int(w), min_face_size, factor) for h, w in sizes]
+        else:                                                                  # one min_face_size per image
+            mfs = np.asarray(min_face_size, np.float64).reshape(-1)
+            if mfs.shape[0] != B or not (np.isfinite(mfs) & (mfs > 0)).all():
+                raise ValueError("detect_faces: min_face_size must be one positive number, or one per image")
+            keys, which = np.unique(np.concatenate([meta[:, 1:3].astype(np.float64), mfs[:, None]], 1), axis=0,
+                                    return_inverse=True)
+            sizes = keys[:, 0:2].astype(np.int64)
+            per_size = [pyramid_scales(int(h), int(w), float(m), factor) for h, w, m in keys]
         which = which.reshape(-1)
-        per_size = [pyramid_scales(int(h), int(w), min_face_size, factor) for h, w in sizes]
         size_levels = np.array([len(p) for p in per_size], np.int64)
         if size_levels.sum() == 0:
             return empty
@@ -335,7 +344,7 @@ def detect_and_embed(model, images, detector, min_face_size=64.0, thresholds=(0.
     """Photo in, embedding out: detect_faces, first_landmarks, then ijb.align_and_embed (align_matrices, align_faces, the
     eval input pairs, the model) for the images in which a face was found.  images: cv2.imread results (BGR), as
     ijb.align_and_embed takes them; the detector sees their RGB view.  The alignment is the project's Umeyama estimate of
-    ijb.align_matrices, not the reference's cp2tform / warp_and_crop_face.  Returns (feats [F][2E] f32 on the device, one
+    ijb.align_matrices, not the reference's cp2tform / warp_and_crop_face (those: mtcnn_align.align_and_embed).  Returns (feats [F][2E] f32 on the device, one
     row per found image in order; found [B] bool; Detections).  embed: align_and_embed's batch, lo, hi, seed, out_size."""
     from . import ijb
     det = detector.detect_faces([im[:, :, ::-1] for im in images], min_face_size, thresholds, nms_thresholds, factor)

@@ -207,6 +207,47 @@ PROTOCOLS = {"BB": 0, "NB": 1}                      # _load_one_input's protocol
 LEVELS = tuple((lo, lo + 1) for lo in range(0, 100, 10))      # lo_list / hi_list of qeval_mxnet.py:528-529
 
 
+def pairs_file_order(files_by_identity):
+    """The flat order read_pairs_txt indexes: identities sorted, the files of each sorted (qeval_folder.py:43-49 sorts
+    the files; the identity order is this function's): [(identity, file)]."""
+    return [(ident, f) for ident in sorted(files_by_identity) for f in sorted(files_by_identity[ident])]
+
+
+def read_pairs_txt(lines, files_by_identity):
+    """The pair list of eval/qeval_folder.py:52-73 (MFR2 / RMFRD pairs.txt) without its file I/O.  lines: the lines of the
+    file; files_by_identity: {identity: [file names]}.  A line of 3 words `name i j` is a SAME pair of one identity, a
+    line of 4 words `name1 i name2 j` a DIFFERENT pair; i, j count from 1 into the SORTED file list of the identity.
+    Returns (pairs int64 [P][2], rows of pairs_file_order(files_by_identity); issame bool [P]).  ValueError naming the
+    line for another word count, an unknown identity or an index outside the identity's list."""
+    first, n = {}, 0
+    for ident in sorted(files_by_identity):
+        first[ident] = (n, len(files_by_identity[ident]))
+        n += len(files_by_identity[ident])
+    pairs, issame = [], []
+    for k, line in enumerate(lines):
+        words = line.strip().split(" ")
+        if len(words) == 3:
+            names, idx = (words[0], words[0]), (words[1], words[2])
+        elif len(words) == 4:
+            names, idx = (words[0], words[2]), (words[1], words[3])
+        else:
+            raise ValueError("read_pairs_txt: line %d has %d words, not 3 or 4" % (k, len(words)))
+        row = []
+        for name, i in zip(names, idx):
+            if name not in first:
+                raise ValueError("read_pairs_txt: line %d names the unknown identity %r" % (k, name))
+            try:
+                i = int(i)
+            except ValueError:
+                raise ValueError("read_pairs_txt: line %d: %r is not an index" % (k, i)) from None
+            if not 1 <= i <= first[name][1]:
+                raise ValueError("read_pairs_txt: line %d: index %d outside 1..%d of %r" % (k, i, first[name][1], name))
+            row.append(first[name][0] + i - 1)
+        pairs.append(row)
+        issame.append(len(words) == 3)
+    return np.array(pairs, np.int64).reshape(-1, 2), np.array(issame, bool)
+
+
 def _no_block(lo, hi):
     return (lo is None and hi is None) or (lo == 0 and hi == 1)
 
