@@ -367,6 +367,17 @@ __global__ void __launch_bounds__(256) k_occ_resize(const unsigned char* __restr
   }
 }
 
+// _get_gauss at pixel (x, y) of the image the light is added to: integer-truncated offsets (astype(int16)), Euclidean
+// distance, sigma 128, float16 map
+__device__ __forceinline__ float occ_lightmap(int x, int y, float lcx, float lcy, float lscale) {
+  const int ix = (int)((float)x - lcx), iy = (int)((float)y - lcy);
+  const float dist = sqrtf((float)(ix * ix + iy * iy));
+  const float g = expf(-0.5f * (dist * dist) / 16384.0f);
+  const __half g16 = __float2half(g);
+  const __half l16 = __float2half(__half2float(g16) * __half2float(__float2half(lscale)));
+  return __half2float(l16);
+}
+
 __global__ void __launch_bounds__(256) k_occ_apply(const unsigned char* __restrict__ src, const int* __restrict__ desc,
                                                    float* __restrict__ img, long* __restrict__ msk,
                                                    float* __restrict__ ori, int H, int W, int light,
@@ -381,15 +392,6 @@ __global__ void __launch_bounds__(256) k_occ_apply(const unsigned char* __restri
   float* o = img + (long)n * 3 * HW;
   const bool flip = d[8] != 0;
   const float lcx = __int_as_float(d[9]), lcy = __int_as_float(d[10]), lscale = __int_as_float(d[11]);
-  auto lightmap = [&](int x, int y) -> float {
-    // _get_gauss: integer-truncated offsets (astype(int16)), Euclidean distance, sigma 128, float16 map
-    const int ix = (int)((float)x - lcx), iy = (int)((float)y - lcy);
-    const float dist = sqrtf((float)(ix * ix + iy * iy));
-    const float g = expf(-0.5f * (dist * dist) / 16384.0f);
-    const __half g16 = __float2half(g);
-    const __half l16 = __float2half(__half2float(g16) * __half2float(__float2half(lscale)));
-    return __half2float(l16);
-  };
   float vmax = 0.f;
   for (int p = t; p < HW; p += 256) {
     const int y = p / W, x = p - y * W;
@@ -410,7 +412,7 @@ __global__ void __launch_bounds__(256) k_occ_apply(const unsigned char* __restri
       }
     }
     msk[(long)n * HW + p] = in ? 0 : 1;
-    const float l = light ? lightmap(x, y) : 1.f;
+    const float l = light ? occ_lightmap(x, y, lcx, lcy, lscale) : 1.f;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
       const float clean = (float)q[c] / 255.0f;                       // ToTensor
@@ -437,13 +439,19 @@ __global__ void __launch_bounds__(256) k_occ_apply(const unsigned char* __restri
   }
 }
 
+// the k_occ_draw launch of the four draw entry points (LH x LW: the size the light is added at)
+static int occ_draw_launch(const char* name, long seed, long offset, int N, int H, int W, int mode, int lo, int hi,
+                           int flip, const int* meta, int nsets, int* desc, int LH, int LW, float p_mask, void* stream) {
+  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, meta, nsets, desc, LH, LW, p_mask);
+  MSML_LAUNCH_OK(name);
+  return MSML_OK;
+}
+
 extern "C" int msml_occ_draw(long seed, long offset, int N, int H, int W, int mode, int lo, int hi,
                              int flip, int* desc, void* stream) {
   MSML_CHECK(desc && N > 0 && H >= 32 && W >= 32 && mode >= 0 && mode <= 4 && lo >= 0 && hi > lo && hi <= 101,
              MSML_ERR_SHAPE, "occ_draw: bad arguments N=%d H=%d W=%d mode=%d lo=%d hi=%d", N, H, W, mode, lo, hi);
-  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, nullptr, 0, desc, H, W, 0.f);
-  MSML_LAUNCH_OK("occ_draw");
-  return MSML_OK;
+  return occ_draw_launch("occ_draw", seed, offset, N, H, W, mode, lo, hi, flip, nullptr, 0, desc, H, W, 0.f, stream);
 }
 
 extern "C" int msml_occ_draw_tex(long seed, long offset, int N, int H, int W, int mode, int lo, int hi, int flip,
@@ -452,9 +460,7 @@ extern "C" int msml_occ_draw_tex(long seed, long offset, int N, int H, int W, in
              MSML_ERR_SHAPE, "occ_draw_tex: bad arguments N=%d H=%d W=%d mode=%d lo=%d hi=%d", N, H, W, mode, lo, hi);
   MSML_CHECK(mode < 5 || (meta && nsets > 0 && nsets <= 16), MSML_ERR_SHAPE,
              "occ_draw_tex: modes 5-9 need 1..16 occluder sets (got %d)", nsets);
-  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, meta, nsets, desc, H, W, 0.f);
-  MSML_LAUNCH_OK("occ_draw_tex");
-  return MSML_OK;
+  return occ_draw_launch("occ_draw_tex", seed, offset, N, H, W, mode, lo, hi, flip, meta, nsets, desc, H, W, 0.f, stream);
 }
 
 extern "C" int msml_occ_resize(const unsigned char* atlas, const int* meta, const int* dir, const int* rtab,
@@ -510,12 +516,14 @@ extern "C" int msml_occ_apply_tex(const unsigned char* src, const int* desc, con
 // 136 960 B at 112 -> 128 RGB, 104 192 B gray.  Every global store is 16 B per lane (float4 / two int64); needs ow % 4 == 0.
 #define OCC_OUT_T 1024
 #define OCC_OUT_HDR 512          // desc[64] int32 + the 16 per-wave maxima
-struct OccOutLds {
-  long tabw, tabh, raw, mk, s, bh, o, total;
+// The one LDS layout of k_occ_apply_out (mb = false) and of the mask overlay k_occ_apply_mask below (mb = true: plus
+// MB [oh][ow], the binarised mask its last pass reads), for the host and for both kernels.
+struct OccLds {
+  long tabw, tabh, raw, mk, s, bh, o, mb, total;
 };
-__host__ __device__ inline long occ_r16(long b) { return (b + 15) & ~15L; }
-__host__ __device__ inline OccOutLds occ_out_lds(int H, int W, int oh, int ow, int C) {
-  OccOutLds L;
+__host__ __device__ constexpr long occ_r16(long b) { return (b + 15) & ~15L; }
+__host__ __device__ constexpr OccLds occ_lds(int H, int W, int oh, int ow, int C, bool mb) {
+  OccLds L{};
   long off = OCC_OUT_HDR;
   L.tabw = off; off += ow != W ? occ_r16((long)ow * OCC_RT * 4) : 0;
   L.tabh = off; off += oh != H ? occ_r16((long)oh * OCC_RT * 4) : 0;
@@ -524,11 +532,110 @@ __host__ __device__ inline OccOutLds occ_out_lds(int H, int W, int oh, int ow, i
   L.s = off;    off += occ_r16((long)H * W);
   L.bh = off;   off += ow != W ? occ_r16((long)H * ow) : 0;
   L.o = off;    off += occ_r16((long)C * oh * ow);
+  L.mb = off;   off += mb ? occ_r16((long)oh * ow) : 0;
   L.total = off;
   return L;
 }
+// the byte counts docs/KERNELS.md states: source -> output (oh, ow), channels
+static_assert(occ_lds(112, 112, 128, 128, 1, false).total == 104192 && occ_lds(112, 112, 128, 128, 3, false).total == 136960 &&
+              occ_lds(112, 112, 96, 96, 1, false).total == 90880 && occ_lds(112, 112, 112, 96, 3, false).total == 110080 &&
+              occ_lds(112, 112, 144, 144, 3, false).total == 153088 && occ_lds(112, 112, 224, 224, 1, false).total == 156416 &&
+              occ_lds(112, 112, 224, 224, 3, false).total == 256768, "k_occ_apply_out: LDS bytes");
+static_assert(occ_lds(112, 112, 128, 128, 3, true).total == 153344 && occ_lds(112, 112, 128, 128, 1, true).total == 120576 &&
+              occ_lds(112, 112, 112, 112, 3, true).total == 113408, "k_occ_apply_mask: LDS bytes");
 __device__ __forceinline__ unsigned int occ_luma(unsigned int r, unsigned int g, unsigned int b) {
   return (19595u * r + 38470u * g + 7471u * b + 0x8000u) >> 16;          // Pillow Convert.c L24 + rounding
+}
+
+// ---- what k_occ_apply_out and k_occ_apply_mask share.  None of these holds a barrier: the kernels place them.
+// The descriptor of image n (to the head of the LDS) and the coefficient tables of the axes that change (has_w, has_h)
+// -> LDS.
+__device__ __forceinline__ void occ_stage_tables(unsigned char* sm, const OccLds& L, bool has_w, bool has_h,
+                                                 const int* __restrict__ desc, const int* __restrict__ tabw,
+                                                 const int* __restrict__ tabh, int n, int oh, int ow, int t) {
+  if (t < OCC_DESC) reinterpret_cast<int*>(sm)[t] = desc[n * OCC_DESC + t];
+  if (has_w) for (int i = t; i < ow * OCC_RT; i += OCC_OUT_T) reinterpret_cast<int*>(sm + L.tabw)[i] = tabw[i];
+  if (has_h) for (int i = t; i < oh * OCC_RT; i += OCC_OUT_T) reinterpret_cast<int*>(sm + L.tabh)[i] = tabh[i];
+}
+// `bytes` bytes of a byte plane -> LDS (dst 16-byte aligned), 16 B per lane when the source allows it
+__device__ __forceinline__ void occ_stage_bytes(unsigned char* dst, const unsigned char* __restrict__ s, int bytes, int t) {
+  if (bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+    for (int i = t; i < bytes / 16; i += OCC_OUT_T)
+      reinterpret_cast<u32x4*>(dst)[i] = reinterpret_cast<const u32x4*>(s)[i];
+  } else {
+    for (int i = t; i < bytes; i += OCC_OUT_T) dst[i] = s[i];
+  }
+}
+// horizontal pass P [H][W] -> Bh [H][ow], four outputs per lane
+__device__ __forceinline__ void occ_pass_h(const unsigned char* P, unsigned char* Bh, const int* tw, int H, int W, int ow,
+                                           int t) {
+  for (int i = t; i < H * ow / 4; i += OCC_OUT_T) {
+    const int y = (i * 4) / ow, xx = i * 4 - y * ow;
+    unsigned int pack = 0;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const int* k = tw + (xx + e) * OCC_RT;
+      const unsigned char* row = P + y * W + k[0];
+      int ss = 1 << 21;
+      for (int j = 0; j < k[1]; j++) ss += (int)row[j] * k[2 + j];
+      pack |= (unsigned int)occ_clip8(ss >> 22) << (8 * e);
+    }
+    reinterpret_cast<unsigned int*>(Bh)[i] = pack;
+  }
+}
+// vertical pass (th null: the axis keeps its size) + flip of Q [.][ow] for output pixels (x .. x + 3, yy) -> v
+__device__ __forceinline__ void occ_pass_v4(const unsigned char* Q, const int* th, int ow, int yy, int x, bool flip,
+                                            int (&v)[4]) {
+  const int base = flip ? ow - 4 - x : x;           // the four source columns, a 4-byte aligned word of every row
+  if (th) {
+    const int* k = th + yy * OCC_RT;
+    int ss[4] = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
+    for (int j = 0; j < k[1]; j++) {
+      const unsigned int wd = *reinterpret_cast<const unsigned int*>(Q + (k[0] + j) * ow + base);
+      const int kk = k[2 + j];
+#pragma unroll
+      for (int e = 0; e < 4; e++) ss[e] += (int)((wd >> (8 * e)) & 255u) * kk;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) v[e] = occ_clip8(ss[e] >> 22);
+  } else {
+    const unsigned int wd = *reinterpret_cast<const unsigned int*>(Q + yy * ow + base);
+#pragma unroll
+    for (int e = 0; e < 4; e++) v[e] = (int)((wd >> (8 * e)) & 255u);
+  }
+  if (flip) {
+    int s0 = v[0], s1 = v[1];
+    v[0] = v[3]; v[1] = v[2]; v[2] = s1; v[3] = s0;
+  }
+}
+// The light's maximum (out_img.max(), load_dataset.py:199) over O [C][oh * ow], first half: this wave's maximum -> red.
+// The kernel's barrier follows, then occ_light_max_fold gives every thread the workgroup's.
+__device__ __forceinline__ void occ_light_max_waves(const unsigned char* O, int C, int ohow, int ow, float lcx, float lcy,
+                                                    float lscale, float* red, int t) {
+  float vmax = 0.f;
+  for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
+    const int p = i * 4, y = p / ow, x = p - y * ow;
+    float l[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) l[e] = occ_lightmap(x + e, y, lcx, lcy, lscale);
+    for (int c = 0; c < C; c++) {
+      const unsigned int wd = reinterpret_cast<const unsigned int*>(O + (long)c * ohow)[i];
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        float v = (float)((wd >> (8 * e)) & 255u) / 255.0f;
+        v *= l[e];
+        vmax = fmaxf(vmax, v);
+      }
+    }
+  }
+  vmax = wave_max(vmax);
+  if ((t & 63) == 0) red[t >> 6] = vmax;
+}
+__device__ __forceinline__ float occ_light_max_fold(const float* red) {
+  float vmax = red[0];
+#pragma unroll
+  for (int w = 1; w < OCC_OUT_T / 64; w++) vmax = fmaxf(vmax, red[w]);
+  return vmax;
 }
 
 __global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_out(
@@ -538,7 +645,7 @@ __global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_out(
   extern __shared__ __attribute__((aligned(16))) unsigned char smo[];
   const int n = blockIdx.x, t = threadIdx.x;
   const int C = gray ? 1 : 3, HW = H * W, ohow = oh * ow;
-  const OccOutLds L = occ_out_lds(H, W, oh, ow, C);
+  const OccLds L = occ_lds(H, W, oh, ow, C, false);
   int* d = reinterpret_cast<int*>(smo);
   float* red = reinterpret_cast<float*>(smo + OCC_DESC * 4);
   const int* tw = ow != W ? reinterpret_cast<const int*>(smo + L.tabw) : nullptr;
@@ -549,18 +656,8 @@ __global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_out(
   unsigned char* Bh = smo + L.bh;
   unsigned char* O = smo + L.o;
   MSML_LDS_REGION(O, (long)C * ohow);
-  if (t < OCC_DESC) d[t] = desc[n * OCC_DESC + t];
-  if (tw) for (int i = t; i < ow * OCC_RT; i += OCC_OUT_T) reinterpret_cast<int*>(smo + L.tabw)[i] = tabw[i];
-  if (th) for (int i = t; i < oh * OCC_RT; i += OCC_OUT_T) reinterpret_cast<int*>(smo + L.tabh)[i] = tabh[i];
-  {
-    const unsigned char* s = src + (long)n * HW * 3;
-    if ((HW * 3) % 16 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-      for (int i = t; i < HW * 3 / 16; i += OCC_OUT_T)
-        reinterpret_cast<u32x4*>(raw)[i] = reinterpret_cast<const u32x4*>(s)[i];
-    } else {
-      for (int i = t; i < HW * 3; i += OCC_OUT_T) raw[i] = s[i];
-    }
-  }
+  occ_stage_tables(smo, L, tw != nullptr, th != nullptr, desc, tabw, tabh, n, oh, ow, t);
+  occ_stage_bytes(raw, src + (long)n * HW * 3, HW * 3, t);
   __syncthreads();
   const int kind = d[0];
   const bool flip = d[8] != 0;
@@ -606,48 +703,16 @@ __global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_out(
       P = S;
     }
     const unsigned char* Q = P;                       // [H][ow]
-    if (tw) {                                         // horizontal pass, four outputs per lane
-      for (int i = t; i < H * ow / 4; i += OCC_OUT_T) {
-        const int y = (i * 4) / ow, xx = i * 4 - y * ow;
-        unsigned int pack = 0;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const int* k = tw + (xx + e) * OCC_RT;
-          const unsigned char* row = P + y * W + k[0];
-          int ss = 1 << 21;
-          for (int j = 0; j < k[1]; j++) ss += (int)row[j] * k[2 + j];
-          pack |= (unsigned int)occ_clip8(ss >> 22) << (8 * e);
-        }
-        reinterpret_cast<unsigned int*>(Bh)[i] = pack;
-      }
+    if (tw) {
+      occ_pass_h(P, Bh, tw, H, W, ow, t);
       __syncthreads();
       Q = Bh;
     }
     // vertical pass + flip, four outputs per lane: the mask and the clean face go to HBM, the occluded face to O
     for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
       const int p = i * 4, yy = p / ow, x = p - yy * ow;
-      const int base = flip ? ow - 4 - x : x;         // the four source columns, a 4-byte aligned word of every row
       int v[4];
-      if (th) {
-        const int* k = th + yy * OCC_RT;
-        int ss[4] = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
-        for (int j = 0; j < k[1]; j++) {
-          const unsigned int wd = *reinterpret_cast<const unsigned int*>(Q + (k[0] + j) * ow + base);
-          const int kk = k[2 + j];
-#pragma unroll
-          for (int e = 0; e < 4; e++) ss[e] += (int)((wd >> (8 * e)) & 255u) * kk;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; e++) v[e] = occ_clip8(ss[e] >> 22);
-      } else {
-        const unsigned int wd = *reinterpret_cast<const unsigned int*>(Q + yy * ow + base);
-#pragma unroll
-        for (int e = 0; e < 4; e++) v[e] = (int)((wd >> (8 * e)) & 255u);
-      }
-      if (flip) {
-        int s0 = v[0], s1 = v[1];
-        v[0] = v[3]; v[1] = v[2]; v[2] = s1; v[3] = s0;
-      }
+      occ_pass_v4(Q, th, ow, yy, x, flip, v);
       if (pl == 0) {                                  // Msk2Tenser: != 255 -> 0, else 1
         longlong2 a, b;
         a.x = v[0] == 255; a.y = v[1] == 255; b.x = v[2] == 255; b.y = v[3] == 255;
@@ -671,43 +736,17 @@ __global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_out(
   }
   // ToTensor, light at the output size, / max, Normalize: img is written once
   const float lcx = __int_as_float(d[9]), lcy = __int_as_float(d[10]), lscale = __int_as_float(d[11]);
-  auto lightmap = [&](int x, int y) -> float {        // as k_occ_apply
-    const int ix = (int)((float)x - lcx), iy = (int)((float)y - lcy);
-    const float dist = sqrtf((float)(ix * ix + iy * iy));
-    const float g = expf(-0.5f * (dist * dist) / 16384.0f);
-    const __half g16 = __float2half(g);
-    const __half l16 = __float2half(__half2float(g16) * __half2float(__float2half(lscale)));
-    return __half2float(l16);
-  };
   float vmax = 0.f;
   if (light) {
-    for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
-      const int p = i * 4, y = p / ow, x = p - y * ow;
-      float l[4];
-#pragma unroll
-      for (int e = 0; e < 4; e++) l[e] = lightmap(x + e, y);
-      for (int c = 0; c < C; c++) {
-        const unsigned int wd = reinterpret_cast<const unsigned int*>(O + (long)c * ohow)[i];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          float v = (float)((wd >> (8 * e)) & 255u) / 255.0f;
-          v *= l[e];
-          vmax = fmaxf(vmax, v);
-        }
-      }
-    }
-    vmax = wave_max(vmax);
-    if ((t & 63) == 0) red[t >> 6] = vmax;
+    occ_light_max_waves(O, C, ohow, ow, lcx, lcy, lscale, red, t);
     __syncthreads();
-    vmax = red[0];
-#pragma unroll
-    for (int w = 1; w < OCC_OUT_T / 64; w++) vmax = fmaxf(vmax, red[w]);
+    vmax = occ_light_max_fold(red);
   }
   for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
     const int p = i * 4, y = p / ow, x = p - y * ow;
     float l[4];
 #pragma unroll
-    for (int e = 0; e < 4; e++) l[e] = light ? lightmap(x + e, y) : 1.f;
+    for (int e = 0; e < 4; e++) l[e] = light ? occ_lightmap(x + e, y, lcx, lcy, lscale) : 1.f;
     for (int c = 0; c < C; c++) {
       const unsigned int wd = reinterpret_cast<const unsigned int*>(O + (long)c * ohow)[i];
       f32x4 r;
@@ -730,8 +769,27 @@ extern "C" int msml_occ_draw_out(long seed, long offset, int N, int H, int W, in
              "occ_draw_out: bad arguments N=%d H=%d W=%d out=%dx%d mode=%d lo=%d hi=%d", N, H, W, out_h, out_w, mode, lo, hi);
   MSML_CHECK(mode < 5 || (meta && nsets > 0 && nsets <= 16), MSML_ERR_SHAPE,
              "occ_draw_out: modes 5-9 need 1..16 occluder sets (got %d)", nsets);
-  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, mode < 5 ? nullptr : meta, mode < 5 ? 0 : nsets, desc, out_h, out_w, 0.f);
-  MSML_LAUNCH_OK("occ_draw_out");
+  return occ_draw_launch("occ_draw_out", seed, offset, N, H, W, mode, lo, hi, flip, mode < 5 ? nullptr : meta,
+                         mode < 5 ? 0 : nsets, desc, out_h, out_w, 0.f, stream);
+}
+
+// What msml_occ_apply_out and msml_occ_apply_mask (mb) check after their own arguments, and the launch's LDS bytes, which
+// `kernel` is allowed from here on; *attr_lds is the caller's record of what it has been allowed so far.
+static int occ_out_setup(const char* name, const void* kernel, int* attr_lds, bool mb, const int* tabw, const int* tabh,
+                         int H, int W, int out_h, int out_w, int gray, long* lds_bytes) {
+  MSML_CHECK((out_w == W || tabw) && (out_h == H || tabh), MSML_ERR_SHAPE,
+             "%s: %dx%d -> %dx%d needs the resampling table of every axis that changes", name, H, W, out_h, out_w);
+  MSML_CHECK(out_w % 4 == 0, MSML_ERR_UNSUPPORTED,
+             "%s: output width %d is not a multiple of 4 (16-byte stores)", name, out_w);
+  const OccLds L = occ_lds(H, W, out_h, out_w, gray ? 1 : 3, mb);
+  MSML_CHECK(L.total <= 160 * 1024, MSML_ERR_UNSUPPORTED,
+             "%s: %dx%d -> %dx%d %s needs %ld bytes of LDS (163840 available)", name, H, W, out_h, out_w,
+             gray ? "gray" : "RGB", L.total);
+  if ((int)L.total > *attr_lds) {               // (monotonic; racing callers set the same or a larger value)
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total);
+    *attr_lds = (int)L.total;
+  }
+  *lds_bytes = L.total;
   return MSML_OK;
 }
 
@@ -741,21 +799,12 @@ extern "C" int msml_occ_apply_out(const unsigned char* src, const int* desc, con
   MSML_CHECK(src && desc && img && msk && N > 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0 && H <= 4096 && W <= 4096 &&
                  out_h <= 4096 && out_w <= 4096 && (patch == nullptr || patch_stride > 0),
              MSML_ERR_SHAPE, "occ_apply_out: bad arguments N=%d H=%d W=%d out=%dx%d", N, H, W, out_h, out_w);
-  MSML_CHECK((out_w == W || tabw) && (out_h == H || tabh), MSML_ERR_SHAPE,
-             "occ_apply_out: %dx%d -> %dx%d needs the resampling table of every axis that changes", H, W, out_h, out_w);
-  MSML_CHECK(out_w % 4 == 0, MSML_ERR_UNSUPPORTED,
-             "occ_apply_out: output width %d is not a multiple of 4 (16-byte stores)", out_w);
-  const OccOutLds L = occ_out_lds(H, W, out_h, out_w, gray ? 1 : 3);
-  MSML_CHECK(L.total <= 160 * 1024, MSML_ERR_UNSUPPORTED,
-             "occ_apply_out: %dx%d -> %dx%d %s needs %ld bytes of LDS (163840 available)", H, W, out_h, out_w,
-             gray ? "gray" : "RGB", L.total);
   static int attr_lds = 0;
-  if ((int)L.total > attr_lds) {                // (monotonic; racing callers set the same or a larger value)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_occ_apply_out), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)L.total);
-    attr_lds = (int)L.total;
-  }
-  k_occ_apply_out<<<N, OCC_OUT_T, (size_t)L.total, (hipStream_t)stream>>>(src, desc, patch, patch_stride, tabw, tabh, img, msk, ori, H, W, out_h, out_w, gray, norm, light);
+  long lds = 0;
+  const int rc = occ_out_setup("occ_apply_out", reinterpret_cast<const void*>(&k_occ_apply_out), &attr_lds, false, tabw,
+                               tabh, H, W, out_h, out_w, gray, &lds);
+  if (rc != MSML_OK) return rc;
+  k_occ_apply_out<<<N, OCC_OUT_T, (size_t)lds, (hipStream_t)stream>>>(src, desc, patch, patch_stride, tabw, tabh, img, msk, ori, H, W, out_h, out_w, gray, norm, light);
   MSML_LAUNCH_OK("occ_apply_out");
   return MSML_OK;
 }
@@ -777,24 +826,8 @@ extern "C" int msml_occ_apply_out(const unsigned char* src, const int* desc, con
 //     types 0 / 1: times the channel's jitter bit (:261); gray: (0.2989 l0 + 0.5870 l1 + 0.1140 l2) / 3 with every
 //     operation rounded to float16 (:265-267)
 //   img = face - msk_light in f32, not clamped (:271) -> Normalize only when asked.
-// LDS as k_occ_apply_out without the clean planes, plus MB [oh][ow], the binarised mask the last pass reads.
-struct OccMaskLds {
-  long tabw, tabh, raw, mk, s, bh, o, mb, total;
-};
-__host__ __device__ inline OccMaskLds occ_mask_lds(int H, int W, int oh, int ow, int C) {
-  OccMaskLds L;
-  long off = OCC_OUT_HDR;
-  L.tabw = off; off += ow != W ? occ_r16((long)ow * OCC_RT * 4) : 0;
-  L.tabh = off; off += oh != H ? occ_r16((long)oh * OCC_RT * 4) : 0;
-  L.raw = off;  off += occ_r16((long)H * W * 3);
-  L.mk = off;   off += occ_r16((long)H * W);
-  L.s = off;    off += occ_r16((long)H * W);
-  L.bh = off;   off += ow != W ? occ_r16((long)H * ow) : 0;
-  L.o = off;    off += occ_r16((long)C * oh * ow);
-  L.mb = off;   off += occ_r16((long)oh * ow);
-  L.total = off;
-  return L;
-}
+// LDS as k_occ_apply_out without the clean planes, plus MB [oh][ow], the binarised mask the last pass reads
+// (occ_lds with mb).
 // The standard normal of output pixel (x, y) of image `img` (= offset + n), as a float16: a key domain of its own
 // (seed + "mask"), keyed by the absolute pixel, so it depends on nothing else: r = mix(key + y * 65536 + x) with the image's
 // key = mix(mix(seed + 0x6D61736B) + img), which k_occ_draw leaves in words 28 (low half) and 29 (high half).  Box-Muller
@@ -822,7 +855,7 @@ __global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_mask(
   const int row = rows ? rows[n] : n;
   if (row < 0 || row >= M) return;               // no render for this sample: it stays the clean one
   const int C = gray ? 1 : 3, HW = H * W, ohow = oh * ow;
-  const OccMaskLds L = occ_mask_lds(H, W, oh, ow, C);
+  const OccLds L = occ_lds(H, W, oh, ow, C, true);
   int* d = reinterpret_cast<int*>(smm);
   float* red = reinterpret_cast<float*>(smm + OCC_DESC * 4);
   const int* tw = ow != W ? reinterpret_cast<const int*>(smm + L.tabw) : nullptr;
@@ -834,25 +867,9 @@ __global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_mask(
   unsigned char* O = smm + L.o;
   unsigned char* MB = smm + L.mb;
   MSML_LDS_REGION(MB, (long)ohow);
-  if (t < OCC_DESC) d[t] = desc[n * OCC_DESC + t];
-  if (tw) for (int i = t; i < ow * OCC_RT; i += OCC_OUT_T) reinterpret_cast<int*>(smm + L.tabw)[i] = tabw[i];
-  if (th) for (int i = t; i < oh * OCC_RT; i += OCC_OUT_T) reinterpret_cast<int*>(smm + L.tabh)[i] = tabh[i];
-  {
-    const unsigned char* s = masked + (long)row * HW * 3;
-    if ((HW * 3) % 16 == 0 && (reinterpret_cast<uintptr_t>(masked) & 15) == 0) {
-      for (int i = t; i < HW * 3 / 16; i += OCC_OUT_T)
-        reinterpret_cast<u32x4*>(raw)[i] = reinterpret_cast<const u32x4*>(s)[i];
-    } else {
-      for (int i = t; i < HW * 3; i += OCC_OUT_T) raw[i] = s[i];
-    }
-    const unsigned char* m = mask + (long)row * HW;
-    if (HW % 16 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0) {
-      for (int i = t; i < HW / 16; i += OCC_OUT_T)
-        reinterpret_cast<u32x4*>(Mk)[i] = reinterpret_cast<const u32x4*>(m)[i];
-    } else {
-      for (int i = t; i < HW; i += OCC_OUT_T) Mk[i] = m[i];
-    }
-  }
+  occ_stage_tables(smm, L, tw != nullptr, th != nullptr, desc, tabw, tabh, n, oh, ow, t);
+  occ_stage_bytes(raw, masked + (long)row * HW * 3, HW * 3, t);
+  occ_stage_bytes(Mk, mask + (long)row * HW, HW, t);
   __syncthreads();
   const bool flip = d[8] != 0;
   // planes: 0 = mask, 1 .. C = rendered face
@@ -868,48 +885,16 @@ __global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_mask(
       P = S;
     }
     const unsigned char* Q = P;                       // [H][ow]
-    if (tw) {                                         // horizontal pass, four outputs per lane
-      for (int i = t; i < H * ow / 4; i += OCC_OUT_T) {
-        const int y = (i * 4) / ow, xx = i * 4 - y * ow;
-        unsigned int pack = 0;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const int* k = tw + (xx + e) * OCC_RT;
-          const unsigned char* rw = P + y * W + k[0];
-          int ss = 1 << 21;
-          for (int j = 0; j < k[1]; j++) ss += (int)rw[j] * k[2 + j];
-          pack |= (unsigned int)occ_clip8(ss >> 22) << (8 * e);
-        }
-        reinterpret_cast<unsigned int*>(Bh)[i] = pack;
-      }
+    if (tw) {
+      occ_pass_h(P, Bh, tw, H, W, ow, t);
       __syncthreads();
       Q = Bh;
     }
     // vertical pass + flip, four outputs per lane: the mask goes to HBM and, binarised, to MB; the face to O
     for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
       const int p = i * 4, yy = p / ow, x = p - yy * ow;
-      const int base = flip ? ow - 4 - x : x;
       int v[4];
-      if (th) {
-        const int* k = th + yy * OCC_RT;
-        int ss[4] = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
-        for (int j = 0; j < k[1]; j++) {
-          const unsigned int wd = *reinterpret_cast<const unsigned int*>(Q + (k[0] + j) * ow + base);
-          const int kk = k[2 + j];
-#pragma unroll
-          for (int e = 0; e < 4; e++) ss[e] += (int)((wd >> (8 * e)) & 255u) * kk;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; e++) v[e] = occ_clip8(ss[e] >> 22);
-      } else {
-        const unsigned int wd = *reinterpret_cast<const unsigned int*>(Q + yy * ow + base);
-#pragma unroll
-        for (int e = 0; e < 4; e++) v[e] = (int)((wd >> (8 * e)) & 255u);
-      }
-      if (flip) {
-        int s0 = v[0], s1 = v[1];
-        v[0] = v[3]; v[1] = v[2]; v[2] = s1; v[3] = s0;
-      }
+      occ_pass_v4(Q, th, ow, yy, x, flip, v);
       if (pl == 0) {                                  // :212: <= 128 -> 0 (occluded), else 255; :278: // 255
         longlong2 a, b;
         a.x = v[0] > 128; a.y = v[1] > 128; b.x = v[2] > 128; b.y = v[3] > 128;
@@ -926,37 +911,11 @@ __global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_mask(
     __syncthreads();                                  // S / Bh are rebuilt for the next plane; O and MB are complete after the last
   }
   const float lcx = __int_as_float(d[9]), lcy = __int_as_float(d[10]), lscale = __int_as_float(d[11]);
-  auto lightmap = [&](int x, int y) -> float {        // as k_occ_apply
-    const int ix = (int)((float)x - lcx), iy = (int)((float)y - lcy);
-    const float dist = sqrtf((float)(ix * ix + iy * iy));
-    const float g = expf(-0.5f * (dist * dist) / 16384.0f);
-    const __half g16 = __float2half(g);
-    const __half l16 = __float2half(__half2float(g16) * __half2float(__float2half(lscale)));
-    return __half2float(l16);
-  };
   float vmax = 0.f;
   if (light) {
-    for (int i = t; i < ohow / 4; i += OCC_OUT_T) {
-      const int p = i * 4, y = p / ow, x = p - y * ow;
-      float l[4];
-#pragma unroll
-      for (int e = 0; e < 4; e++) l[e] = lightmap(x + e, y);
-      for (int c = 0; c < C; c++) {
-        const unsigned int wd = reinterpret_cast<const unsigned int*>(O + (long)c * ohow)[i];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          float v = (float)((wd >> (8 * e)) & 255u) / 255.0f;
-          v *= l[e];
-          vmax = fmaxf(vmax, v);
-        }
-      }
-    }
-    vmax = wave_max(vmax);
-    if ((t & 63) == 0) red[t >> 6] = vmax;
+    occ_light_max_waves(O, C, ohow, ow, lcx, lcy, lscale, red, t);
     __syncthreads();
-    vmax = red[0];
-#pragma unroll
-    for (int w = 1; w < OCC_OUT_T / 64; w++) vmax = fmaxf(vmax, red[w]);
+    vmax = occ_light_max_fold(red);
   }
   const int type = d[16], lx = d[17], ly = d[18], rx = d[19], ry = d[20];
   const float sgn = (float)d[21];
@@ -974,7 +933,7 @@ __global__ void __launch_bounds__(OCC_OUT_T) k_occ_apply_mask(
     __half m16[4];
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-      l[e] = light ? lightmap(x + e, y) : 1.f;
+      l[e] = light ? occ_lightmap(x + e, y, lcx, lcy, lscale) : 1.f;
       const int X = x + e;
       m16[e] = hzero;
       if (((mb >> (8 * e)) & 255u) == 0u && X >= lx && X < rx && y >= ly && y < ry) {
@@ -1028,9 +987,8 @@ extern "C" int msml_occ_draw_mask(long seed, long offset, int N, int H, int W, i
              "occ_draw_mask: modes 5-9 need 1..16 occluder sets (got %d)", nsets);
   MSML_CHECK(p_mask == 0.f || (out_h >= 111 && out_w >= 110), MSML_ERR_SHAPE,
              "occ_draw_mask: the mask rectangle (up to x 110, y 111) does not fit an output of %dx%d", out_h, out_w);
-  k_occ_draw<<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>((unsigned long long)seed, (unsigned long long)offset, N, H, W, mode, lo, hi, flip, mode < 5 ? nullptr : meta, mode < 5 ? 0 : nsets, desc, out_h, out_w, p_mask);
-  MSML_LAUNCH_OK("occ_draw_mask");
-  return MSML_OK;
+  return occ_draw_launch("occ_draw_mask", seed, offset, N, H, W, mode, lo, hi, flip, mode < 5 ? nullptr : meta,
+                         mode < 5 ? 0 : nsets, desc, out_h, out_w, p_mask, stream);
 }
 
 extern "C" int msml_occ_apply_mask(const unsigned char* masked, const unsigned char* mask, const int* rows, int M,
@@ -1039,21 +997,12 @@ extern "C" int msml_occ_apply_mask(const unsigned char* masked, const unsigned c
   MSML_CHECK(masked && mask && desc && img && msk && N > 0 && M > 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0 &&
                  H <= 4096 && W <= 4096 && out_h <= 4096 && out_w <= 4096 && (rows || M >= N),
              MSML_ERR_SHAPE, "occ_apply_mask: bad arguments N=%d M=%d H=%d W=%d out=%dx%d", N, M, H, W, out_h, out_w);
-  MSML_CHECK((out_w == W || tabw) && (out_h == H || tabh), MSML_ERR_SHAPE,
-             "occ_apply_mask: %dx%d -> %dx%d needs the resampling table of every axis that changes", H, W, out_h, out_w);
-  MSML_CHECK(out_w % 4 == 0, MSML_ERR_UNSUPPORTED,
-             "occ_apply_mask: output width %d is not a multiple of 4 (16-byte stores)", out_w);
-  const OccMaskLds L = occ_mask_lds(H, W, out_h, out_w, gray ? 1 : 3);
-  MSML_CHECK(L.total <= 160 * 1024, MSML_ERR_UNSUPPORTED,
-             "occ_apply_mask: %dx%d -> %dx%d %s needs %ld bytes of LDS (163840 available)", H, W, out_h, out_w,
-             gray ? "gray" : "RGB", L.total);
   static int attr_lds = 0;
-  if ((int)L.total > attr_lds) {                // (monotonic; racing callers set the same or a larger value)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_occ_apply_mask), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)L.total);
-    attr_lds = (int)L.total;
-  }
-  k_occ_apply_mask<<<N, OCC_OUT_T, (size_t)L.total, (hipStream_t)stream>>>(masked, mask, rows, M, desc, tabw, tabh, img, msk, H, W, out_h, out_w, gray, norm, light);
+  long lds = 0;
+  const int rc = occ_out_setup("occ_apply_mask", reinterpret_cast<const void*>(&k_occ_apply_mask), &attr_lds, true, tabw,
+                               tabh, H, W, out_h, out_w, gray, &lds);
+  if (rc != MSML_OK) return rc;
+  k_occ_apply_mask<<<N, OCC_OUT_T, (size_t)lds, (hipStream_t)stream>>>(masked, mask, rows, M, desc, tabw, tabh, img, msk, H, W, out_h, out_w, gray, norm, light);
   MSML_LAUNCH_OK("occ_apply_mask");
   return MSML_OK;
 }

@@ -38,49 +38,19 @@ KINDS = {"glasses": 5, "scarf": 6, "object": 7}
 META_WORDS, RT_WORDS = 16, 10
 
 
-def _bicubic(x):
-    x = abs(x)
-    if x < 1.0:
-        return (1.5 * x - 2.5) * x * x + 1
-    if x < 2.0:
-        return (((x - 5) * x + 8) * x - 4) * -0.5
-    return 0.0
-
-
-def _bilinear(x):
-    x = abs(x)
-    return 1.0 - x if x < 1.0 else 0.0
-
-
-_FILTERS = {"bicubic": (_bicubic, 2.0), "bilinear": (_bilinear, 1.0)}      # Resample.c: filter, support
-
-
 def resample_table(insz, outsz, filter="bicubic"):
-    """Pillow's resampling coefficients for one axis (Resample.c precompute_coeffs + normalize_coeffs_8bpc): int32
+    """Pillow's resampling coefficients for one axis (resample.pillow_coeffs) as csrc/occ.hip reads them: int32
     [outsz][10] = first tap, taps, up to 8 coefficients in 22-bit fixed point.  "bicubic" is what Image.resize -- the
     call of rand_occ.py:375,466,562 -- uses by default; "bilinear" (the triangle filter, support 1) is
-    transforms.Resize on a PIL image (load_dataset.py:117-120).  Double precision on the host, exactly as the library
-    computes them."""
+    transforms.Resize on a PIL image (load_dataset.py:117-120)."""
     import numpy as np
-    kernel, support = _FILTERS[filter]
-    scale = insz / outsz
-    fscale = max(scale, 1.0)
-    support = support * fscale
+    from .resample import pillow_coeffs
+    xmin, cnt, fixed = pillow_coeffs(insz, outsz, filter)
+    if fixed.shape[1] > RT_WORDS - 2:
+        raise ValueError("resample_table: %d -> %d needs %d taps (at most %d)"
+                         % (insz, outsz, cnt[np.argmax(cnt > RT_WORDS - 2)], RT_WORDS - 2))
     tab = np.zeros((outsz, RT_WORDS), np.int32)
-    for xx in range(outsz):
-        center = (xx + 0.5) * scale
-        xmin = max(int(center - support + 0.5), 0)
-        cnt = min(int(center + support + 0.5), insz) - xmin
-        if cnt > RT_WORDS - 2:
-            raise ValueError("resample_table: %d -> %d needs %d taps (at most %d)" % (insz, outsz, cnt, RT_WORDS - 2))
-        k = [kernel((x + xmin - center + 0.5) / fscale) for x in range(cnt)]
-        ww = 0.0
-        for v in k:
-            ww += v
-        if ww != 0.0:
-            k = [v / ww for v in k]
-        tab[xx, 0], tab[xx, 1] = xmin, cnt
-        tab[xx, 2:2 + cnt] = [int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22)) for v in k]
+    tab[:, 0], tab[:, 1], tab[:, 2:2 + fixed.shape[1]] = xmin, cnt, fixed
     return tab
 
 

@@ -35,6 +35,7 @@ import torch
 
 from . import _lib, detect, ijb
 from ._lib import call
+from .resample import pillow_coeffs
 
 BILINEAR, BICUBIC = 2, 3                                  # PIL.Image's filter numbers
 FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM, ROTATE_90, ROTATE_180, ROTATE_270 = range(5)
@@ -199,51 +200,22 @@ def map_boxes(boxes, i, w, h):
 # ---------------------------------------------------------------------------------------------------------------------
 # device: packed images, Image.transpose, Image.resize
 
-def _bicubic(x):
-    x = np.abs(x)
-    return np.where(x < 1.0, (1.5 * x - 2.5) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * -0.5, 0.0))
-
-
-def _bilinear(x):
-    x = np.abs(x)
-    return np.where(x < 1.0, 1.0 - x, 0.0)
-
-
-_FILTERS = {BILINEAR: (_bilinear, 1.0), BICUBIC: (_bicubic, 2.0)}          # Resample.c: filter, support
+_FILTERS = {BILINEAR: "bilinear", BICUBIC: "bicubic"}                      # resample.FILTERS' names
 
 
 @functools.lru_cache(maxsize=256)
 def resample_rows(insz, outsz, filter=BICUBIC):
-    """Pillow's coefficients for one axis (Resample.c precompute_coeffs + normalize_coeffs_8bpc) as msml_img_resize
-    reads them: int32 [outsz][2 + ksize] = first tap, taps, coefficients in 22-bit fixed point (zero behind the taps).
-    Double precision, in Pillow's order of operations: support scaled by max(scale, 1), window int(center -+ support +
-    0.5) clamped to the axis, the weights summed tap after tap and divided by the sum, then int(+-0.5 + k 2^22).  Equal
-    lengths give the identity (one tap of 2^22): Pillow skips that pass, which is a copy."""
+    """Pillow's coefficients for one axis (resample.pillow_coeffs) as msml_img_resize reads them: int32
+    [outsz][2 + ksize] = first tap, taps, coefficients in 22-bit fixed point (zero behind the taps).  Equal lengths
+    give the identity (one tap of 2^22): Pillow skips that pass, which is a copy."""
     insz, outsz = int(insz), int(outsz)
     if insz == outsz:
         tab = np.zeros((outsz, 3), np.int32)
         tab[:, 0], tab[:, 1], tab[:, 2] = np.arange(outsz), 1, 1 << 22
         return tab
-    kernel, support = _FILTERS[filter]
-    scale = insz / outsz
-    fscale = max(scale, 1.0)
-    support = support * fscale
-    ss = 1.0 / fscale
-    center = (np.arange(outsz) + 0.5) * scale
-    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)        # C's (int): truncation
-    cnt = np.minimum((center + support + 0.5).astype(np.int64), insz) - xmin
-    ksize = int(cnt.max())
-    j = np.arange(ksize)
-    w = kernel((j[None, :] + xmin[:, None] - center[:, None] + 0.5) * ss)
-    w = np.where(j[None, :] < cnt[:, None], w, 0.0)
-    ww = np.zeros(outsz)
-    for k in range(ksize):                                                 # ww += w, tap after tap as the C loop
-        ww = ww + w[:, k]
-    w = np.where((ww != 0.0)[:, None], w / np.where(ww != 0.0, ww, 1.0)[:, None], w)
-    fixed = np.where(w < 0, -0.5 + w * (1 << 22), 0.5 + w * (1 << 22)).astype(np.int64)      # (int): truncation
-    tab = np.zeros((outsz, 2 + ksize), np.int32)
-    tab[:, 0], tab[:, 1] = xmin, cnt
-    tab[:, 2:] = np.where(j[None, :] < cnt[:, None], fixed, 0)
+    xmin, cnt, fixed = pillow_coeffs(insz, outsz, _FILTERS[filter])
+    tab = np.zeros((outsz, 2 + fixed.shape[1]), np.int32)
+    tab[:, 0], tab[:, 1], tab[:, 2:] = xmin, cnt, fixed
     return tab
 
 

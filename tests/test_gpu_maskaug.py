@@ -84,6 +84,23 @@ def test_mask_samples_match_restatement(gray, out_size, use_norm, light):
     assert img.min().item() < lo and img.max().item() > 1.0            # not clamped (:271)
 
 
+@pytest.mark.parametrize("light", [False, True])
+@pytest.mark.parametrize("gray,use_norm", [(True, False), (False, True)])
+def test_mask_samples_horizontal_pass_alone(gray, use_norm, light):
+    """out_size = (112, 116): the height stays, so the overlay runs its horizontal pass and no vertical one (CONFIGS has
+    the other half, (111, 112)).  116 is the smallest multiple of 4 that holds the 110-pixel rectangle."""
+    from msml_amd import data
+    n, out_size = 8, (112, 116)
+    src, masked, mask, dsrc, dmasked, dmask = batch(n)
+    img, msk, ori, desc = data.augment(dsrc, SEED, OFFSET, "train", 0, 36, True, light, True, None, gray, out_size, use_norm,
+                                       1.0, dmasked, dmask)
+    ref_desc = MC.draw(SEED, OFFSET, n, 112, 112, 0, out_size=out_size, p_mask=1.0)
+    assert np.array_equal(desc.cpu().numpy(), ref_desc)
+    assert img.shape == (n, 1 if gray else 3, 112, 116)
+    check((img, msk, ori), MC.apply(src, masked, mask, ref_desc, light, (), gray, out_size, use_norm, steps=(0, -1, 1)),
+          light, use_norm)
+
+
 @pytest.mark.parametrize("mode", ["train", "ms1m"])
 def test_flag_consistency(mode):
     """p_mask = 0.2: the flagged set is mask_flags'; unflagged samples are the p_mask = 0 run's bits, flagged ones the

@@ -71,6 +71,23 @@ def test_gray_resized_pipeline_matches_restatement(mode, gray, out_size, use_nor
         assert (msk == 0).any()
 
 
+@pytest.mark.parametrize("mode", ["rect", "glasses"])
+def test_vertical_pass_alone(mode):
+    """out_size = (96, 112): the width stays, so the kernel runs its vertical pass and no horizontal one (SWITCHES has
+    the other half, (112, 96)); gray, with ori, a geometric and a texture occluder."""
+    from msml_amd import data
+    n, out_size = 8, (96, 112)
+    src, dsrc = faces(n)
+    atlas, osets = atlas_and_sets() if mode in TEXTURE else (None, ())
+    img, msk, ori, desc = data.augment(dsrc, 1234, 5000, mode, 0, 36, True, True, True, atlas, gray=True, out_size=out_size,
+                                       use_norm=False)
+    ref_desc = G.draw(1234, 5000, n, 112, 112, data.MODES[mode], 0, 36, True, sets=osets, out_size=out_size)
+    assert np.array_equal(desc.cpu().numpy(), ref_desc)
+    assert img.shape == (n, 1, 96, 112)
+    check((img, msk, ori), G.apply(src, ref_desc, True, True, osets, True, out_size, False), True, False)
+    assert (msk == 0).any()
+
+
 def test_mask_is_interpolated_on_the_device():
     """The 40 x 70 rectangle of the CPU test: 3 807 occluded pixels at 128, as Pillow's interpolated mask -- a kernel that
     rescaled the rectangle instead (3 657) fails here."""
