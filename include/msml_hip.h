@@ -942,6 +942,40 @@ int msml_img_resize(const unsigned char* src, const long* meta, unsigned char* d
                     const int* tables, const long* jobs, const long* sizes, int N, int filter, unsigned char* ws,
                     long ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- baseline JPEG decoding -------------------------
+ * mx.image.imdecode / cv2.imread on the device (datasets/load_dataset.py:106-174, eval/verification.py:202-236): N
+ * baseline (SOF0, 8-bit, Huffman, one scan) streams of any sizes in one call, the same uint8 pixels libjpeg writes
+ * with its defaults (JDCT_ISLOW, fancy upsampling).  The host parses the headers only (msml_amd/jpeg.py); the device
+ * walks the entropy-coded bytes.  Integer arithmetic, no atomics, one writer per byte: two runs give the same bits.
+ *
+ *   streams: the packed byte strings, stream n at dword offset desc[n][0]; stream_bytes: the length of the buffer, a
+ *     multiple of 4 (the device reads the streams as aligned dwords, none past the dword of a stream's last byte).
+ *   desc / desc_host [N][32] int32: the same descriptors on the device and on the HOST (csrc/jpeg_core.h names the
+ *     words: stream range, H, W, components, sampling, table selectors, restart interval, the parser's status, MCU
+ *     counts, workspace offset).  The library checks desc_host before it launches: sizes in 1..32767, gray / 4:4:4 /
+ *     4:2:2 / 4:2:0, table selectors below nq / nh, the stream inside stream_bytes, the workspace offsets those
+ *     msml_jpeg_workspace wrote.  A descriptor whose status word is not 0 (a stream the parser refused) is not decoded.
+ *   qtabs [nq][64] int32: quantisation tables in natural order; htabs [nh][832] int32: Huffman tables in lookup form.
+ *   dst / meta_out [N][4] int64 (device) = byte offset, H, W, row pitch, as msml_align_warp takes its sources;
+ *     channels 3 (R, G, B; B, G, R with swap_rb; a gray stream replicates Y) or 1 (gray streams only, one byte per
+ *     pixel).  The device checks each row of meta_out against the stream's H and W and against dst_bytes; where offset
+ *     and pitch are multiples of 4 the bytes between the row and its pitch are written as 0.
+ *   status [N] int32: 0, or why image n was not decoded: 1 a code in no table, 2 a coefficient index past 63, 3 a DC
+ *     category above 11 or an AC category above 10, 4 a restart marker missing or out of sequence, 5 data that ends
+ *     before the last MCU, 6 a meta_out row that is not this image inside dst, 16.. the parser's reason.  Such an image
+ *     leaves its output rectangle as it was; the other images are unaffected.  For ANY bytes the device reads only
+ *     inside the stream's range and the tables and writes only the image's own workspace and rectangle.
+ *   msml_jpeg_workspace(desc, N): on the HOST descriptors, writes each image's workspace offset into its descriptor
+ *     and returns the bytes msml_jpeg_decode needs (0 for a descriptor it would refuse).
+ *   MSML_ERR_UNSUPPORTED before any launch for N outside 1..65535, channels other than 1 or 3, a 3-component stream
+ *   with channels 1; MSML_ERR_SHAPE for null or misaligned pointers (4 bytes; meta_out 8, ws 16) and an inconsistent
+ *   descriptor; MSML_ERR_WORKSPACE for a workspace that is too small. */
+long msml_jpeg_workspace(int* desc, int N);
+int msml_jpeg_decode(const unsigned char* streams, long stream_bytes, const int* desc, const int* desc_host,
+                     const int* qtabs, int nq, const int* htabs, int nh, unsigned char* dst, long dst_bytes,
+                     const long* meta_out, int channels, int swap_rb, int* status, unsigned char* ws, long ws_bytes,
+                     int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,238 @@
+// Baseline JPEG decoding on the device, bit-exact with libjpeg's defaults (JDCT_ISLOW, fancy upsampling): the
+// mx.image.imdecode / cv2.imread in front of every input path of the reference (datasets/load_dataset.py,
+// eval/verification.py).  The arithmetic is csrc/jpeg_core.h, shared with the host check; tests/jpeg_cases.py restates it.
+//   k_jpeg_entropy  one wavefront per image: the Huffman walk is the same for all 64 lanes (every address it reads is
+//                   wave-uniform) out of LDS: the image's Huffman tables and a window of its stream.  Lane k keeps the
+//                   k-th coefficient of the current block, so a finished block leaves as one 128-byte vector store.
+//                   Writes status[n].
+//   k_jpeg_idct     one thread per 8 x 8 block: dequantise, IDCT, into the component planes of the workspace
+//   k_jpeg_store    one thread per 4 output pixels: upsample, convert, store into the packed destination
+// No atomics, one writer per byte: two runs give the same bits.  An image whose status is not 0 is skipped by the two
+// later passes: its output rectangle is left as it was.
+#include "common.h"
+#include "jpeg_core.h"
+
+// lane k keeps the k-th coefficient (zigzag order) of the current block and stores it at its natural index
+struct JpgWaveSink {
+  int16_t* coef;
+  int lane, nat;
+  int c;
+  __device__ void begin() { c = 0; }
+  __device__ void put(int k, int v) {
+    if (lane == k) c = v;
+  }
+  __device__ void end(long blk) { coef[blk * 64 + nat] = (int16_t)c; }
+};
+
+// The stream of one image behind a window of JPG_CHUNK bytes in LDS: the decoder reads forward, a byte at a time, and
+// a read outside the window makes all 64 lanes fetch the chunk that holds it (aligned dwords, none past the dword of
+// the stream's last byte; msml_jpeg_decode checks that the buffer is whole dwords).
+#define JPG_CHUNK 2048
+struct JpgLdsSrc {
+  const unsigned char* g;
+  unsigned int* win;
+  int w0, end, lane;
+  __device__ int byte(int i) {
+    if ((unsigned int)(i - w0) >= (unsigned int)JPG_CHUNK) {
+      w0 = i & ~(JPG_CHUNK - 1);
+      __syncthreads();
+      for (int k = lane; k < JPG_CHUNK / 4; k += 64) {
+        const int o = w0 + k * 4;
+        win[k] = o < end ? *reinterpret_cast<const unsigned int*>(g + o) : 0u;
+      }
+      __syncthreads();
+    }
+    return reinterpret_cast<const unsigned char*>(win)[i - w0];
+  }
+};
+
+__global__ void __launch_bounds__(64) k_jpeg_entropy(const unsigned char* __restrict__ streams,
+                                                     const int* __restrict__ desc, const int* __restrict__ huff,
+                                                     unsigned char* __restrict__ ws, int* __restrict__ status) {
+  __shared__ int s_tab[6 * JPG_HUFF_WORDS];                  // the DC and AC table of each component
+  __shared__ unsigned int s_win[JPG_CHUNK / 4];
+  const int n = blockIdx.x;
+  const int* d = desc + (long)n * JPG_DESC_WORDS;
+  int st = d[JD_STATUS];
+  if (st == 0) {
+    const int nc = d[JD_NCOMP];
+    const int* dctab[3];
+    const int* actab[3];
+    for (int c = 0; c < 3; ++c) {
+      dctab[c] = s_tab + (2 * c) * JPG_HUFF_WORDS;
+      actab[c] = s_tab + (2 * c + 1) * JPG_HUFF_WORDS;
+      if (c < nc) {
+        const int* gd = huff + (long)d[JD_DC + c] * JPG_HUFF_WORDS;
+        const int* ga = huff + (long)d[JD_AC + c] * JPG_HUFF_WORDS;
+        for (int k = threadIdx.x; k < JPG_HUFF_WORDS; k += 64) {
+          s_tab[(2 * c) * JPG_HUFF_WORDS + k] = gd[k];
+          s_tab[(2 * c + 1) * JPG_HUFF_WORDS + k] = ga[k];
+        }
+      }
+    }
+    __syncthreads();
+    JpgWaveSink sink;
+    sink.coef = reinterpret_cast<int16_t*>(ws + (long)d[JD_WS] * JPG_WS_ALIGN);
+    sink.lane = threadIdx.x;
+    sink.nat = jpg_natural(threadIdx.x);
+    sink.c = 0;
+    JpgLdsSrc src;
+    src.g = streams + (long)d[JD_BASE] * 4;
+    src.win = s_win;
+    src.w0 = -JPG_CHUNK;
+    src.end = d[JD_END];
+    src.lane = threadIdx.x;
+    st = jpg_entropy(d, src, dctab, actab, sink);
+  }
+  if (threadIdx.x == 0) status[n] = st;
+}
+
+__global__ void __launch_bounds__(256) k_jpeg_idct(const int* __restrict__ desc, const int* __restrict__ qtabs,
+                                                   unsigned char* __restrict__ ws, const int* __restrict__ status) {
+  const int n = blockIdx.y;
+  if (status[n] != 0) return;
+  const int* d = desc + (long)n * JPG_DESC_WORDS;
+  JpgLayout L;
+  jpg_layout(d, L);
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= L.nblk) return;
+  // the component of block i, and its fields picked by comparison: indexing L's arrays with a run-time c would put
+  // the whole struct into scratch
+  const int c = i >= L.cbase[2] && L.ncomp == 3 ? 2 : (i >= L.cbase[1] && L.ncomp == 3 ? 1 : 0);
+  const long cbase = c == 2 ? L.cbase[2] : (c == 1 ? L.cbase[1] : L.cbase[0]);
+  const long pbase = c == 2 ? L.pbase[2] : (c == 1 ? L.pbase[1] : L.pbase[0]);
+  const int bw = c == 2 ? L.bw[2] : (c == 1 ? L.bw[1] : L.bw[0]);
+  const long j = i - cbase;
+  const int by = (int)(j / bw), bx = (int)(j - (long)by * bw);
+  unsigned char* base = ws + (long)d[JD_WS] * JPG_WS_ALIGN;
+  const long pitch = (long)bw * 8;
+  jpg_idct(reinterpret_cast<const int16_t*>(base) + i * 64, qtabs + (long)d[JD_QT + c] * 64,
+           base + pbase + (long)by * 8 * pitch + bx * 8, pitch);
+}
+
+// channels 3: R, G, B (B, G, R with swap_rb); channels 1: the Y plane.  A thread owns 4 pixels of a row; where the
+// image's offset and pitch are multiples of 4 they leave as dwords, and the bytes between the row and its pitch as 0.
+__global__ void __launch_bounds__(256) k_jpeg_store(const int* __restrict__ desc, const unsigned char* __restrict__ ws,
+                                                    unsigned char* __restrict__ dst, long dst_bytes,
+                                                    const long* __restrict__ meta, int channels, int swap_rb,
+                                                    int* __restrict__ status) {
+  const int n = blockIdx.y;
+  if (status[n] != 0) return;
+  const int* d = desc + (long)n * JPG_DESC_WORDS;
+  const int H = d[JD_H], W = d[JD_W];
+  const long* mt = meta + (long)n * 4;
+  const long off = mt[0], pitch = mt[3];
+  const long rowb = (long)W * channels;
+  // the destination rectangle is checked here, on the device, where meta_out lives: an image that does not fit is
+  // not written (every workgroup of the image sees the same values and leaves)
+  // (compared by subtraction: H <= 32767 and pitch < 2^31 keep the span below 2^46, and off <= dst_bytes)
+  if (off < 0 || off > dst_bytes || mt[1] != H || mt[2] != W || pitch < rowb || pitch > 0x7fffffffL ||
+      (long)(H - 1) * pitch + (((off | pitch) & 3) == 0 ? pitch : rowb) > dst_bytes - off) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) status[n] = JPG_ERR_OUTPUT;
+    return;
+  }
+  const int gw = (W + 3) / 4;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (long)gw * H) return;
+  const int y = (int)(g / gw), x0 = (int)(g - (long)y * gw) * 4;
+  JpgLayout L;
+  jpg_layout(d, L);
+  const unsigned char* base = ws + (long)d[JD_WS] * JPG_WS_ALIGN;
+  unsigned char px[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) px[e] = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (x0 + e < W) {
+      if (channels == 1) {
+        px[e] = base[L.pbase[0] + (long)y * (L.bw[0] * 8) + x0 + e];
+      } else {
+        int rgb[3];
+        jpg_pixel(d, L, base, x0 + e, y, rgb);
+        px[e * 3 + 0] = (unsigned char)rgb[swap_rb ? 2 : 0];
+        px[e * 3 + 1] = (unsigned char)rgb[1];
+        px[e * 3 + 2] = (unsigned char)rgb[swap_rb ? 0 : 2];
+      }
+    }
+  }
+  unsigned char* row = dst + off + (long)y * pitch;
+  const long b0 = (long)x0 * channels;
+  if (((off | pitch) & 3) == 0) {
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+      if (w < channels && b0 + w * 4 < pitch) {
+        *reinterpret_cast<unsigned int*>(row + b0 + w * 4) =
+            px[w * 4] | (px[w * 4 + 1] << 8) | (px[w * 4 + 2] << 16) | ((unsigned int)px[w * 4 + 3] << 24);
+      }
+    }
+    if (x0 + 4 >= W)                                         // the last group of the row: zeros up to the pitch
+      for (long p = b0 + channels * 4; p < pitch; p += 4) *reinterpret_cast<unsigned int*>(row + p) = 0u;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 12; ++e)
+      if (e < channels * 4 && b0 + e < rowb) row[b0 + e] = px[e];
+  }
+}
+
+extern "C" long msml_jpeg_workspace(int* desc, int N) {
+  if (!desc || N < 1) return 0;
+  long units = 0;
+  for (int n = 0; n < N; ++n) {
+    int* d = desc + (long)n * JPG_DESC_WORDS;
+    d[JD_WS] = 0;
+    if (d[JD_STATUS] != 0) continue;
+    if (jpg_desc_ok(d, 0x7fffffffffffL, 0x7fffffff, 0x7fffffff) != 1) return 0;
+    if (units > 0x7fffffffL) return 0;
+    JpgLayout L;
+    jpg_layout(d, L);
+    d[JD_WS] = (int)units;
+    units += L.bytes / JPG_WS_ALIGN;
+  }
+  return units * JPG_WS_ALIGN;
+}
+
+extern "C" int msml_jpeg_decode(const unsigned char* streams, long stream_bytes, const int* desc, const int* desc_host,
+                                const int* qtabs, int nq, const int* htabs, int nh, unsigned char* dst, long dst_bytes,
+                                const long* meta_out, int channels, int swap_rb, int* status, unsigned char* ws,
+                                long ws_bytes, int N, void* stream) {
+  MSML_CHECK(N >= 1 && N <= 65535, MSML_ERR_UNSUPPORTED, "jpeg_decode: N=%d outside 1..65535", N);
+  MSML_CHECK(channels == 1 || channels == 3, MSML_ERR_UNSUPPORTED, "jpeg_decode: channels=%d (1 or 3)", channels);
+  MSML_CHECK(streams && desc && desc_host && qtabs && htabs && dst && meta_out && status && ws, MSML_ERR_SHAPE,
+             "jpeg_decode: null pointer");
+  MSML_CHECK(((uintptr_t)streams & 3) == 0 && ((uintptr_t)desc & 3) == 0 && ((uintptr_t)qtabs & 3) == 0 &&
+                 ((uintptr_t)htabs & 3) == 0 && ((uintptr_t)dst & 3) == 0 && ((uintptr_t)status & 3) == 0 &&
+                 ((uintptr_t)meta_out & 7) == 0 && ((uintptr_t)ws & 15) == 0,
+             MSML_ERR_SHAPE, "jpeg_decode: streams, desc, tables, dst, status must be 4-byte, meta_out 8-byte, ws 16-byte "
+                             "aligned");
+  MSML_CHECK(stream_bytes % 4 == 0, MSML_ERR_SHAPE, "jpeg_decode: stream_bytes=%ld is not whole dwords", stream_bytes);
+  MSML_CHECK(stream_bytes >= 0 && dst_bytes >= 0 && ws_bytes >= 0 && nq >= 1 && nh >= 1, MSML_ERR_SHAPE,
+             "jpeg_decode: stream_bytes=%ld dst_bytes=%ld ws_bytes=%ld nq=%d nh=%d", stream_bytes, dst_bytes, ws_bytes,
+             nq, nh);
+  long units = 0, max_blk = 0, max_grp = 0;
+  for (int n = 0; n < N; ++n) {
+    const int* d = desc_host + (long)n * JPG_DESC_WORDS;
+    MSML_CHECK(jpg_desc_ok(d, stream_bytes, nq, nh) == 1, MSML_ERR_SHAPE, "jpeg_decode: descriptor %d is inconsistent", n);
+    if (d[JD_STATUS] != 0) continue;
+    MSML_CHECK(channels == 3 || d[JD_NCOMP] == 1, MSML_ERR_UNSUPPORTED,
+               "jpeg_decode: image %d has 3 components, channels=1 takes gray streams", n);
+    JpgLayout L;
+    jpg_layout(d, L);
+    MSML_CHECK(d[JD_WS] == units, MSML_ERR_SHAPE, "jpeg_decode: descriptor %d: workspace offset %d, not the %ld "
+               "msml_jpeg_workspace writes", n, d[JD_WS], units);
+    units += L.bytes / JPG_WS_ALIGN;
+    MSML_CHECK(units * JPG_WS_ALIGN <= ws_bytes, MSML_ERR_WORKSPACE, "jpeg_decode: workspace of %ld bytes is too small "
+               "(image %d ends at %ld)", ws_bytes, n, units * JPG_WS_ALIGN);
+    const long grp = (long)((d[JD_W] + 3) / 4) * d[JD_H];
+    max_blk = L.nblk > max_blk ? L.nblk : max_blk;
+    max_grp = grp > max_grp ? grp : max_grp;
+  }
+  k_jpeg_entropy<<<N, 64, 0, (hipStream_t)stream>>>(streams, desc, htabs, ws, status);
+  MSML_LAUNCH_OK("jpeg_entropy");
+  if (max_blk == 0) return MSML_OK;                          // only refused streams: their statuses are written
+  k_jpeg_idct<<<dim3(cdiv(max_blk, 256), N), 256, 0, (hipStream_t)stream>>>(desc, qtabs, ws, status);
+  MSML_LAUNCH_OK("jpeg_idct");
+  k_jpeg_store<<<dim3(cdiv(max_grp, 256), N), 256, 0, (hipStream_t)stream>>>(desc, ws, dst, dst_bytes, meta_out,
+                                                                             channels, swap_rb, status);
+  MSML_LAUNCH_OK("jpeg_store");
+  return MSML_OK;
+}

@@ -28,6 +28,7 @@ import threading
 import torch
 
 from ._lib import call
+from .jpeg import JpegBatch
 
 # "train": the asset-free mix {rect, ellipse, polygon, none}; "ms1m" / "casia": the reference's full mixes with the
 # texture occluders (load_dataset.py:155-163), which need an OccluderAtlas; "glasses" / "scarf" / "object": one class.
@@ -389,7 +390,11 @@ class DeviceLoaderX:
 
     p_mask > 0 (the reference: 0.2): the source yields (faces, masked, mask, label) or (faces, masked, mask, rows, label)
     -- the renders of the facial-mask samples, one per face or packed with rows[n] the render of face n (-1: none; see
-    mask_flags) -- and they go over on the side stream with the faces."""
+    mask_flags) -- and they go over on the side stream with the faces.
+
+    A source of compressed records (jpeg.RecordFaceSource) yields JpegBatch objects in place of the uint8 tensors; they
+    are decoded on the side stream in front of augment, and after every `__next__` `self.jpeg_status` is the int32 [B]
+    status tensor of the batch just returned (0 = decoded)."""
 
     def __init__(self, source, local_rank=0, seed=1, mode="train", lo=0, hi=36, flip=True, light=True,
                  want_ori=True, max_prefetch=6, atlas=None, gray=False, out_size=None, use_norm=True, p_mask=0.0):
@@ -399,6 +404,8 @@ class DeviceLoaderX:
         self.cfg = (seed, mode, lo, hi, flip, light, want_ori)
         self.out = (gray, out_size, use_norm)   # the reference's is_gray / out_size / use_norm (LightCNN: True, 128, False)
         self.p_mask = p_mask
+        self.jpeg_status = None              # JpegBatch sources: the status int32 [B] of the batch __next__ returned last
+        self._status = None
         self.max_prefetch = max_prefetch
         self.count = 0
         self.batch = None
@@ -419,16 +426,46 @@ class DeviceLoaderX:
         faces, label = host[0], host[-1]
         if self.p_mask > 0 and len(host) not in (4, 5):
             raise ValueError("p_mask > 0: the source must yield (faces, masked, mask[, rows], label)")
+        status = None
         with torch.cuda.stream(self.stream):
-            src = faces.to(device=self.local_rank, non_blocking=True)
-            lab = label.to(device=self.local_rank, non_blocking=True)
-            extra = ()
-            if self.p_mask > 0:                  # masked, mask and, when the renders are packed, rows
-                extra = tuple(t.to(device=self.local_rank, non_blocking=True) for t in host[1:-1])
-            img, msk, ori, _ = augment(src, seed, self.count * faces.shape[0], mode, lo, hi, flip, light, want_ori,
+            if isinstance(faces, JpegBatch):     # compressed records (jpeg.RecordFaceSource): decoded here, on the side stream
+                src, extra, status = self._decode(host)
+                lab = label.to(device=self.local_rank, non_blocking=True)
+            else:
+                src = faces.to(device=self.local_rank, non_blocking=True)
+                lab = label.to(device=self.local_rank, non_blocking=True)
+                extra = ()
+                if self.p_mask > 0:              # masked, mask and, when the renders are packed, rows
+                    extra = tuple(t.to(device=self.local_rank, non_blocking=True) for t in host[1:-1])
+            img, msk, ori, _ = augment(src, seed, self.count * src.shape[0], mode, lo, hi, flip, light, want_ori,
                                        self.atlas, *self.out, self.p_mask, *extra)
         self.count += 1
         self.batch = (img, msk, ori, lab, src) + extra
+        self._status = status                # of self.batch, and its last element: __next__ stream-records it with the rest
+        if status is not None:
+            self.batch += (status,)
+
+    def _decode(self, host):
+        """host: (JpegBatch, label) or (JpegBatch, JpegBatch of mask_out, JpegBatch of mask, rows, label) -> the faces
+        uint8 [B, H, W, 3], (masked, mask, rows) or (), and the batch's status int32 [B] on the device: 0, or why
+        face n -- or, where that is 0, the render rows[n] points at -- was not decoded (jpeg.STATUS).  A record the
+        parser refused, face or render, is an error here, before anything is launched."""
+        from . import jpeg
+        faces = host[0]
+        bad = faces.status.nonzero()[0]
+        if bad.size:
+            raise ValueError("DeviceLoaderX: record %d of the batch: %s" % (bad[0], faces.descriptors[bad[0]].reason))
+        size = faces.sizes[0]
+        dev = torch.device("cuda", self.local_rank)
+        src, status = jpeg.decode_batch(faces, size=size, strict=False, device=dev)
+        extra = ()
+        if self.p_mask > 0:
+            masked, mask, rst = jpeg.decode_renders(host[1], host[2], size, dev)
+            rows = host[3].to(device=dev, non_blocking=True)
+            extra = (masked, mask, rows)
+            of_face = torch.where(rows >= 0, rst[rows.clamp(0, rst.shape[0] - 1).long()], torch.zeros_like(status))
+            status = torch.where(status != 0, status, of_face)
+        return src, extra, status
 
     def __next__(self):
         cur = torch.cuda.current_stream()
@@ -439,5 +476,8 @@ class DeviceLoaderX:
         for t in batch:                      # produced on the side stream, consumed on this one
             if t is not None:
                 t.record_stream(cur)
+        # the status of THIS batch (0 = decoded; see _decode), ordered on the current stream like its images; reading
+        # it on the host is the caller's synchronisation, the loader makes none
+        self.jpeg_status = self._status
         self.preload()
         return batch[:4]

@@ -2,7 +2,8 @@
 
 Eval forward of ires18-MSML (f32 parity mode) on 2 synthetic occluded faces: embeddings within
 1e-3 rel of the oracle, occlusion-mask indices bit-exact; then one bf16 training step
-(forward + backward + fused clip/SGD) to exercise the backward kernels."""
+(forward + backward + fused clip/SGD) to exercise the backward kernels; then one fixture JPEG decoded on the device,
+bit-exact with the pixels Pillow recorded."""
 import torch
 
 
@@ -40,5 +41,19 @@ def run():
     opt.step()
     torch.cuda.synchronize()
     assert torch.isfinite(loss).item() and torch.isfinite(opt.grad_norm()).item()
+    _jpeg()
     print("smoke ok: eval feature rel err %.2e, masks bit-exact, train loss %.4f grad-norm %.3f"
           % (err, loss.item(), opt.grad_norm().item()))
+
+
+def _jpeg():
+    import os
+    import numpy as np
+    from msml_amd import jpeg
+    z = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden",
+                             "g15_jpeg.npz"), allow_pickle=False)
+    i = [str(s) for s in z["names"]].index("face0_112x112_420_q95_r3")
+    data = z["streams"][z["stream_offsets"][i]:z["stream_offsets"][i + 1]].tobytes()
+    want = z["pixels"][z["pixel_offsets"][i]:z["pixel_offsets"][i + 1]].reshape(112, 112, 3)
+    got = jpeg.decode_batch([data], size=(112, 112))[0].cpu().numpy()
+    assert np.array_equal(got, want), "JPEG decode differs from libjpeg's pixels"

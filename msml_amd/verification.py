@@ -365,3 +365,30 @@ def occlusion_sweep(model, src, issame, levels=LEVELS, repeats=10, seed=1, batch
         res["roc_acc"].append(rocs)
         res["tarfar_runs"].append(np.stack(runs))
     return res
+
+
+@torch.no_grad()
+def load_bin(path, image_size, device="cuda"):
+    """eval/verification.py:202-236: read a verification `.bin` (a pickle of (JPEG byte strings, issame)) and decode it
+    on the device (jpeg.decode_batch, bit-exact with mx.image.imdecode) -> ([data, flipped], issame): two f32
+    [2P, 3, H, W] tensors on the device holding the pixel values 0..255 as the reference does, the second mirrored
+    along the width.  image_size: (H, W).  A decoded width other than image_size[0] raises NotImplementedError: the
+    reference then calls mx.image.resize_short, a cv2 resize that is not restated here."""
+    import pickle
+    from . import jpeg
+    with open(path, "rb") as f:
+        try:
+            bins, issame = pickle.load(f)
+        except UnicodeDecodeError:
+            f.seek(0)
+            bins, issame = pickle.load(f, encoding="bytes")
+    n = len(issame) * 2
+    batch = jpeg.pack_jpegs([bytes(b) for b in bins[:n]])
+    for i, d in enumerate(batch.descriptors):
+        if d.status == 0 and d.width != image_size[0]:
+            raise NotImplementedError("load_bin: image %d is %d pixels wide, not %d: the reference resizes it with "
+                                      "mx.image.resize_short (cv2), which is not restated" % (i, d.width, image_size[0]))
+    faces = jpeg.decode_batch(batch, size=(int(image_size[0]), int(image_size[1])), order="rgb", strict=True,
+                              device=device)
+    data = faces.permute(0, 3, 1, 2).float().contiguous()
+    return [data, data.flip(3).contiguous()], issame
