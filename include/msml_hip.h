@@ -976,6 +976,42 @@ int msml_jpeg_decode(const unsigned char* streams, long stream_bytes, const int*
                      const long* meta_out, int channels, int swap_rb, int* status, unsigned char* ws, long ws_bytes,
                      int N, void* stream);
 
+/* ---------------------------------------------------------------- baseline JPEG encoding -------------------------
+ * PIL.Image.save on the device (eval/align_dataset.py:52-75, iterate_pku.py) and the JPEG inside mx.recordio.pack_img
+ * (datasets/3d_tools/cvt_casia_webface.py:57, cvt_casia_webface_masked.py:108-114): N images of any sizes, samplings,
+ * qualities and restart intervals in one call, the bytes libjpeg writes for Pillow (JDCT_ISLOW, the standard Huffman
+ * tables, no optimisation pass).  The host builds quantisation tables and header bytes (msml_amd/jpeg.py); the device
+ * does the rest.  Integer arithmetic; the only atomics are integer ORs into a zeroed buffer: two runs give the same
+ * bytes.  The mirror of msml_jpeg_decode.
+ *
+ *   src / meta [N][4] int64 (device) = byte offset, H, W, row pitch of each source, as msml_align_warp takes them (a
+ *     contiguous [N][H][W][channels] tensor is the special case); channels 3 (R, G, B; B, G, R with swap_rb) or 1 (gray
+ *     descriptors only).  A 3-channel source with a gray descriptor stores Y.
+ *   desc / desc_host [N][12] int32: the same descriptors on the device and on the HOST (csrc/jpeg_enc_core.h names
+ *     the words: sampling 0 gray / 1 4:4:4 / 2 4:2:2 / 3 4:2:0, H, W, the luma and chroma table selectors, the restart
+ *     interval in MCUs, the header's offset and length in `headers`, the workspace offset).
+ *   qtabs [nq][64] int32: quantisation tables in natural order; headers: the packed header bytes (SOI .. SOS).
+ *   dst / out_meta [N][2] int64 (device) = byte offset and capacity of each image's slot; length [N] int32: the bytes
+ *     written (0 for an image with a status).
+ *   status [N] int32: 0, 1 a meta row that is not this image inside src, 2 a slot outside dst or too small.  Such an
+ *     image writes nothing outside its own workspace and slot; the other images are unaffected, for ANY input bytes.
+ *   msml_jpeg_encode_workspace(desc, N): on the HOST descriptors, writes each image's workspace offset into its
+ *     descriptor and returns the bytes msml_jpeg_encode needs (0 for a descriptor it would refuse).
+ *   msml_jpeg_encode_bound(H, W, sampling, restart, header_bytes): a slot capacity no stream can exceed (0 for
+ *     arguments outside the range): at most 20 bits of DC and 63 x 26 bits of AC per block (rounded up to 208 bytes),
+ *     doubled for stuffing, plus two bytes per restart interval, the header and EOI.  Typical output (photographs at
+ *     quality 75-97) is 20-40 times smaller than this bound.
+ *   MSML_ERR_UNSUPPORTED before any launch for N outside 1..65535, channels other than 1 or 3, a size outside
+ *   1..32767, another sampling, channels 1 with a colour sampling; MSML_ERR_SHAPE for null or misaligned pointers (4
+ *   bytes; meta, out_meta 8, ws 16) and an inconsistent descriptor; MSML_ERR_WORKSPACE for a workspace that is too
+ *   small. */
+long msml_jpeg_encode_workspace(int* desc, int N);
+long msml_jpeg_encode_bound(int H, int W, int sampling, int restart, int header_bytes);
+int msml_jpeg_encode(const unsigned char* src, long src_bytes, const long* meta, int channels, int swap_rb,
+                     const int* desc, const int* desc_host, const int* qtabs, int nq, const unsigned char* headers,
+                     long header_bytes, unsigned char* dst, long dst_bytes, const long* out_meta, int* length,
+                     int* status, unsigned char* ws, long ws_bytes, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

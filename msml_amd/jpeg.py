@@ -597,3 +597,373 @@ def decode_renders(mask_out, mask, size, device="cuda"):
         rgb = rgb.to(torch.int32)
         m = ((rgb[..., 0] * 19595 + rgb[..., 1] * 38470 + rgb[..., 2] * 7471 + 32768) >> 16).to(torch.uint8)
     return masked, m, torch.where(st != 0, st, st2)
+
+
+# ---------------------------------------------------------------------------------------------------- encoding
+# Baseline JPEG encoding on the device, byte for byte what libjpeg writes with Pillow's save() options (csrc/jpeg_enc.hip,
+# csrc/jpeg_enc_core.h): PIL.Image.save of eval/align_dataset.py:52-75 and iterate_pku.py, and the entropy-coded data of
+# mx.recordio.pack_img in datasets/3d_tools/cvt_casia_webface.py:57 and cvt_casia_webface_masked.py:108-114.  pack_img
+# goes through cv2.imencode: the same library with the same defaults, so its scan should equal Pillow's at the same
+# quality and sampling, but its header bytes were never compared -- byte equality is claimed with Pillow only.
+ENC_DESC_WORDS = 12
+(JE_SAMP, JE_H, JE_W, JE_QT, JE_RI, JE_HOFF, JE_HLEN, JE_WS) = 0, 1, 2, 3, 5, 6, 7, 8
+SAMPLINGS = {"gray": 0, "444": 1, "422": 2, "420": 3}
+ENCODE_STATUS = {0: "ok", 1: "the meta row is not this image inside the source buffer",
+                 2: "the slot is outside the output buffer or too small for the stream"}
+
+# Annex K.1 / K.2, natural order
+_BASE_Q = (np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17,
+                     22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78,
+                     87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99], np.int64),
+           np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66,
+                     99, 99, 99, 99, 99, 99] + [99] * 32, np.int64))
+# Annex K.3 - K.6: (class, id) -> (counts [16], symbols)
+_AC_LUMA = bytes.fromhex(
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a"
+    "434445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9"
+    "aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")
+_AC_CHROMA = bytes.fromhex(
+    "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a3536373839"
+    "3a434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7"
+    "a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")
+STD_HUFFMAN = {
+    (0, 0): ([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0], bytes(range(12))),
+    (0, 1): ([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0], bytes(range(12))),
+    (1, 0): ([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125], _AC_LUMA),
+    (1, 1): ([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119], _AC_CHROMA),
+}
+
+
+def quant_tables(quality):
+    """libjpeg's jpeg_set_quality(quality, force_baseline=TRUE): (luma, chroma) int32 [64] in natural order."""
+    q = int(quality)
+    if not 1 <= q <= 100:
+        raise ValueError("quality must be 1..100, got %r" % (quality,))
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(np.clip((b * scale + 50) // 100, 1, 255).astype(np.int32) for b in _BASE_Q)
+
+
+def _segment(marker, body):
+    return bytes((0xFF, marker)) + struct.pack(">H", len(body) + 2) + body
+
+
+def build_header(height, width, sampling, qtabs, restart=0):
+    """SOI .. SOS as libjpeg writes them for Pillow (jcmarker.c): APP0 JFIF 1.01 with density 1 x 1 and no unit, one DQT
+    per table, SOF0, one DHT per standard table (DC 0, AC 0, DC 1, AC 1; a gray stream has the first two), DRI when a
+    restart interval is set, SOS.  sampling: a key of SAMPLINGS; qtabs: (luma, chroma) in natural order."""
+    s = SAMPLINGS[sampling] if isinstance(sampling, str) else int(sampling)
+    nc = 1 if s == 0 else 3
+    out = b"\xff\xd8" + _segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for t in range(2 if nc == 3 else 1):
+        out += _segment(0xDB, bytes((t,)) + bytes(int(v) for v in np.asarray(qtabs[t])[ZIGZAG]))
+    comps = [(1, (0x11, 0x11, 0x21, 0x22)[s], 0)] + ([(2, 0x11, 1), (3, 0x11, 1)] if nc == 3 else [])
+    out += _segment(0xC0, struct.pack(">BHHB", 8, height, width, nc) + b"".join(bytes(c) for c in comps))
+    for th in range(2 if nc == 3 else 1):
+        for tc in (0, 1):
+            counts, symbols = STD_HUFFMAN[(tc, th)]
+            out += _segment(0xC4, bytes(((tc << 4) | th,)) + bytes(counts) + symbols)
+    if restart:
+        out += _segment(0xDD, struct.pack(">H", restart))
+    scan = bytes((nc,)) + b"".join(bytes((c[0], 0x11 * c[2])) for c in comps) + b"\x00\x3f\x00"
+    return out + _segment(0xDA, scan)
+
+
+class EncodePlan:
+    """Everything msml_jpeg_encode reads besides the pixels, built on the host from sizes and options: desc int32
+    [N, 12] (pinned), qtabs int32 [nq, 64] (each distinct table once), headers uint8 (each distinct header once),
+    bounds int64 [N] = msml_jpeg_encode_bound of every image rounded up to 4, ws_bytes, and what the decoder needs to read
+    the streams back (recompress)."""
+
+    def __init__(self, sizes, quality=75, sampling="420", restart=0):
+        n = len(sizes)
+        if n == 0:
+            raise ValueError("encode: needs at least one image")
+
+        def per_image(v, name):
+            if isinstance(v, (str, int, np.integer)):
+                return [v] * n
+            v = list(v)
+            if len(v) != n:
+                raise ValueError("encode: %s has %d values for %d images" % (name, len(v), n))
+            return v
+
+        quality, sampling, restart = per_image(quality, "quality"), per_image(sampling, "sampling"), per_image(restart, "restart")
+        self.n, self.sizes = n, [(int(h), int(w)) for h, w in sizes]
+        self.desc = _pinned((n, ENC_DESC_WORDS), torch.int32)
+        dn = self.desc.numpy()
+        dn[...] = 0
+        qidx, qtabs, hidx, headers, hoff = {}, [], {}, [], 0
+        self.bounds = np.zeros(n, np.int64)
+        for i, ((h, w), q, s, r) in enumerate(zip(self.sizes, quality, sampling, restart)):
+            if s not in SAMPLINGS:
+                raise ValueError("encode: sampling must be one of %s, got %r" % (sorted(SAMPLINGS), s))
+            q, r = int(q), int(r)
+            if not (1 <= h <= 32767 and 1 <= w <= 32767):
+                raise ValueError("encode: image %d is %d x %d, sizes must be 1..32767" % (i, h, w))
+            if not 0 <= r <= 65535:
+                raise ValueError("encode: restart must be 0..65535 MCUs, got %d" % r)
+            if q not in qidx:
+                qidx[q] = len(qtabs)
+                qtabs.extend(quant_tables(q))
+            key = (h, w, s, q, r)
+            if key not in hidx:
+                hb = build_header(h, w, s, quant_tables(q), r)
+                hidx[key] = (hoff, len(hb))
+                headers.append(hb)
+                hoff += len(hb)
+            dn[i, JE_SAMP], dn[i, JE_H], dn[i, JE_W], dn[i, JE_RI] = SAMPLINGS[s], h, w, r
+            dn[i, JE_QT], dn[i, JE_QT + 1] = qidx[q], qidx[q] + 1
+            dn[i, JE_HOFF], dn[i, JE_HLEN] = hidx[key]
+            self.bounds[i] = (value("msml_jpeg_encode_bound", h, w, SAMPLINGS[s], r, hidx[key][1]) + 3) & ~3
+        self.qtabs = _pinned((len(qtabs), 64), torch.int32)
+        self.qtabs.numpy()[...] = np.stack(qtabs)
+        hb = b"".join(headers)
+        self.headers = _pinned((len(hb) + 3) & ~3, torch.uint8)
+        self.headers.numpy()[:len(hb)] = np.frombuffer(hb, np.uint8)
+        self.headers.numpy()[len(hb):] = 0
+        self.ws_bytes = value("msml_jpeg_encode_workspace", self.desc.data_ptr(), n)
+        if self.ws_bytes <= 0:
+            raise RuntimeError("msml_jpeg_encode_workspace refused the descriptors")
+        self._dev = None
+        self._decode = {}
+
+    def to_device(self, device="cuda"):
+        if self._dev is None or self._dev[0].device != torch.device(device):
+            self._dev = tuple(t.to(device, non_blocking=True) for t in (self.desc, self.qtabs, self.headers))
+        return self._dev
+
+    def decode_batch_of(self, buf, slots):
+        """The JpegBatch that decodes the streams this plan's encode wrote into `buf` at `slots` (numpy [N][2], offsets
+        multiples of 4), built without reading anything back: the header length is known, and the end of the stream is
+        given as the end of the slot, which msml_jpeg_decode allows (it stops at the EOI marker after the last MCU)."""
+        key = slots.tobytes()
+        if key not in self._decode:
+            n = self.n
+            en = self.desc.numpy()
+            desc = _pinned((n, DESC_WORDS), torch.int32)
+            dn = desc.numpy()
+            dn[...] = 0
+            lookups = [huffman_lookup(*STD_HUFFMAN[k]) for k in ((0, 0), (1, 0), (0, 1), (1, 1))]
+            for i in range(n):
+                s = int(en[i, JE_SAMP])
+                hm, vm = (2 if s >= 2 else 1), (2 if s == 3 else 1)
+                h, w = self.sizes[i]
+                dn[i, JD_BASE], dn[i, JD_BEGIN], dn[i, JD_END] = slots[i, 0] // 4, en[i, JE_HLEN], slots[i, 1]
+                dn[i, JD_H], dn[i, JD_W], dn[i, JD_NCOMP], dn[i, JD_HMAX], dn[i, JD_VMAX] = h, w, 1 if s == 0 else 3, hm, vm
+                dn[i, JD_QT:JD_QT + 3] = en[i, JE_QT], en[i, JE_QT + 1], en[i, JE_QT + 1]
+                dn[i, JD_DC:JD_DC + 3] = 0, 2, 2
+                dn[i, JD_AC:JD_AC + 3] = 1, 3, 3
+                dn[i, JD_RI] = en[i, JE_RI]
+                dn[i, JD_MCUX], dn[i, JD_MCUY] = -(-w // (8 * hm)), -(-h // (8 * vm))
+            ht = _pinned((4, HUFF_WORDS), torch.int32)
+            ht.numpy()[...] = np.stack(lookups)
+            ws_bytes = value("msml_jpeg_workspace", desc.data_ptr(), n)
+            if ws_bytes <= 0:
+                raise RuntimeError("msml_jpeg_workspace refused the descriptors")
+            if len(self._decode) >= 4:
+                self._decode.clear()
+            self._decode[key] = (desc, ht, ws_bytes)
+        desc, ht, ws_bytes = self._decode[key]
+        return JpegBatch(buf, desc, self.qtabs, ht, None, ws_bytes)
+
+
+_PLANS = {}
+
+
+def _plan(sizes, quality, sampling, restart):
+    """EncodePlan, remembered for a uniform batch with scalar options (what a loop over batches of crops asks for)."""
+    scalar = all(isinstance(v, (str, int, np.integer)) for v in (quality, sampling, restart))
+    if scalar and len(set(sizes)) == 1:
+        key = (len(sizes), sizes[0], int(quality), sampling, int(restart))
+        if key not in _PLANS:
+            if len(_PLANS) >= 16:
+                _PLANS.clear()
+            _PLANS[key] = EncodePlan(sizes, quality, sampling, restart)
+        return _PLANS[key]
+    return EncodePlan(sizes, quality, sampling, restart)
+
+
+class EncodedBatch:
+    """encode_batch's result, all on the device: buf uint8 (the slots), slots int64 [N][2] = byte offset and capacity of
+    each image's slot (slots_host: the same in numpy), length int32 [N] (0 for an image that failed), status int32 [N]
+    (ENCODE_STATUS).  Image n is buf[slots[n, 0] : slots[n, 0] + length[n]]."""
+
+    def __init__(self, buf, slots, slots_host, length, status, plan):
+        self.buf, self.slots, self.slots_host, self.length, self.status, self.plan = buf, slots, slots_host, length, status, plan
+
+    def __len__(self):
+        return self.length.shape[0]
+
+    def to_bytes(self, strict=True):
+        """-> a list of N byte strings.  One device-to-host copy (the slots, the lengths and the statuses together) for
+        which the host waits.  strict: ValueError naming the first image whose status is not 0; otherwise that image's
+        string is empty."""
+        n = len(self)
+        tail = torch.stack([self.length, self.status]).view(torch.uint8).reshape(-1)
+        host = torch.cat([self.buf.reshape(-1), tail]).cpu().numpy()
+        ls = host[self.buf.numel():].view(np.int32).reshape(2, n)
+        if strict:
+            bad = np.flatnonzero(ls[1])
+            if bad.size:
+                i = int(bad[0])
+                raise ValueError("encode: image %d: %s (status %d)" % (i, ENCODE_STATUS.get(int(ls[1, i]), "?"), ls[1, i]))
+        return [host[o:o + l].tobytes() for o, l in zip(self.slots_host[:, 0], ls[0])]
+
+
+def _source(images, channels, device):
+    """-> (src uint8 flat on the device, meta int64 numpy [N][4] or None for a contiguous tensor, sizes, channels)."""
+    if isinstance(images, (tuple, list)) and len(images) == 2 and isinstance(images[0], torch.Tensor) and images[0].dim() == 1:
+        buf, meta = images
+        meta = np.ascontiguousarray(meta.cpu().numpy() if isinstance(meta, torch.Tensor) else meta, dtype=np.int64)
+        if buf.dtype != torch.uint8 or meta.ndim != 2 or meta.shape[1] != 4:
+            raise ValueError("encode: the packed form is (uint8 buffer, int64 meta [N][4])")
+        return buf.to(device).contiguous(), meta, [(int(h), int(w)) for h, w in meta[:, 1:3]], channels
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() not in (3, 4) or \
+            (images.dim() == 4 and images.shape[3] != 3):
+        raise ValueError("encode: images must be a uint8 [N, H, W, 3] or [N, H, W] tensor, or the packed (buf, meta)")
+    images = images.to(device).contiguous()
+    return images, None, [(int(images.shape[1]), int(images.shape[2]))] * images.shape[0], 3 if images.dim() == 4 else 1
+
+
+@torch.no_grad()
+def encode_into(plan, src, meta, dst, slots, channels=3, order="rgb", length=None, status=None, ws=None):
+    """msml_jpeg_encode with the caller's buffers, on the current stream.  plan: an EncodePlan; src: uint8 on the
+    device; meta: int64 [N][4] on the device = byte offset, H, W, pitch of each source; dst: uint8 on the device; slots:
+    int64 [N][2] on the device = byte offset and capacity of each image's slot.  length / status int32 [N] and ws (at
+    least plan.ws_bytes) are allocated when None.  -> (length, status).  The device checks every meta row against src
+    and every slot against dst: an image that does not fit gets a status and length 0 and writes nothing outside its slot."""
+    n = plan.n
+    device = dst.device
+    for t, shape, name in ((meta, (n, 4), "meta"), (slots, (n, 2), "slots")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != shape or t.device != device or \
+                not t.is_contiguous():
+            raise ValueError("encode_into: %s must be a contiguous int64 %s tensor on %s" % (name, list(shape), device))
+    if order not in ("rgb", "bgr"):
+        raise ValueError("encode_into: order must be 'rgb' or 'bgr'")
+    desc, qtabs, headers = plan.to_device(device)
+    if length is None:
+        length = torch.empty(n, dtype=torch.int32, device=device)
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=device)
+    if ws is None:
+        ws = torch.empty(plan.ws_bytes, dtype=torch.uint8, device=device)
+    call("msml_jpeg_encode", src, src.numel(), meta, channels, 1 if order == "bgr" else 0, desc, plan.desc.data_ptr(),
+         qtabs, qtabs.shape[0], headers, headers.numel(), dst, dst.numel(), slots, length, status, ws, ws.numel(), n)
+    return length, status
+
+
+@torch.no_grad()
+def encode_batch(images, quality=75, sampling="420", restart=0, order="rgb", device="cuda", channels=3, slot_bytes=None):
+    """Encode N images on the device to baseline JPEG, the bytes PIL.Image.save(quality=, subsampling=,
+    restart_marker_blocks=) writes; the defaults are those of a bare save().  -> EncodedBatch.  No synchronisation.
+
+    images: uint8 [N, H, W, 3], or [N, H, W] (one channel; sampling becomes "gray" unless given per image), or the packed
+    (buf, meta) of ijb.pack_images / decode_batch with `channels` bytes per pixel.  quality (1..100), sampling ("420",
+    "422", "444", "gray") and restart (MCUs per restart interval, 0 = none) are scalars or one value per image.  order
+    "bgr": the sources are B, G, R (cv2).  A 3-channel source with sampling "gray" stores libjpeg's Y, which is what
+    convert("L") gives.  slot_bytes: the capacity of every slot; the default is msml_jpeg_encode_bound, which no stream
+    can exceed and which is 20-40 times what a photograph takes, so a caller that knows its data may pass less (an image
+    that does not fit gets status 2)."""
+    src, meta, sizes, channels = _source(images, channels, device)
+    if channels == 1 and isinstance(sampling, str):
+        sampling = "gray"
+    plan = _plan(sizes, quality, sampling, restart)
+    n = plan.n
+    if channels == 1 and (plan.desc.numpy()[:, JE_SAMP] != 0).any():
+        raise ValueError("encode: one-channel sources take sampling 'gray' only")
+    if meta is None:
+        h, w = sizes[0]
+        meta_dev = _uniform_meta(n, h, w, channels, src.device)
+    else:
+        meta_dev = torch.from_numpy(meta).to(src.device)
+    caps = plan.bounds if slot_bytes is None else np.full(n, (int(slot_bytes) + 3) & ~3, np.int64)
+    slots = np.empty((n, 2), np.int64)
+    slots[:, 1] = caps
+    slots[:, 0] = np.cumsum(caps) - caps
+    dst = torch.empty(int(caps.sum()), dtype=torch.uint8, device=src.device)
+    slots_dev = torch.from_numpy(slots).to(src.device)
+    length, status = encode_into(plan, src.reshape(-1), meta_dev, dst, slots_dev, channels, order)
+    return EncodedBatch(dst, slots_dev, slots, length, status, plan)
+
+
+@torch.no_grad()
+def recompress(images, quality=75, sampling="420", order="rgb", device="cuda"):
+    """Encode, then decode, on the device: the pixels Image.open(path) gives after Image.save(path, quality=,
+    subsampling=) -- what eval/qeval_folder.py reads after eval/align_dataset.py:52-75 saved the crops.  images: uint8
+    [N, H, W, 3] or [N, H, W]; the same shape comes back, channels in the order they came in.
+
+    Nothing is read back and the host does not wait: the decoder's descriptors are known on the host except for the end
+    of each stream, and msml_jpeg_decode's contract allows trailing bytes (it stops at the marker after the last MCU),
+    so the end of the slot is passed instead of `length`."""
+    if not isinstance(images, torch.Tensor) or images.dim() not in (3, 4):
+        raise ValueError("recompress: images must be a uint8 [N, H, W, 3] or [N, H, W] tensor")
+    enc = encode_batch(images, quality, sampling, 0, order, device)
+    batch = enc.plan.decode_batch_of(enc.buf, enc.slots_host)
+    n, h, w = images.shape[:3]
+    channels = 3 if images.dim() == 4 else 1
+    out = torch.empty(tuple(images.shape), dtype=torch.uint8, device=enc.buf.device)
+    decode_into(batch, out, _uniform_meta(n, h, w, channels, out.device), channels, order)
+    return out
+
+
+class RecordWriter:
+    """The writing twin of RecordFile: MXNet indexed RecordIO (mx.recordio.MXIndexedRecordIO(idx, rec, 'w') + pack)
+    without mxnet.  A record is uint32 magic, uint32 length, the payload padded with zeros to 4 bytes; the index holds
+    `key\\toffset` lines.  dmlc's writer splits a payload that holds the magic word at a 4-byte-aligned offset into
+    continued parts, which RecordFile does not read (and no mxnet was at hand to check a split against): such a payload is
+    a ValueError naming the key, and nothing is written for it."""
+
+    def __init__(self, rec_path, idx_path):
+        self._f = open(rec_path, "wb")
+        self._idx = open(idx_path, "w")
+        self.keys = []
+
+    @staticmethod
+    def pack(header, payload):
+        """header (flag, label, id, id2) as mx.recordio.IRHeader: a number as label gives flag 0; a sequence of labels gives
+        flag = their count, label 0 and the float32 labels in front of the payload."""
+        flag, label, id1, id2 = header
+        if isinstance(label, (int, float, np.integer, np.floating)):
+            return struct.pack("<IfQQ", 0, float(label), int(id1), int(id2)) + bytes(payload)
+        label = np.asarray(label, dtype="<f4").reshape(-1)
+        return struct.pack("<IfQQ", label.size, 0.0, int(id1), int(id2)) + label.tobytes() + bytes(payload)
+
+    def write_idx(self, key, header, payload=None):
+        """Write record `key`: pack(header, payload), or `header` itself when payload is None (already packed)."""
+        data = bytes(header) if payload is None else self.pack(header, payload)
+        if len(data) >= 1 << 29:
+            raise ValueError("record %d: %d bytes do not fit one RecordIO record" % (key, len(data)))
+        words = np.frombuffer(data[:len(data) & ~3], dtype="<u4")
+        if (words == RECORD_MAGIC).any():
+            raise ValueError("record %d: the payload holds the RecordIO magic word at a 4-byte-aligned offset; it would be "
+                             "written as a continued record, which is unsupported" % key)
+        self._idx.write("%d\t%d\n" % (key, self._f.tell()))
+        self._f.write(struct.pack("<II", RECORD_MAGIC, len(data)) + data + b"\x00" * (-len(data) % 4))
+        self.keys.append(int(key))
+
+    def close(self):
+        self._f.close()
+        self._idx.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def write_faces(writer, encoded, labels, first_key=1, header0=None):
+    """What datasets/3d_tools/cvt_casia_webface.py:40-60 does with a batch: record first_key + n holds IRHeader(0,
+    labels[n], 0, 0) and the JPEG stream of image n (one synchronising copy, EncodedBatch.to_bytes).  header0 = (count,
+    classes): also write record 0 as that script's lines 31-37 do, with the labels (count + 1, classes) and id 1, which is
+    what load_dataset.py:51-57 (and RecordFile) read the number of samples from; its image (a PNG of zeros there, never
+    decoded) is left empty.  -> the next free key."""
+    streams = encoded.to_bytes() if isinstance(encoded, EncodedBatch) else list(encoded)
+    labels = [int(v) for v in (labels.tolist() if isinstance(labels, (torch.Tensor, np.ndarray)) else labels)]
+    if len(labels) != len(streams):
+        raise ValueError("write_faces: %d labels for %d images" % (len(labels), len(streams)))
+    if header0 is not None:
+        writer.write_idx(0, (0, [header0[0] + 1, header0[1]], 1, 0), b"")
+    for k, (s, label) in enumerate(zip(streams, labels)):
+        writer.write_idx(first_key + k, (0, label, 0, 0), s)
+    return first_key + len(streams)

@@ -57,3 +57,10 @@ def _jpeg():
     want = z["pixels"][z["pixel_offsets"][i]:z["pixel_offsets"][i + 1]].reshape(112, 112, 3)
     got = jpeg.decode_batch([data], size=(112, 112))[0].cpu().numpy()
     assert np.array_equal(got, want), "JPEG decode differs from libjpeg's pixels"
+    z = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden",
+                             "g16_jpeg_enc.npz"), allow_pickle=False)
+    i = [str(s) for s in z["names"]].index("uniform0_112x112_420_q75_r0")
+    src = z["sources"][z["source_offsets"][i]:z["source_offsets"][i + 1]].reshape(1, 112, 112, 3)
+    want = z["streams"][z["stream_offsets"][i]:z["stream_offsets"][i + 1]].tobytes()
+    import torch
+    assert jpeg.encode_batch(torch.from_numpy(src).cuda()).to_bytes() == [want], "JPEG encode differs from libjpeg's bytes"
