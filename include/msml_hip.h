@@ -1012,6 +1012,42 @@ int msml_jpeg_encode(const unsigned char* src, long src_bytes, const long* meta,
                      long header_bytes, unsigned char* dst, long dst_bytes, const long* out_meta, int* length,
                      int* status, unsigned char* ws, long ws_bytes, int N, void* stream);
 
+/* ---------------------------------------------------------------- PNG decoding -----------------------------------
+ * PIL.Image.open(f).convert(mode) on the device (eval/qeval_folder.py:43-49, eval/align_dataset.py:44,
+ * datasets/augment/rand_occ.py:345-366): N non-interlaced PNG streams of 1 / 2 / 4 / 8-bit samples, of any sizes and
+ * colour types, in one call, the uint8 pixels Pillow gives for mode L / RGB / RGBA.  The host walks the chunks only
+ * (msml_amd/png.py); the device inflates (zlib wrapper, stored / fixed / dynamic blocks, tables built on the device),
+ * undoes the row filters and expands the samples.  Integer arithmetic, no global atomics, one writer per byte: two
+ * runs give the same bits.  The mirror of msml_jpeg_decode; every argument it shares means the same.
+ *
+ *   streams: per image its IDAT payloads back to back (one zlib stream) at dword offset desc[n][0]; stream_bytes a
+ *     multiple of 4 (aligned dword reads, none past the dword of a stream's last byte).
+ *   desc / desc_host [N][16] int32: the same descriptors on the device and on the HOST (csrc/png_core.h names the
+ *     words: stream range, H, W, bit depth, colour type, palette index, the parser's status, workspace offset, tRNS
+ *     colour key).  The library checks desc_host before it launches.  A descriptor whose status word is not 0 is not
+ *     decoded.
+ *   palettes [palette_bytes / 1024][256][4] uint8: R, G, B, A of each distinct palette (PLTE + tRNS).
+ *   dst / meta_out [N][4] int64 (device) = byte offset, H, W, row pitch; channels 4 (R, G, B, A), 3 (alpha dropped) or
+ *     1 (gray and gray + alpha streams only); swap_rb exchanges R and B.  Where offset and pitch are multiples of 4
+ *     the bytes between a row's end and its pitch are written as 0.
+ *   status [N] int32: 0, 1 bad zlib header, 2 reserved block type, 3 stored-block length check, 4 bad code-length
+ *     set or repeat, 5 bad literal/length or distance symbol, 6 distance before the start, 7 data ends early, 8 more
+ *     data than the image holds, 9 Adler-32 mismatch, 10 filter byte above 4, 11 a meta_out row that is not this image
+ *     inside dst, 12 reserved, 16.. the parser's reason.  Status 0 exactly when zlib inflates the stream to its end
+ *     without an error and it holds H * (1 + row bytes) bytes.  An image with a status leaves its output rectangle as
+ *     it was; the other images are unaffected.  For ANY bytes the device reads only inside the stream's range and the
+ *     palettes and writes only the image's own workspace and rectangle.
+ *   msml_png_workspace(desc, N): on the HOST descriptors, writes each image's workspace offset into its descriptor
+ *     and returns the bytes msml_png_decode needs (0 for a descriptor it would refuse).
+ *   MSML_ERR_UNSUPPORTED before any launch for N outside 1..65535, channels other than 1, 3, 4, a colour or palette
+ *   stream with channels 1; MSML_ERR_SHAPE for null or misaligned pointers (4 bytes; meta_out 8, ws 16) and an
+ *   inconsistent descriptor; MSML_ERR_WORKSPACE for a workspace that is too small. */
+long msml_png_workspace(int* desc, int N);
+int msml_png_decode(const unsigned char* streams, long stream_bytes, const int* desc, const int* desc_host,
+                    const unsigned char* palettes, long palette_bytes, unsigned char* dst, long dst_bytes,
+                    const long* meta_out, int channels, int swap_rb, int* status, unsigned char* ws, long ws_bytes,
+                    int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -248,6 +248,40 @@ def read_pairs_txt(lines, files_by_identity):
     return np.array(pairs, np.int64).reshape(-1, 2), np.array(issame, bool)
 
 
+def list_folder(root):
+    """The directory walk of eval/qeval_folder.py:42-47: {identity: [file names, sorted]} for every sub-directory of
+    root (the identity) and every regular file in it.  An identity without files keeps its empty list."""
+    import os
+    out = {}
+    for ident in sorted(os.listdir(root)):
+        sub = os.path.join(root, ident)
+        if os.path.isdir(sub):
+            out[ident] = sorted(f for f in os.listdir(sub) if os.path.isfile(os.path.join(sub, f)))
+    return out
+
+
+def load_folder(root, device="cuda"):
+    """The file I/O read_pairs_txt leaves out (qeval_folder.py:42-49, Image.open(...).convert('RGB') of every file of
+    every identity): -> (files_by_identity, buf, meta), the images decoded on the device (imageio.decode_images: JPEG
+    and PNG files, mixed freely) in pairs_file_order -- row k of meta is the image read_pairs_txt's index k names.
+    ValueError naming the file for one that cannot be decoded."""
+    import os
+    from . import imageio
+    files = list_folder(root)
+    order = pairs_file_order(files)
+    if not order:
+        raise ValueError("load_folder: no files under %r" % (root,))
+    blobs = []
+    for ident, f in order:
+        with open(os.path.join(root, ident, f), "rb") as fh:
+            blobs.append(fh.read())
+    try:
+        buf, meta = imageio.decode_images(blobs, order="rgb", strict=True, device=device)
+    except imageio.DecodeError as e:
+        raise ValueError("load_folder: %s: %s" % (os.path.join(*order[e.index]), e)) from None
+    return files, buf, meta
+
+
 def _no_block(lo, hi):
     return (lo is None and hi is None) or (lo == 0 and hi == 1)
 
