@@ -24,33 +24,11 @@ struct JpgWaveSink {
   __device__ void end(long blk) { coef[blk * 64 + nat] = (int16_t)c; }
 };
 
-// The stream of one image behind a window of JPG_CHUNK bytes in LDS: the decoder reads forward, a byte at a time, and
-// a read outside the window makes all 64 lanes fetch the chunk that holds it (aligned dwords, none past the dword of
-// the stream's last byte; msml_jpeg_decode checks that the buffer is whole dwords).
-#define JPG_CHUNK 2048
-struct JpgLdsSrc {
-  const unsigned char* g;
-  unsigned int* win;
-  int w0, end, lane;
-  __device__ int byte(int i) {
-    if ((unsigned int)(i - w0) >= (unsigned int)JPG_CHUNK) {
-      w0 = i & ~(JPG_CHUNK - 1);
-      __syncthreads();
-      for (int k = lane; k < JPG_CHUNK / 4; k += 64) {
-        const int o = w0 + k * 4;
-        win[k] = o < end ? *reinterpret_cast<const unsigned int*>(g + o) : 0u;
-      }
-      __syncthreads();
-    }
-    return reinterpret_cast<const unsigned char*>(win)[i - w0];
-  }
-};
-
 __global__ void __launch_bounds__(64) k_jpeg_entropy(const unsigned char* __restrict__ streams,
                                                      const int* __restrict__ desc, const int* __restrict__ huff,
                                                      unsigned char* __restrict__ ws, int* __restrict__ status) {
   __shared__ int s_tab[6 * JPG_HUFF_WORDS];                  // the DC and AC table of each component
-  __shared__ unsigned int s_win[JPG_CHUNK / 4];
+  __shared__ unsigned int s_win[IMG_CHUNK / 4];
   const int n = blockIdx.x;
   const int* d = desc + (long)n * JPG_DESC_WORDS;
   int st = d[JD_STATUS];
@@ -74,14 +52,9 @@ __global__ void __launch_bounds__(64) k_jpeg_entropy(const unsigned char* __rest
     JpgWaveSink sink;
     sink.coef = reinterpret_cast<int16_t*>(ws + (long)d[JD_WS] * JPG_WS_ALIGN);
     sink.lane = threadIdx.x;
-    sink.nat = jpg_natural(threadIdx.x);
+    sink.nat = img_zigzag(threadIdx.x);
     sink.c = 0;
-    JpgLdsSrc src;
-    src.g = streams + (long)d[JD_BASE] * 4;
-    src.win = s_win;
-    src.w0 = -JPG_CHUNK;
-    src.end = d[JD_END];
-    src.lane = threadIdx.x;
+    LdsStreamSrc src = {streams + (long)d[JD_BASE] * 4, s_win, -IMG_CHUNK, d[JD_END], (int)threadIdx.x};
     st = jpg_entropy(d, src, dctab, actab, sink);
   }
   if (threadIdx.x == 0) status[n] = st;
@@ -125,9 +98,7 @@ __global__ void __launch_bounds__(256) k_jpeg_store(const int* __restrict__ desc
   const long rowb = (long)W * channels;
   // the destination rectangle is checked here, on the device, where meta_out lives: an image that does not fit is
   // not written (every workgroup of the image sees the same values and leaves)
-  // (compared by subtraction: H <= 32767 and pitch < 2^31 keep the span below 2^46, and off <= dst_bytes)
-  if (off < 0 || off > dst_bytes || mt[1] != H || mt[2] != W || pitch < rowb || pitch > 0x7fffffffL ||
-      (long)(H - 1) * pitch + (((off | pitch) & 3) == 0 ? pitch : rowb) > dst_bytes - off) {
+  if (!img_rect_ok(mt, H, W, rowb, img_aligned(off, pitch) ? pitch : rowb, dst_bytes)) {
     if (blockIdx.x == 0 && threadIdx.x == 0) status[n] = JPG_ERR_OUTPUT;
     return;
   }
@@ -155,23 +126,7 @@ __global__ void __launch_bounds__(256) k_jpeg_store(const int* __restrict__ desc
       }
     }
   }
-  unsigned char* row = dst + off + (long)y * pitch;
-  const long b0 = (long)x0 * channels;
-  if (((off | pitch) & 3) == 0) {
-#pragma unroll
-    for (int w = 0; w < 3; ++w) {
-      if (w < channels && b0 + w * 4 < pitch) {
-        *reinterpret_cast<unsigned int*>(row + b0 + w * 4) =
-            px[w * 4] | (px[w * 4 + 1] << 8) | (px[w * 4 + 2] << 16) | ((unsigned int)px[w * 4 + 3] << 24);
-      }
-    }
-    if (x0 + 4 >= W)                                         // the last group of the row: zeros up to the pitch
-      for (long p = b0 + channels * 4; p < pitch; p += 4) *reinterpret_cast<unsigned int*>(row + p) = 0u;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 12; ++e)
-      if (e < channels * 4 && b0 + e < rowb) row[b0 + e] = px[e];
-  }
+  img_store4<3>(dst + off + (long)y * pitch, off, pitch, rowb, x0, W, channels, px);
 }
 
 extern "C" long msml_jpeg_workspace(int* desc, int N) {

@@ -10,11 +10,7 @@
 #define MSML_JPEG_CORE_H
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define JPG_HD __host__ __device__
-#else
-#define JPG_HD
-#endif
+#include "packed_image.h"
 
 // ---- the descriptor: JPG_DESC_WORDS int32 per image (msml_amd/jpeg.py writes it, msml_jpeg_decode checks it) ----------
 #define JPG_DESC_WORDS 32
@@ -69,7 +65,7 @@ struct JpgLayout {
 
 // Workspace of one image: coefficients int16 [nblk][64] (natural order), then the component planes uint8
 // [bh * 8][bw * 8].
-JPG_HD inline void jpg_layout(const int* d, JpgLayout& L) {
+IMG_HD inline void jpg_layout(const int* d, JpgLayout& L) {
   L.ncomp = d[JD_NCOMP];
   long blk = 0;
   for (int c = 0; c < 3; ++c) {
@@ -92,7 +88,7 @@ JPG_HD inline void jpg_layout(const int* d, JpgLayout& L) {
 // the device stages it through LDS (jpeg.hip).
 struct JpgPtrSrc {
   const unsigned char* p;
-  JPG_HD int byte(int i) { return p[i]; }
+  IMG_HD int byte(int i) { return p[i]; }
 };
 
 template <class Src>
@@ -105,7 +101,7 @@ struct JpgBits {
 };
 
 template <class Src>
-JPG_HD inline void jpg_fill(JpgBits<Src>& b) {
+IMG_HD inline void jpg_fill(JpgBits<Src>& b) {
   while (b.n <= 24) {
     uint32_t c = 0;
     if (!b.marker && b.pos < b.end) {
@@ -128,22 +124,22 @@ JPG_HD inline void jpg_fill(JpgBits<Src>& b) {
 }
 
 template <class Src>
-JPG_HD inline void jpg_skip(JpgBits<Src>& b, int k) { b.acc <<= k; b.n -= k; }
+IMG_HD inline void jpg_skip(JpgBits<Src>& b, int k) { b.acc <<= k; b.n -= k; }
 
 // k in 1..16
 template <class Src>
-JPG_HD inline int jpg_receive(JpgBits<Src>& b, int k) {
+IMG_HD inline int jpg_receive(JpgBits<Src>& b, int k) {
   if (b.n < k) jpg_fill(b);
   const int v = (int)(b.acc >> (32 - k));
   jpg_skip(b, k);
   return v;
 }
 
-JPG_HD inline int jpg_extend(int v, int k) { return v >= (1 << (k - 1)) ? v : v - (1 << k) + 1; }
+IMG_HD inline int jpg_extend(int v, int k) { return v >= (1 << (k - 1)) ? v : v - (1 << k) + 1; }
 
 // the next symbol of table t, or -1 for a code the table does not hold
 template <class Src>
-JPG_HD inline int jpg_symbol(JpgBits<Src>& b, const int* t) {
+IMG_HD inline int jpg_symbol(JpgBits<Src>& b, const int* t) {
   if (b.n < 16) jpg_fill(b);
   const int look = t[b.acc >> (32 - JPG_HUFF_LOOK)];
   if (look) {
@@ -163,7 +159,7 @@ JPG_HD inline int jpg_symbol(JpgBits<Src>& b, const int* t) {
 
 // At a restart: the rest of the current byte is dropped, RSTm (m = index & 7) must follow, predictions start over.
 template <class Src>
-JPG_HD inline int jpg_restart(JpgBits<Src>& b, int index) {
+IMG_HD inline int jpg_restart(JpgBits<Src>& b, int index) {
   if (b.n < b.pad) return JPG_ERR_TRUNCATED;
   if (b.n - b.pad >= 8) return JPG_ERR_RESTART;             // whole data bytes in front of the marker
   int q = b.pos;
@@ -178,20 +174,11 @@ JPG_HD inline int jpg_restart(JpgBits<Src>& b, int index) {
   return JPG_OK;
 }
 
-// natural (row-major) index of the k-th coefficient in zigzag order
-JPG_HD inline int jpg_natural(int k) {
-  constexpr unsigned char zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                                    12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                                    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                                    58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-  return zz[k & 63];
-}
-
 // Entropy decoding of one image.  d: its descriptor; src: its stream (d[JD_BASE] applied); dctab / actab: the lookup
 // tables of each component.  Sink: begin() starts a block of zeros, put(k, value) sets the k-th coefficient in ZIGZAG
-// order (the sink knows jpg_natural), end(block) stores the block.
+// order (the sink knows img_zigzag), end(block) stores the block.
 template <class Src, class Sink>
-JPG_HD inline int jpg_entropy(const int* d, const Src& src, const int* const dctab[3], const int* const actab[3],
+IMG_HD inline int jpg_entropy(const int* d, const Src& src, const int* const dctab[3], const int* const actab[3],
                               Sink& sink) {
   JpgLayout L;
   jpg_layout(d, L);
@@ -261,9 +248,9 @@ JPG_HD inline int jpg_entropy(const int* d, const Src& src, const int* const dct
 // ---- dequantisation + JDCT_ISLOW ------------------------------------------------------------------------------------
 // 32-bit arithmetic that wraps (unsigned): equal to libjpeg's for every coefficient a real encoder writes, and defined
 // for every other.
-JPG_HD inline int jpg_descale(uint32_t x, int n) { return (int)(x + (1u << (n - 1))) >> n; }
+IMG_HD inline int jpg_descale(uint32_t x, int n) { return (int)(x + (1u << (n - 1))) >> n; }
 
-JPG_HD inline void jpg_idct_1d(const uint32_t in[8], int out[8], int n) {
+IMG_HD inline void jpg_idct_1d(const uint32_t in[8], int out[8], int n) {
   const uint32_t z1e = (in[2] + in[6]) * 4433u;
   const uint32_t t2 = z1e - in[6] * 15137u, t3 = z1e + in[2] * 6270u;
   const uint32_t t0 = (in[0] + in[4]) << 13, t1 = (in[0] - in[4]) << 13;
@@ -283,7 +270,7 @@ JPG_HD inline void jpg_idct_1d(const uint32_t in[8], int out[8], int n) {
 }
 
 // coef: 64 coefficients in natural order; q: the quantisation table in natural order; out: 8 rows of 8 samples
-JPG_HD inline void jpg_idct(const int16_t* coef, const int* q, unsigned char* out, long pitch) {
+IMG_HD inline void jpg_idct(const int16_t* coef, const int* q, unsigned char* out, long pitch) {
   int wsp[64];
   for (int x = 0; x < 8; ++x) {
     uint32_t in[8];
@@ -306,7 +293,7 @@ JPG_HD inline void jpg_idct(const int16_t* coef, const int* q, unsigned char* ou
 
 // ---- upsampling + colour ---------------------------------------------------------------------------------------------
 // One chroma sample at output (x, y).  p: the component plane, dw x dh its cropped size, hs / vs the expansion (1 or 2).
-JPG_HD inline int jpg_chroma(const unsigned char* p, long pitch, int dw, int dh, int hs, int vs, int x, int y) {
+IMG_HD inline int jpg_chroma(const unsigned char* p, long pitch, int dw, int dh, int hs, int vs, int x, int y) {
   if (hs == 1) return p[(long)y * pitch + x];
   const int i = x >> 1;
   if (vs == 1) {
@@ -326,10 +313,10 @@ JPG_HD inline int jpg_chroma(const unsigned char* p, long pitch, int dw, int dh,
   return i == dw - 1 ? (4 * s + 7) >> 4 : (3 * s + 3 * r0[i + 1] + r1[i + 1] + 7) >> 4;
 }
 
-JPG_HD inline int jpg_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+IMG_HD inline int jpg_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // The pixel (x, y) of the image whose workspace is ws: rgb[0..2] = R, G, B (all Y for a gray stream).
-JPG_HD inline void jpg_pixel(const int* d, const JpgLayout& L, const unsigned char* ws, int x, int y, int rgb[3]) {
+IMG_HD inline void jpg_pixel(const int* d, const JpgLayout& L, const unsigned char* ws, int x, int y, int rgb[3]) {
   const int yy = ws[L.pbase[0] + (long)y * (L.bw[0] * 8) + x];
   if (L.ncomp == 1) {
     rgb[0] = rgb[1] = rgb[2] = yy;

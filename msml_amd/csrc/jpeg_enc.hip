@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(64) k_jpeg_enc_dct(const unsigned char* __rest
   const int my = blockIdx.x / tpr, mx0 = (blockIdx.x - my * tpr) * tm;
   for (int k = t; k < 128; k += 64) {
     const int tb = k >> 6, z = k & 63;
-    const uint32_t dv = 8u * (uint32_t)qtabs[(long)d[JE_QT + tb] * 64 + jpe_natural(z)];
+    const uint32_t dv = 8u * (uint32_t)qtabs[(long)d[JE_QT + tb] * 64 + img_zigzag(z)];
     s_div[tb][z] = dv;
     s_rcp[tb][z] = jpe_recip(dv < 8u ? 8u : dv);
   }
@@ -75,8 +75,8 @@ __global__ void __launch_bounds__(64) k_jpeg_enc_dct(const unsigned char* __rest
     unsigned int pk[32];
 #pragma unroll
     for (int k = 0; k < 64; k += 2) {
-      const int a = jpe_quant(blk[jpe_natural(k)], s_div[tb][k], s_rcp[tb][k], k ? 1023 : 1024);
-      const int c = jpe_quant(blk[jpe_natural(k + 1)], s_div[tb][k + 1], s_rcp[tb][k + 1], 1023);
+      const int a = jpe_quant(blk[img_zigzag(k)], s_div[tb][k], s_rcp[tb][k], k ? 1023 : 1024);
+      const int c = jpe_quant(blk[img_zigzag(k + 1)], s_div[tb][k + 1], s_rcp[tb][k + 1], 1023);
       if (k == 0) s_dc[t] = a;
       pk[k >> 1] = ((unsigned int)a & 0xffffu) | ((unsigned int)c << 16);
     }

@@ -11,11 +11,7 @@
 #define MSML_JPEG_ENC_CORE_H
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define JPE_HD __host__ __device__
-#else
-#define JPE_HD
-#endif
+#include "packed_image.h"
 
 // ---- the descriptor: JPE_DESC_WORDS int32 per image (msml_amd/jpeg.py writes it, msml_jpeg_encode checks it) ---------
 #define JPE_DESC_WORDS 12
@@ -48,7 +44,7 @@ struct JpeGeom {
   long o_boff, o_ioff, o_ubuf, bytes;
 };
 
-JPE_HD inline void jpe_geom(const int* d, JpeGeom& G) {
+IMG_HD inline void jpe_geom(const int* d, JpeGeom& G) {
   G.samp = d[JE_SAMP];
   G.ncomp = G.samp == 0 ? 1 : 3;
   G.hs = G.samp >= 2 ? 2 : 1;
@@ -91,21 +87,21 @@ inline long jpe_bound(int H, int W, int samp, int ri, int header_bytes) {
   return header_bytes + 2 * G.nblk * JPE_BLOCK_BYTES + 2 * G.nint + 2;
 }
 
-// The meta row [offset, H, W, pitch] of a source against the descriptor and the buffer (compared by subtraction: no overflow).
-JPE_HD inline bool jpe_source_ok(const JpeGeom& G, const long* mt, int channels, long src_bytes) {
-  const long off = mt[0], pitch = mt[3], rowb = (long)G.W * channels;
-  return !(off < 0 || off > src_bytes || mt[1] != G.H || mt[2] != G.W || pitch < rowb || pitch > 0x7fffffffL ||
-           (long)(G.H - 1) * pitch + rowb > src_bytes - off);
+// The meta row [offset, H, W, pitch] of a source against the descriptor and the buffer: read, so its last row ends with
+// its last pixel.
+IMG_HD inline bool jpe_source_ok(const JpeGeom& G, const long* mt, int channels, long src_bytes) {
+  const long rowb = (long)G.W * channels;
+  return img_rect_ok(mt, G.H, G.W, rowb, rowb, src_bytes);
 }
 
 // ---- colour (jccolor.c) ---------------------------------------------------------------------------------------------
-JPE_HD inline int jpe_y(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
-JPE_HD inline int jpe_cb(int r, int g, int b) { return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16; }
-JPE_HD inline int jpe_cr(int r, int g, int b) { return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16; }
+IMG_HD inline int jpe_y(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
+IMG_HD inline int jpe_cb(int r, int g, int b) { return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16; }
+IMG_HD inline int jpe_cr(int r, int g, int b) { return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16; }
 
 // The source row a chroma sample of full-resolution row y comes from (jcprepct.c, jcsample.c): the source is replicated
 // only up to a multiple of vs, and the last DOWNSAMPLED row is what fills the rest of the block rows.
-JPE_HD inline int jpe_chroma_row(const JpeGeom& G, int y) {
+IMG_HD inline int jpe_chroma_row(const JpeGeom& G, int y) {
   const int cy = y / G.vs, j = y - cy * G.vs, chh = (G.H + G.vs - 1) / G.vs;
   const int r = (cy < chh ? cy : chh - 1) * G.vs + j;
   return r < G.H ? r : G.H - 1;
@@ -114,11 +110,11 @@ JPE_HD inline int jpe_chroma_row(const JpeGeom& G, int y) {
 // ---- the tile: a run of MCUs of one MCU row, its samples staged as full-resolution Y, Cb, Cr planes ------------------------
 // JPE_TILE_PIXELS samples per plane in every sampling: vs * 8 rows of jpe_tile_mcus() * hs * 8 columns.
 #define JPE_TILE_PIXELS 2048
-JPE_HD inline int jpe_tile_mcus(const JpeGeom& G) { return G.samp == 0 ? 32 : (G.samp == 3 ? 8 : 16); }
+IMG_HD inline int jpe_tile_mcus(const JpeGeom& G) { return G.samp == 0 ? 32 : (G.samp == 3 ? 8 : 16); }
 
 // Thread t0 of `step` stages its share of the tile at MCU row my, MCU column mx0.  img: the image's first byte.
 // Columns past W repeat the last one (the right edge of every component is the replicated source); rows as above.
-JPE_HD inline void jpe_stage(const JpeGeom& G, const unsigned char* img, long pitch, int channels, int swap_rb, int my,
+IMG_HD inline void jpe_stage(const JpeGeom& G, const unsigned char* img, long pitch, int channels, int swap_rb, int my,
                              int mx0, unsigned char* Y, unsigned char* Cb, unsigned char* Cr, int t0, int step) {
   const int tw = jpe_tile_mcus(G) * G.hs * 8, tr = G.vs * 8;
   const int xend = (G.mcux - mx0) * G.hs * 8;                // columns of the tile that belong to an MCU of the image
@@ -149,7 +145,7 @@ JPE_HD inline void jpe_stage(const JpeGeom& G, const unsigned char* img, long pi
 }
 
 // Block j of the tile's MCU mloc: which component, where in the MCU, and whether it is a dummy (jccoefct.c).
-JPE_HD inline void jpe_block_place(const JpeGeom& G, int my, int mx, int j, int& comp, int& jx, int& jy, bool& dummy) {
+IMG_HD inline void jpe_block_place(const JpeGeom& G, int my, int mx, int j, int& comp, int& jx, int& jy, bool& dummy) {
   comp = j < G.ny ? 0 : j - G.ny + 1;
   jx = comp == 0 ? j % G.hs : 0;
   jy = comp == 0 ? j / G.hs : 0;
@@ -158,7 +154,7 @@ JPE_HD inline void jpe_block_place(const JpeGeom& G, int my, int mx, int j, int&
 
 // The 64 samples of that block minus 128, chroma downsampled (jcsample.c: h2v1 bias 0, 1, 0, 1, .. and h2v2 bias
 // 1, 2, 1, 2, .. by output column).
-JPE_HD inline void jpe_block_samples(const JpeGeom& G, const unsigned char* Y, const unsigned char* Cb,
+IMG_HD inline void jpe_block_samples(const JpeGeom& G, const unsigned char* Y, const unsigned char* Cb,
                                      const unsigned char* Cr, int mloc, int comp, int jx, int jy, int blk[64]) {
   const int tw = jpe_tile_mcus(G) * G.hs * 8;
   if (comp == 0 || G.hs == 1) {
@@ -181,10 +177,10 @@ JPE_HD inline void jpe_block_samples(const JpeGeom& G, const unsigned char* Y, c
 }
 
 // ---- JDCT_ISLOW forward (jfdctint.c), CONST_BITS 13, PASS1_BITS 2 ----------------------------------------------------------
-JPE_HD inline int jpe_descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+IMG_HD inline int jpe_descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 
 // one pass over 8 values: pass 0 (rows) scales up by 4, pass 1 (columns) takes that out and divides by 8 less than a true DCT
-JPE_HD inline void jpe_fdct_1d(const int d[8], int o[8], int pass) {
+IMG_HD inline void jpe_fdct_1d(const int d[8], int o[8], int pass) {
   const int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
   const int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
   const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
@@ -207,7 +203,7 @@ JPE_HD inline void jpe_fdct_1d(const int d[8], int o[8], int pass) {
   o[1] = jpe_descale(a7 + z1 + z4, n);
 }
 
-JPE_HD inline void jpe_fdct(int blk[64]) {
+IMG_HD inline void jpe_fdct(int blk[64]) {
   for (int r = 0; r < 8; ++r) {
     int d[8], o[8];
     for (int c = 0; c < 8; ++c) d[c] = blk[r * 8 + c];
@@ -225,23 +221,15 @@ JPE_HD inline void jpe_fdct(int blk[64]) {
 // ---- quantisation (jcdctmgr.c): sign(c) * ((|c| + divisor / 2) / divisor), divisor = 8 q --------------------------------------
 // The division is a multiplication by ceil(2^32 / divisor): exact while (|c| + divisor / 2) * divisor < 2^32, and
 // |c| < 2^15, divisor <= 2040.  One division per table entry instead of one per coefficient.
-JPE_HD inline uint32_t jpe_recip(uint32_t divisor) { return (uint32_t)(((1ull << 32) + divisor - 1) / divisor); }
+IMG_HD inline uint32_t jpe_recip(uint32_t divisor) { return (uint32_t)(((1ull << 32) + divisor - 1) / divisor); }
 
 // -> the coefficient, clamped to what the entropy coder can write (DC +-1024 so that differences stay within category
 // 11, AC +-1023 = category 10; 8-bit samples never reach the clamps)
-JPE_HD inline int jpe_quant(int c, uint32_t divisor, uint32_t recip, int limit) {
+IMG_HD inline int jpe_quant(int c, uint32_t divisor, uint32_t recip, int limit) {
   const uint32_t a = (uint32_t)(c < 0 ? -c : c) + (divisor >> 1);
   int v = (int)(uint32_t)(((uint64_t)a * recip) >> 32);
   v = v > limit ? limit : v;
   return c < 0 ? -v : v;
-}
-
-JPE_HD inline int jpe_natural(int k) {
-  constexpr unsigned char zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                                    12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                                    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                                    58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-  return zz[k & 63];
 }
 
 // ---- the standard Huffman tables (Annex K.3 - K.6) --------------------------------------------------------------------------
@@ -256,7 +244,7 @@ struct JpeStdTable {
   unsigned char val[162];
 };
 
-JPE_HD inline const JpeStdTable& jpe_std_table(int which) {   // 0 DC luma, 1 DC chroma, 2 AC luma, 3 AC chroma
+IMG_HD inline const JpeStdTable& jpe_std_table(int which) {   // 0 DC luma, 1 DC chroma, 2 AC luma, 3 AC chroma
   static constexpr JpeStdTable T[4] = {
       {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}},
       {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}},
@@ -287,10 +275,10 @@ JPE_HD inline const JpeStdTable& jpe_std_table(int which) {   // 0 DC luma, 1 DC
 
 // Thread t0 of `step` writes its share of the code tables: zeros first, then (after a barrier where step > 1) the p-th
 // symbol of each table gets the canonical code of its length.
-JPE_HD inline void jpe_huff_zero(uint32_t* tab, int t0, int step) {
+IMG_HD inline void jpe_huff_zero(uint32_t* tab, int t0, int step) {
   for (int i = t0; i < JPE_HUFF_WORDS; i += step) tab[i] = 0;
 }
-JPE_HD inline void jpe_huff_fill(uint32_t* tab, int t0, int step) {
+IMG_HD inline void jpe_huff_fill(uint32_t* tab, int t0, int step) {
   for (int w = 0; w < 4; ++w) {
     const JpeStdTable& T = jpe_std_table(w);
     uint32_t* out = tab + (w < 2 ? 16 * w : JPE_HUFF_AC + 256 * (w - 2));
@@ -311,11 +299,11 @@ JPE_HD inline void jpe_huff_fill(uint32_t* tab, int t0, int step) {
 }
 
 // ---- entropy coding of one block (jchuff.c) ------------------------------------------------------------------------------------
-JPE_HD inline int jpe_nbits(int a) { return a == 0 ? 0 : 32 - __builtin_clz((unsigned int)a); }
+IMG_HD inline int jpe_nbits(int a) { return a == 0 ? 0 : 32 - __builtin_clz((unsigned int)a); }
 
 // The block whose DC this block's difference is taken from: the previous block of the same component in scan order,
 // -1 at the start of a restart interval (prediction 0).
-JPE_HD inline long jpe_pred_block(const JpeGeom& G, long b) {
+IMG_HD inline long jpe_pred_block(const JpeGeom& G, long b) {
   const long m = b / G.bpm;
   const int j = (int)(b - m * G.bpm);
   const bool first = G.ri > 0 ? m % G.ri == 0 : m == 0;
@@ -325,7 +313,7 @@ JPE_HD inline long jpe_pred_block(const JpeGeom& G, long b) {
 
 // Sink: put(code, length) with length 1..16.  zz: the block in zigzag order.  One walk for the size pass and the emit pass.
 template <class Sink>
-JPE_HD inline void jpe_block_code(const int16_t* zz, int pred, const uint32_t* dct, const uint32_t* act, Sink& s) {
+IMG_HD inline void jpe_block_code(const int16_t* zz, int pred, const uint32_t* dct, const uint32_t* act, Sink& s) {
   int diff = (int)zz[0] - pred;
   diff = diff > 2047 ? 2047 : (diff < -2047 ? -2047 : diff);
   int cat = jpe_nbits(diff < 0 ? -diff : diff);
@@ -354,7 +342,7 @@ JPE_HD inline void jpe_block_code(const int16_t* zz, int pred, const uint32_t* d
 
 struct JpeCountSink {
   int bits;
-  JPE_HD void put(uint32_t, int len) { bits += len; }
+  IMG_HD void put(uint32_t, int len) { bits += len; }
 };
 
 // Bits into a zeroed buffer of 32-bit words at any bit position: the stream is big-endian, so a finished word is
@@ -366,12 +354,12 @@ struct JpeBitSink {
   long w, nwords;
   uint64_t acc;
   int n;
-  JPE_HD void begin(long bitpos) {
+  IMG_HD void begin(long bitpos) {
     w = bitpos >> 5;
     n = (int)(bitpos & 31);
     acc = 0;
   }
-  JPE_HD void put(uint32_t code, int len) {
+  IMG_HD void put(uint32_t code, int len) {
     acc |= (uint64_t)code << (64 - n - len);
     n += len;
     if (n >= 32) {
@@ -380,23 +368,23 @@ struct JpeBitSink {
       n -= 32;
     }
   }
-  JPE_HD void flush(uint32_t v) {
+  IMG_HD void flush(uint32_t v) {
     if (v != 0 && w >= 0 && w < nwords) out.merge(w, __builtin_bswap32(v));
     ++w;
   }
   // the end of a restart interval (or of the scan): 1 bits up to the byte boundary
-  JPE_HD void pad() {
+  IMG_HD void pad() {
     const int k = (8 - (n & 7)) & 7;
     if (k) put((1u << k) - 1, k);
   }
-  JPE_HD void end() {
+  IMG_HD void end() {
     if (n > 0) flush((uint32_t)(acc >> 32));
   }
 };
 
 // ---- byte stuffing and markers: the unstuffed bytes of all intervals lie back to back ------------------------------------------
 // the interval that holds unstuffed byte j: the last i with ioff[i] <= j (every interval has at least one byte)
-JPE_HD inline long jpe_interval_of(const long* ioff, long nint, long j) {
+IMG_HD inline long jpe_interval_of(const long* ioff, long nint, long j) {
   long lo = 0, hi = nint;
   while (hi - lo > 1) {
     const long mid = (lo + hi) >> 1;
@@ -410,7 +398,7 @@ JPE_HD inline long jpe_interval_of(const long* ioff, long nint, long j) {
 // image, `ff` = the FF bytes in front of j0: every byte lands after the header, the stuffing bytes and the restart
 // markers in front of it; an FF is followed by 00; the first byte of interval i > 0 is preceded by RST((i - 1) & 7).
 template <class Out>
-JPE_HD inline void jpe_pack_bytes(const unsigned char* ub, long j0, long j1, const long* ioff, long nint, long ff,
+IMG_HD inline void jpe_pack_bytes(const unsigned char* ub, long j0, long j1, const long* ioff, long nint, long ff,
                                   int hlen, Out& out) {
   if (j0 >= j1) return;
   long i = jpe_interval_of(ioff, nint, j0);

@@ -14,34 +14,8 @@
 #include "common.h"
 #include "png_core.h"
 
-#define PNG_CHUNK 2048
 #define PNG_RING 32768
 #define PNG_HALF 16384
-
-// The stream of one image behind a window of PNG_CHUNK bytes in LDS (as JpgLdsSrc of jpeg.hip): a read outside the
-// window makes all 64 lanes fetch the chunk that holds it (aligned dwords, none past the dword of the stream's last
-// byte; msml_png_decode checks that the buffer is whole dwords).
-struct PngLdsSrc {
-  const unsigned char* g;
-  unsigned int* win;
-  int w0, end, lane;
-  __device__ int byte(int i) {
-    if ((unsigned int)(i - w0) >= (unsigned int)PNG_CHUNK) {
-      w0 = i & ~(PNG_CHUNK - 1);
-      __syncthreads();
-      for (int k = lane; k < PNG_CHUNK / 4; k += 64) {
-        const int o = w0 + k * 4;
-        win[k] = o < end ? *reinterpret_cast<const unsigned int*>(g + o) : 0u;
-      }
-      __syncthreads();
-    }
-    return reinterpret_cast<const unsigned char*>(win)[i - w0];
-  }
-  __device__ unsigned int word(int i) {                      // i % 4 == 0, i + 4 <= end
-    if ((unsigned int)(i - w0) >= (unsigned int)PNG_CHUNK) (void)byte(i);
-    return win[(i - w0) >> 2];
-  }
-};
 
 // The last 32 KiB of output in LDS.  All source bytes of a match precede its first output byte, so the lanes copy it
 // without a dependency between them; a slot that a later byte of the same match overwrites (distances near 32768) is
@@ -111,7 +85,7 @@ __global__ void __launch_bounds__(64) k_png_inflate(const unsigned char* __restr
                                                     const int* __restrict__ desc, unsigned char* __restrict__ ws,
                                                     int* __restrict__ status) {
   __shared__ __attribute__((aligned(16))) unsigned char s_ring[PNG_RING];
-  __shared__ unsigned int s_win[PNG_CHUNK / 4];
+  __shared__ unsigned int s_win[IMG_CHUNK / 4];
   __shared__ PngTables s_tab;
   const int n = blockIdx.x;
   const int* d = desc + (long)n * PNG_DESC_WORDS;
@@ -124,12 +98,7 @@ __global__ void __launch_bounds__(64) k_png_inflate(const unsigned char* __restr
     sink.a = 1;
     sink.b = 0;
     sink.lane = threadIdx.x;
-    PngLdsSrc src;
-    src.g = streams + (long)d[PD_BASE] * 4;
-    src.win = s_win;
-    src.w0 = -PNG_CHUNK;
-    src.end = d[PD_END];
-    src.lane = threadIdx.x;
+    LdsStreamSrc src = {streams + (long)d[PD_BASE] * 4, s_win, -IMG_CHUNK, d[PD_END], (int)threadIdx.x};
     st = png_inflate(src, d[PD_END], png_expected(d), sink, &s_tab, (int)threadIdx.x, 64);
   }
   if (threadIdx.x == 0) status[n] = st;
@@ -161,11 +130,9 @@ __global__ void __launch_bounds__(256) k_png_store(const int* __restrict__ desc,
   const long* mt = meta + (long)n * 4;
   const long off = mt[0], pitch = mt[3];
   const long rowb = (long)W * channels;
-  // the destination rectangle is checked here, on the device, where meta_out lives (compared by subtraction: H <=
-  // 32767 and pitch < 2^31 keep the span below 2^46, and off <= dst_bytes).  Every thread of the image sees the same
-  // values and leaves; nobody reads status[n] after this point in this launch but through the same test.
-  if (off < 0 || off > dst_bytes || mt[1] != H || mt[2] != W || pitch < rowb || pitch > 0x7fffffffL ||
-      (long)(H - 1) * pitch + (((off | pitch) & 3) == 0 ? pitch : rowb) > dst_bytes - off) {
+  // the destination rectangle is checked here, on the device, where meta_out lives.  Every thread of the image sees
+  // the same values and leaves; nobody reads status[n] after this point in this launch but through the same test.
+  if (!img_rect_ok(mt, H, W, rowb, img_aligned(off, pitch) ? pitch : rowb, dst_bytes)) {
     if (blockIdx.x == 0 && threadIdx.x == 0) status[n] = PNG_ERR_OUTPUT;
     return;
   }
@@ -197,23 +164,7 @@ __global__ void __launch_bounds__(256) k_png_store(const int* __restrict__ desc,
       }
     }
   }
-  unsigned char* row = dst + off + (long)y * pitch;
-  const long b0 = (long)x0 * channels;
-  if (((off | pitch) & 3) == 0) {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      if (w < channels && b0 + w * 4 < pitch) {
-        *reinterpret_cast<unsigned int*>(row + b0 + w * 4) =
-            px[w * 4] | (px[w * 4 + 1] << 8) | (px[w * 4 + 2] << 16) | ((unsigned int)px[w * 4 + 3] << 24);
-      }
-    }
-    if (x0 + 4 >= W)                                         // the last group of the row: zeros up to the pitch
-      for (long p = b0 + channels * 4; p < pitch; p += 4) *reinterpret_cast<unsigned int*>(row + p) = 0u;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 16; ++e)
-      if (e < channels * 4 && b0 + e < rowb) row[b0 + e] = px[e];
-  }
+  img_store4<4>(dst + off + (long)y * pitch, off, pitch, rowb, x0, W, channels, px);
 }
 
 extern "C" long msml_png_workspace(int* desc, int N) {

@@ -20,11 +20,7 @@
 #define MSML_PNG_CORE_H
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define PNG_HD __host__ __device__
-#else
-#define PNG_HD
-#endif
+#include "packed_image.h"
 #if defined(__HIP_DEVICE_COMPILE__)
 #define PNG_SYNC() __syncthreads()
 #define PNG_COUNT(p) atomicAdd((p), 1u)
@@ -79,19 +75,19 @@ struct PngTables {
   unsigned char lens[320];
 };
 
-PNG_HD inline int png_row_bytes(const int* d) {
+IMG_HD inline int png_row_bytes(const int* d) {
   const int ct = d[PD_CTYPE];
   const int spp = ct == 2 ? 3 : (ct == 4 ? 2 : (ct == 6 ? 4 : 1));
   return (int)(((long)d[PD_W] * spp * d[PD_DEPTH] + 7) >> 3);
 }
-PNG_HD inline int png_bpp(const int* d) {
+IMG_HD inline int png_bpp(const int* d) {
   const int ct = d[PD_CTYPE];
   const int spp = ct == 2 ? 3 : (ct == 4 ? 2 : (ct == 6 ? 4 : 1));
   const int b = spp * d[PD_DEPTH] >> 3;
   return b < 1 ? 1 : b;
 }
-PNG_HD inline long png_expected(const int* d) { return (long)d[PD_H] * (1 + png_row_bytes(d)); }
-PNG_HD inline long png_ws_bytes(const int* d) {
+IMG_HD inline long png_expected(const int* d) { return (long)d[PD_H] * (1 + png_row_bytes(d)); }
+IMG_HD inline long png_ws_bytes(const int* d) {
   return (png_expected(d) + (PNG_WS_ALIGN - 1)) / PNG_WS_ALIGN * PNG_WS_ALIGN;
 }
 
@@ -102,8 +98,8 @@ PNG_HD inline long png_ws_bytes(const int* d) {
 // Src: byte(i) for i in [0, end) only; word(i) = bytes i .. i + 3, little-endian, for i % 4 == 0 and i + 4 <= end only.
 struct PngPtrSrc {
   const unsigned char* p;
-  PNG_HD int byte(int i) { return p[i]; }
-  PNG_HD uint32_t word(int i) {
+  IMG_HD int byte(int i) { return p[i]; }
+  IMG_HD uint32_t word(int i) {
     return (uint32_t)p[i] | ((uint32_t)p[i + 1] << 8) | ((uint32_t)p[i + 2] << 16) | ((uint32_t)p[i + 3] << 24);
   }
 };
@@ -118,7 +114,7 @@ struct PngBits {
 
 // k in 0..16: called with n < 16, so a refill of 32 bits fits
 template <class Src>
-PNG_HD inline void png_need(PngBits<Src>& b, int k) {
+IMG_HD inline void png_need(PngBits<Src>& b, int k) {
   while (b.n < k) {
     if (b.pos + 4 <= b.end) {
       b.acc |= (uint64_t)b.src.word(b.pos) << b.n;
@@ -134,23 +130,23 @@ PNG_HD inline void png_need(PngBits<Src>& b, int k) {
   }
 }
 template <class Src>
-PNG_HD inline void png_drop(PngBits<Src>& b, int k) { b.acc >>= k; b.n -= k; }
+IMG_HD inline void png_drop(PngBits<Src>& b, int k) { b.acc >>= k; b.n -= k; }
 // k in 0..16
 template <class Src>
-PNG_HD inline int png_bits(PngBits<Src>& b, int k) {
+IMG_HD inline int png_bits(PngBits<Src>& b, int k) {
   png_need(b, k);
   const int v = (int)((uint32_t)b.acc & ((1u << k) - 1u));
   png_drop(b, k);
   return v;
 }
 template <class Src>
-PNG_HD inline bool png_over(const PngBits<Src>& b) { return b.n < b.pad; }
+IMG_HD inline bool png_over(const PngBits<Src>& b) { return b.n < b.pad; }
 
 // ---- code tables ------------------------------------------------------------------------------------------------------
 // Build the tables of the n code lengths lens[0..n).  Returns -1 for an over-subscribed set, otherwise what is left of
 // the code space (0: complete); maxlen: the longest code.
 template <int BITS>
-PNG_HD inline int png_build(unsigned int* cnt, unsigned short* off, unsigned short* sorted, unsigned short* look,
+IMG_HD inline int png_build(unsigned int* cnt, unsigned short* off, unsigned short* sorted, unsigned short* look,
                             const unsigned char* lens, int n, int lane, int nl, int& maxlen) {
   PNG_SYNC();
   for (int i = lane; i < 16; i += nl) cnt[i] = 0;
@@ -197,7 +193,7 @@ PNG_HD inline int png_build(unsigned int* cnt, unsigned short* off, unsigned sho
 }
 
 // the code at the bottom of acc, bit by bit: (symbol << 4) | length, or 0 for a code the set does not hold
-PNG_HD inline int png_slow(const unsigned int* cnt, const unsigned short* sorted, uint32_t acc) {
+IMG_HD inline int png_slow(const unsigned int* cnt, const unsigned short* sorted, uint32_t acc) {
   int code = 0, first = 0, index = 0;
   for (int l = 1; l <= 15; ++l) {
     code |= (int)(acc & 1u);
@@ -213,7 +209,7 @@ PNG_HD inline int png_slow(const unsigned int* cnt, const unsigned short* sorted
 
 // the next symbol, or -1 for a code the set does not hold
 template <class Src>
-PNG_HD inline int png_symbol(PngBits<Src>& b, const unsigned int* cnt, const unsigned short* sorted,
+IMG_HD inline int png_symbol(PngBits<Src>& b, const unsigned int* cnt, const unsigned short* sorted,
                              const unsigned short* look, int bits) {
   png_need(b, 15);
   int e = look[(uint32_t)b.acc & ((1u << bits) - 1u)];
@@ -228,7 +224,7 @@ PNG_HD inline int png_symbol(PngBits<Src>& b, const unsigned int* cnt, const uns
 // the byte `distance` back, repeating for distance < length); finish() flushes and returns the Adler-32 of all bytes.
 // The sink is never asked to hold more than `expected` bytes.
 template <class Src, class Sink>
-PNG_HD inline int png_inflate(const Src& src, int end, long expected, Sink& sink, PngTables* T, int lane, int nl) {
+IMG_HD inline int png_inflate(const Src& src, int end, long expected, Sink& sink, PngTables* T, int lane, int nl) {
   constexpr unsigned short lbase[29] = {3,  4,  5,  6,  7,  8,  9,  10, 11,  13,  15,  17,  19,  23, 27,
                                         31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
   constexpr unsigned char lext[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
@@ -357,7 +353,7 @@ PNG_HD inline int png_inflate(const Src& src, int end, long expected, Sink& sink
 }
 
 // ---- filters ----------------------------------------------------------------------------------------------------------
-PNG_HD inline int png_paeth(int a, int b, int c) {
+IMG_HD inline int png_paeth(int a, int b, int c) {
   const int p = a + b - c;
   const int pa = p > a ? p - a : a - p, pb = p > b ? p - b : b - p, pc = p > c ? p - c : c - p;
   return pa <= pb && pa <= pc ? a : (pb <= pc ? b : c);
@@ -365,7 +361,7 @@ PNG_HD inline int png_paeth(int a, int b, int c) {
 
 // Sub (1), Average (3) or Paeth (4) along one row for the bytes k, k + bpp, k + 2 bpp ...: each depends on the one
 // before it.  The filtered bytes and the row above are read 8 at a time ahead of the chain, which runs in registers.
-PNG_HD inline void png_unfilter_chain(unsigned char* row, const unsigned char* prior, int rowbytes, int bpp, int ft, int k) {
+IMG_HD inline void png_unfilter_chain(unsigned char* row, const unsigned char* prior, int rowbytes, int bpp, int ft, int k) {
   int a = 0, c = 0;
   for (int x0 = k; x0 < rowbytes; x0 += 8 * bpp) {
     int r[8], p[8];
@@ -398,7 +394,7 @@ PNG_HD inline void png_unfilter_chain(unsigned char* row, const unsigned char* p
 }
 
 // raw: H rows of 1 filter byte + rowbytes, unfiltered in place.  The first row's prior row is zeros.
-PNG_HD inline int png_unfilter(unsigned char* raw, int H, int rowbytes, int bpp, int lane, int nl) {
+IMG_HD inline int png_unfilter(unsigned char* raw, int H, int rowbytes, int bpp, int lane, int nl) {
   const long stride = (long)rowbytes + 1;
   for (int y = 0; y < H; ++y) {
     unsigned char* row = raw + (long)y * stride + 1;
@@ -419,7 +415,7 @@ PNG_HD inline int png_unfilter(unsigned char* raw, int H, int rowbytes, int bpp,
 // ---- pixels -------------------------------------------------------------------------------------------------------------
 // Pixel x of an unfiltered row -> out[0..3] = R, G, B, A as Pillow's convert("RGBA") gives them (convert("RGB") drops
 // A, convert("L") of a gray stream is R).  pal: the stream's 256 RGBA entries (palette streams only).
-PNG_HD inline void png_expand(const int* d, const unsigned char* row, const unsigned char* pal, int x, int out[4]) {
+IMG_HD inline void png_expand(const int* d, const unsigned char* row, const unsigned char* pal, int x, int out[4]) {
   const int depth = d[PD_DEPTH], ct = d[PD_CTYPE];
   if (ct == 0 || ct == 3) {
     int s;

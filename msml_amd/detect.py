@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, packed
 from ._lib import call
 
 COLS = 16                      # doubles per candidate row: x1 y1 x2 y2 score | image | offsets[4] / landmarks[10]
@@ -208,8 +208,8 @@ class Detector:
     @torch.no_grad()
     def detect_faces(self, images, min_face_size=64.0, thresholds=(0.6, 0.7, 0.8), nms_thresholds=(0.7, 0.7, 0.7),
                      factor=0.707, max_candidates=None):
-        """images: a list of H x W x 3 uint8 RGB arrays of any sizes, or (buf, meta) as ijb.pack_images returns them.
-        Returns Detections(boxes, landmarks, dropped): per image boxes f64 [n][5] = x1 y1 x2 y2 score and landmarks f32
+        """images: a list of H x W x 3 uint8 RGB arrays of any sizes, or (buf, meta) as ijb.pack_images returns them
+        (a meta row that is not an image inside buf is a ValueError before anything is uploaded).  Returns Detections(boxes, landmarks, dropped): per image boxes f64 [n][5] = x1 y1 x2 y2 score and landmarks f32
         [n][10] = x0..x4 y0..y4 in image coordinates, in the reference's order (descending score).  An image without a
         detection gives arrays of shape (0, 5) and (0, 10); the reference returns np.zeros([0]) for both there.
         dropped: the number of boxes that had no pixel inside their image after a calibration step -- the reference's
@@ -217,12 +217,7 @@ class Detector:
         would try to allocate that cut).  max_candidates: the PER-IMAGE capacity for P-Net
         candidates (default and upper limit: msml_det_nms_capacity()); an image with more raises CapacityError, however
         many the batch holds in all.  min_face_size: one number, or one per image ([B])."""
-        from . import ijb
-        if isinstance(images, tuple) and len(images) == 2 and isinstance(images[0], torch.Tensor):
-            buf, meta = images
-        else:
-            buf, meta = ijb.pack_images(list(images))
-        meta = np.ascontiguousarray(meta.cpu().numpy() if isinstance(meta, torch.Tensor) else meta, dtype=np.int64)
+        buf, meta = packed.sources(images, "detect_faces")     # msml_det_resample leaves the check of meta to its caller
         B = meta.shape[0]
         dev = self.device
         capacity = self.nms_capacity if max_candidates is None else int(max_candidates)

@@ -23,6 +23,7 @@ import collections
 import numpy as np
 import torch
 
+from . import packed
 from ._lib import call, value
 
 FPRS = (1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1)
@@ -317,31 +318,7 @@ def align_matrices(landmarks, out_size=112):
     return m
 
 
-def pack_images(images):
-    """images: a list of H x W x 3 uint8 arrays as cv2.imread returns them (BGR, any sizes, any strides).  Returns
-    (buf, meta): one uint8 tensor holding them back to back (pinned when a GPU is present), and meta [N][4] int64 numpy =
-    byte offset (a multiple of 4), H, W, row pitch in bytes.  Refuses an empty list, other dtypes, a channel count
-    other than 3 and H or W outside 1..32767 (cv2 saturates source coordinates to int16; that is not emulated)."""
-    if not isinstance(images, (list, tuple)) or len(images) == 0:
-        raise ValueError("pack_images: needs a non-empty list of images")
-    meta = np.empty((len(images), 4), np.int64)
-    off = 0
-    for i, im in enumerate(images):
-        if not isinstance(im, np.ndarray) or im.dtype != np.uint8:
-            raise ValueError("pack_images: image %d is not a uint8 array" % i)
-        if im.ndim != 3 or im.shape[2] != 3:
-            raise ValueError("pack_images: image %d has shape %s, not H x W x 3" % (i, tuple(im.shape)))
-        h, w = im.shape[:2]
-        if not (1 <= h <= 32767 and 1 <= w <= 32767):
-            raise ValueError("pack_images: image %d is %d x %d, outside 1..32767" % (i, h, w))
-        meta[i] = (off, h, w, 3 * w)
-        off += (h * w * 3 + 3) & ~3
-    buf = torch.empty(off, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
-    flat = buf.numpy()
-    for i, im in enumerate(images):
-        o, h, w, _ = meta[i]
-        flat[o:o + h * w * 3].reshape(h, w, 3)[...] = im
-    return buf, meta
+pack_images = packed.pack_images
 
 
 def invert_matrices(matrices):
@@ -373,22 +350,9 @@ def align_faces(buf, meta, matrices, out_size=112, bgr=True):
     source in one launch (msml_align_warp) -> uint8 [N][s][s][3] on the device.  buf / meta: pack_images' result (buf
     on the host or already on the device); matrices [N][2][3]: align_matrices' result; out_size: s or (h, w);
     bgr=False leaves the channel order alone.  meta is checked on the host against buf.numel() before anything is
-    uploaded: offsets, pitch >= 3 W, sizes in 1..32767, the last byte of every image inside the buffer."""
-    if not (isinstance(buf, torch.Tensor) and buf.dtype == torch.uint8 and buf.dim() == 1 and buf.is_contiguous()):
-        raise ValueError("align_faces: buf must be a contiguous 1-D uint8 tensor")
-    mt = meta.cpu().numpy() if isinstance(meta, torch.Tensor) else np.asarray(meta)
-    if mt.ndim != 2 or mt.shape[1] != 4 or mt.shape[0] == 0 or not np.issubdtype(mt.dtype, np.integer):
-        raise ValueError("align_faces: meta must be [N][4] integers")
-    mt = np.ascontiguousarray(mt, dtype=np.int64)
+    uploaded (packed.check)."""
+    mt = packed.check(buf, meta, "align_faces")
     n = mt.shape[0]
-    off, h, w, pitch = mt[:, 0], mt[:, 1], mt[:, 2], mt[:, 3]
-    size_ok = (h >= 1) & (h <= 32767) & (w >= 1) & (w <= 32767)
-    ok = size_ok & (off >= 0) & (off % 4 == 0) & (pitch >= 3 * w) & (pitch < 2 ** 31)
-    ok &= off + (h - 1) * pitch + 3 * w <= buf.numel()
-    if not ok.all():
-        i = int(np.flatnonzero(~ok)[0])
-        raise ValueError("align_faces: meta row %d (offset %d, %d x %d, pitch %d) does not describe an image inside "
-                         "the %d-byte buffer" % (i, off[i], h[i], w[i], pitch[i], buf.numel()))
     minv = invert_matrices(matrices)
     if minv.shape[0] != n:
         raise ValueError("align_faces: %d matrices for %d images" % (minv.shape[0], n))

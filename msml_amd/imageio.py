@@ -5,7 +5,7 @@ their own images into it: two device calls, whatever the mix."""
 import numpy as np
 import torch
 
-from . import jpeg, png
+from . import _codec, jpeg, packed, png
 
 UNKNOWN_FORMAT = 64          # the status of a byte string that is neither JPEG nor PNG
 
@@ -57,16 +57,12 @@ def decode_images(blobs, order="rgb", strict=True, device="cuda"):
         if rows[k]:
             batches[k] = pack([blobs[i] for i in rows[k]])
             host[rows[k]] = batches[k].status
-            for i, d in zip(rows[k], batches[k].descriptors):
-                if d.status == 0:
-                    hw[i] = (d.height, d.width)
+            hw[rows[k]] = _codec.extents(batches[k])
     if strict:
         for i in np.flatnonzero(host):
             raise DecodeError(i, kinds[i], host[i])
-    pitch = (hw[:, 1] * 3 + 3) & ~3
-    ends = np.cumsum(hw[:, 0] * pitch)
-    meta = np.stack([ends - hw[:, 0] * pitch, hw[:, 0], hw[:, 1], pitch], axis=1).astype(np.int64)
-    buf = torch.empty(int(ends[-1]), dtype=torch.uint8, device=device)
+    meta, total = packed.layout(hw[:, 0], hw[:, 1])
+    buf = torch.empty(total, dtype=torch.uint8, device=device)
     status = torch.from_numpy(host).to(buf.device)
     for k, mod in (("jpeg", jpeg), ("png", png)):
         if rows[k] and (batches[k].status == 0).any():

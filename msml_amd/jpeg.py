@@ -14,6 +14,8 @@ import threading
 import numpy as np
 import torch
 
+from . import _codec, packed
+from ._codec import StreamBatch, pack_streams, pinned, raise_first
 from ._lib import call, value
 
 DESC_WORDS = 32
@@ -242,37 +244,19 @@ def huffman_lookup(counts, symbols):
     return _LOOKUPS[key]
 
 
-class JpegBatch:
+class JpegBatch(StreamBatch):
     """pack_jpegs' result: everything msml_jpeg_decode reads, on the host (pinned when a GPU is present).
     streams uint8 [bytes]: the byte strings back to back at 4-byte-aligned offsets; desc int32 [N, 32]; qtabs int32
     [nq, 64] (natural order) and htabs int32 [nh, 832] (lookup form), each distinct table once; descriptors: the
     JpegDescriptor of every stream; ws_bytes: the workspace the decode needs."""
 
+    FIELDS = ("streams", "desc", "qtabs", "htabs")
+    STATUS_WORD = JD_STATUS
+
     def __init__(self, streams, desc, qtabs, htabs, descriptors, ws_bytes):
         self.streams, self.desc, self.qtabs, self.htabs = streams, desc, qtabs, htabs
         self.descriptors, self.ws_bytes = descriptors, ws_bytes
         self._dev = None
-
-    def __len__(self):
-        return self.desc.shape[0]
-
-    @property
-    def status(self):
-        return self.desc[:, JD_STATUS].numpy()
-
-    @property
-    def sizes(self):
-        return [(d.height, d.width) for d in self.descriptors]
-
-    def to_device(self, device="cuda"):
-        """(streams, desc, qtabs, htabs) on the device, copied once (non_blocking, on the current stream)."""
-        if self._dev is None or self._dev[0].device != torch.device(device):
-            self._dev = tuple(t.to(device, non_blocking=True) for t in (self.streams, self.desc, self.qtabs, self.htabs))
-        return self._dev
-
-
-def _pinned(shape, dtype):
-    return torch.empty(shape, dtype=dtype, pin_memory=torch.cuda.is_available())
 
 
 def pack_jpegs(streams, cache=None):
@@ -299,13 +283,11 @@ def pack_jpegs(streams, cache=None):
             htabs.append(huffman_lookup(*ch))
         return hidx[k]
 
-    desc = _pinned((n, DESC_WORDS), torch.int32)
+    desc = pinned((n, DESC_WORDS), torch.int32)
     dn = desc.numpy()
     dn[...] = 0
-    off = 0
-    offs = []
-    for i, (s, d) in enumerate(zip(streams, descs)):
-        offs.append(off)
+    buf, offs = pack_streams([len(s) if d.status == 0 else 0 for s, d in zip(streams, descs)], "pack_jpegs")
+    for i, (off, d) in enumerate(zip(offs, descs)):
         dn[i, JD_STATUS] = d.status
         if d.status:
             continue
@@ -318,17 +300,12 @@ def pack_jpegs(streams, cache=None):
             dn[i, JD_AC + c] = h_index(d.huffman[(1, d.acsel[c])])
         dn[i, JD_RI] = d.restart_interval
         dn[i, JD_MCUX], dn[i, JD_MCUY] = -(-d.width // (8 * hm)), -(-d.height // (8 * vm))
-        off += (len(s) + 3) & ~3
-        if off >= 2 ** 33:
-            raise ValueError("pack_jpegs: more than 8 GiB of streams in one batch")
-    buf = _pinned(max(off, 4), torch.uint8)
     flat = buf.numpy()
     for s, d, o in zip(streams, descs, offs):
         if d.status == 0:
             flat[o:o + len(s)] = np.frombuffer(bytes(s), np.uint8)
-            flat[o + len(s):(o + len(s) + 3) & ~3] = 0
-    qt = _pinned((max(len(qtabs), 1), 64), torch.int32)
-    ht = _pinned((max(len(htabs), 1), HUFF_WORDS), torch.int32)
+    qt = pinned((max(len(qtabs), 1), 64), torch.int32)
+    ht = pinned((max(len(htabs), 1), HUFF_WORDS), torch.int32)
     qt.numpy()[...] = np.stack(qtabs) if qtabs else 1
     ht.numpy()[...] = np.stack(htabs) if htabs else 0
     ws_bytes = 0
@@ -337,13 +314,6 @@ def pack_jpegs(streams, cache=None):
         if ws_bytes <= 0:
             raise RuntimeError("msml_jpeg_workspace refused the descriptors")
     return JpegBatch(buf, desc, qt, ht, descs, ws_bytes)
-
-
-def _raise_first(status, what):
-    bad = np.flatnonzero(status)
-    if bad.size:
-        i = int(bad[0])
-        raise ValueError("%s: image %d: %s (status %d)" % (what, i, STATUS.get(int(status[i]), "?"), int(status[i])))
 
 
 @torch.no_grad()
@@ -355,15 +325,7 @@ def decode_into(batch, dst, meta, channels=3, order="rgb", ws=None, status=None)
     least batch.ws_bytes (allocated when None); status: int32 [N] on the device (allocated when None), returned."""
     n = len(batch)
     device = dst.device
-    if isinstance(meta, torch.Tensor):
-        if meta.dtype != torch.int64 or tuple(meta.shape) != (n, 4) or meta.device != device or not meta.is_contiguous():
-            raise ValueError("decode_into: a meta tensor must be contiguous int64 [%d][4] on %s" % (n, device))
-        meta_dev = meta
-    else:
-        meta = np.ascontiguousarray(meta, dtype=np.int64)
-        if meta.shape != (n, 4):
-            raise ValueError("decode_into: meta must be [%d][4]" % n)
-        meta_dev = torch.from_numpy(meta).to(device)
+    meta_dev = packed.meta_on_device(meta, n, device, "decode_into")
     streams, desc, qtabs, htabs = batch.to_device(device)
     if ws is None:
         ws = torch.empty(max(batch.ws_bytes, 16), dtype=torch.uint8, device=device)
@@ -372,22 +334,6 @@ def decode_into(batch, dst, meta, channels=3, order="rgb", ws=None, status=None)
     call("msml_jpeg_decode", streams, streams.numel(), desc, batch.desc.data_ptr(), qtabs, qtabs.shape[0], htabs,
          htabs.shape[0], dst, dst.numel(), meta_dev, channels, 1 if order == "bgr" else 0, status, ws, ws.numel(), n)
     return status
-
-
-_UNIFORM_META = {}       # (n, h, w, channels, device) -> meta of a contiguous [n, h, w, channels] tensor, on the device
-
-
-def _uniform_meta(n, h, w, channels, device):
-    key = (n, h, w, channels, device)
-    m = _UNIFORM_META.get(key)
-    if m is None:
-        if len(_UNIFORM_META) >= 64:
-            _UNIFORM_META.clear()
-        meta = np.empty((n, 4), np.int64)
-        meta[:, 0] = np.arange(n, dtype=np.int64) * (h * w * channels)
-        meta[:, 1], meta[:, 2], meta[:, 3] = h, w, w * channels
-        m = _UNIFORM_META[key] = torch.from_numpy(meta).to(device)
-    return m
 
 
 @torch.no_grad()
@@ -400,45 +346,11 @@ def decode_batch(batch, size=None, order="rgb", strict=True, channels=3, device=
     strict=True: ValueError naming the first failing image and why (this reads the statuses back: a synchronisation);
     strict=False: the int32 status tensor [N] comes back as the last element instead, failing images hold unspecified
     pixels.  A batch with no supported stream launches nothing."""
-    if order not in ("rgb", "bgr"):
-        raise ValueError("decode_batch: order must be 'rgb' or 'bgr'")
-    if channels not in (1, 3):
-        raise ValueError("decode_batch: channels must be 1 or 3")
-    if not isinstance(batch, JpegBatch):
-        batch = pack_jpegs(batch)
-    n = len(batch)
-    host = batch.status
-    if strict:
-        _raise_first(host, "decode_batch")
-    ok = host == 0
-    hw = np.array([(d.height, d.width) if o else (1, 1) for d, o in zip(batch.descriptors, ok)], np.int64)
-    if channels == 1:
-        for i in np.flatnonzero(ok):
-            if batch.descriptors[i].components != 1:
-                raise ValueError("decode_batch: channels=1 takes gray streams; image %d has 3 components" % i)
-    meta = np.empty((n, 4), np.int64)
-    if size is not None:
-        h, w = int(size[0]), int(size[1])
-        for i in np.flatnonzero(ok):
-            if tuple(hw[i]) != (h, w):
-                raise ValueError("decode_batch: image %d is %d x %d, not %d x %d" % (i, hw[i, 0], hw[i, 1], h, w))
-        out = torch.empty((n, h, w, 3) if channels == 3 else (n, h, w), dtype=torch.uint8, device=device)
-        dst = out
-        meta = _uniform_meta(n, h, w, channels, out.device)      # on the device, uploaded once per shape
-    else:
-        pitch = (hw[:, 1] * channels + 3) & ~3
-        ends = np.cumsum(hw[:, 0] * pitch)
-        meta[:, 0], meta[:, 1], meta[:, 2], meta[:, 3] = ends - hw[:, 0] * pitch, hw[:, 0], hw[:, 1], pitch
-        dst = torch.empty(int(ends[-1]), dtype=torch.uint8, device=device)
-        out = (dst, meta)
-    if ok.any():
-        status = decode_into(batch, dst, meta, channels, order)
-    else:
-        status = torch.from_numpy(host.astype(np.int32)).to(device)
-    if strict:
-        _raise_first(status.cpu().numpy(), "decode_batch")
-        return out
-    return (out, status) if size is not None else out + (status,)
+    return _codec.decode_batch(_CODEC, batch, size, order, strict, channels, device)
+
+
+_CODEC = _codec.Codec(pack_jpegs, JpegBatch, (1, 3), lambda d: None if d.components == 1 else "3 components",
+                      decode_into, STATUS)
 
 
 # ---------------------------------------------------------------------------------------------------- RecordIO
@@ -587,8 +499,8 @@ def decode_renders(mask_out, mask, size, device="cuda"):
         return (torch.zeros(1, h, w, 3, dtype=torch.uint8, device=device),
                 torch.full((1, h, w), 255, dtype=torch.uint8, device=device),
                 torch.zeros(1, dtype=torch.int32, device=device))
-    _raise_first(mask_out.status, "decode_renders: mask_out")
-    _raise_first(mask.status, "decode_renders: mask")
+    raise_first(mask_out.status, "decode_renders: mask_out", STATUS)
+    raise_first(mask.status, "decode_renders: mask", STATUS)
     masked, st = decode_batch(mask_out, size=size, strict=False, device=device)
     if all(d.components == 1 for d in mask.descriptors):
         m, st2 = decode_batch(mask, size=size, strict=False, channels=1, device=device)
@@ -689,7 +601,7 @@ class EncodePlan:
 
         quality, sampling, restart = per_image(quality, "quality"), per_image(sampling, "sampling"), per_image(restart, "restart")
         self.n, self.sizes = n, [(int(h), int(w)) for h, w in sizes]
-        self.desc = _pinned((n, ENC_DESC_WORDS), torch.int32)
+        self.desc = pinned((n, ENC_DESC_WORDS), torch.int32)
         dn = self.desc.numpy()
         dn[...] = 0
         qidx, qtabs, hidx, headers, hoff = {}, [], {}, [], 0
@@ -715,10 +627,10 @@ class EncodePlan:
             dn[i, JE_QT], dn[i, JE_QT + 1] = qidx[q], qidx[q] + 1
             dn[i, JE_HOFF], dn[i, JE_HLEN] = hidx[key]
             self.bounds[i] = (value("msml_jpeg_encode_bound", h, w, SAMPLINGS[s], r, hidx[key][1]) + 3) & ~3
-        self.qtabs = _pinned((len(qtabs), 64), torch.int32)
+        self.qtabs = pinned((len(qtabs), 64), torch.int32)
         self.qtabs.numpy()[...] = np.stack(qtabs)
         hb = b"".join(headers)
-        self.headers = _pinned((len(hb) + 3) & ~3, torch.uint8)
+        self.headers = pinned((len(hb) + 3) & ~3, torch.uint8)
         self.headers.numpy()[:len(hb)] = np.frombuffer(hb, np.uint8)
         self.headers.numpy()[len(hb):] = 0
         self.ws_bytes = value("msml_jpeg_encode_workspace", self.desc.data_ptr(), n)
@@ -740,7 +652,7 @@ class EncodePlan:
         if key not in self._decode:
             n = self.n
             en = self.desc.numpy()
-            desc = _pinned((n, DESC_WORDS), torch.int32)
+            desc = pinned((n, DESC_WORDS), torch.int32)
             dn = desc.numpy()
             dn[...] = 0
             lookups = [huffman_lookup(*STD_HUFFMAN[k]) for k in ((0, 0), (1, 0), (0, 1), (1, 1))]
@@ -755,7 +667,7 @@ class EncodePlan:
                 dn[i, JD_AC:JD_AC + 3] = 1, 3, 3
                 dn[i, JD_RI] = en[i, JE_RI]
                 dn[i, JD_MCUX], dn[i, JD_MCUY] = -(-w // (8 * hm)), -(-h // (8 * vm))
-            ht = _pinned((4, HUFF_WORDS), torch.int32)
+            ht = pinned((4, HUFF_WORDS), torch.int32)
             ht.numpy()[...] = np.stack(lookups)
             ws_bytes = value("msml_jpeg_workspace", desc.data_ptr(), n)
             if ws_bytes <= 0:
@@ -873,7 +785,7 @@ def encode_batch(images, quality=75, sampling="420", restart=0, order="rgb", dev
         raise ValueError("encode: one-channel sources take sampling 'gray' only")
     if meta is None:
         h, w = sizes[0]
-        meta_dev = _uniform_meta(n, h, w, channels, src.device)
+        meta_dev = packed.uniform_meta(n, h, w, channels, src.device)
     else:
         meta_dev = torch.from_numpy(meta).to(src.device)
     caps = plan.bounds if slot_bytes is None else np.full(n, (int(slot_bytes) + 3) & ~3, np.int64)
@@ -902,7 +814,7 @@ def recompress(images, quality=75, sampling="420", order="rgb", device="cuda"):
     n, h, w = images.shape[:3]
     channels = 3 if images.dim() == 4 else 1
     out = torch.empty(tuple(images.shape), dtype=torch.uint8, device=enc.buf.device)
-    decode_into(batch, out, _uniform_meta(n, h, w, channels, out.device), channels, order)
+    decode_into(batch, out, packed.uniform_meta(n, h, w, channels, out.device), channels, order)
     return out
 
 

@@ -33,7 +33,7 @@ import functools
 import numpy as np
 import torch
 
-from . import _lib, detect, ijb
+from . import _lib, detect, ijb, packed
 from ._lib import call
 from .resample import pillow_coeffs
 
@@ -220,39 +220,11 @@ def resample_rows(insz, outsz, filter=BICUBIC):
 
 
 def _packed(images):
-    """(buf, meta numpy int64 [N][4]) of a list of RGB uint8 arrays or of a (buf, meta) pair; meta is checked against
-    the buffer's length, because the library cannot.  Nothing is uploaded."""
-    if isinstance(images, tuple) and len(images) == 2 and isinstance(images[0], torch.Tensor):
-        buf, meta = images
-    else:
-        buf, meta = ijb.pack_images(list(images))
-    if not (buf.dtype == torch.uint8 and buf.dim() == 1 and buf.is_contiguous()):
-        raise ValueError("mtcnn_align: buf must be a contiguous 1-D uint8 tensor")
-    mt = meta.cpu().numpy() if isinstance(meta, torch.Tensor) else np.asarray(meta)
-    if mt.ndim != 2 or mt.shape[1] != 4 or mt.shape[0] == 0 or not np.issubdtype(mt.dtype, np.integer):
-        raise ValueError("mtcnn_align: meta must be [N][4] integers")
-    mt = np.ascontiguousarray(mt, dtype=np.int64)
-    off, h, w, pitch = mt[:, 0], mt[:, 1], mt[:, 2], mt[:, 3]
-    ok = (h >= 1) & (h <= 32767) & (w >= 1) & (w <= 32767) & (off >= 0) & (off % 4 == 0) & (pitch >= 3 * w)
-    ok &= (pitch < 2 ** 31) & (off + (h - 1) * pitch + 3 * w <= buf.numel())
-    if not ok.all():
-        i = int(np.flatnonzero(~ok)[0])
-        raise ValueError("mtcnn_align: meta row %d (offset %d, %d x %d, pitch %d) does not describe an image inside the "
-                         "%d-byte buffer" % (i, off[i], h[i], w[i], pitch[i], buf.numel()))
-    return buf, mt
+    return packed.sources(images, "mtcnn_align")
 
 
 def _up(buf, device="cuda"):
     return buf if buf.is_cuda else buf.to(device, non_blocking=True)
-
-
-def _layout(heights, widths):
-    """meta [N][4] of new images packed back to back with rows of a multiple of 4 bytes, and the total length."""
-    heights, widths = np.asarray(heights, np.int64), np.asarray(widths, np.int64)
-    pitch = (3 * widths + 3) & ~3
-    size = heights * pitch
-    off = np.cumsum(size) - size
-    return np.ascontiguousarray(np.stack([off, heights, widths, pitch], 1)), int(size.sum())
 
 
 def _dev(a, device):
@@ -273,7 +245,7 @@ def img_orient(images, methods):
     if ((m < 0) | (m > 4)).any():
         raise ValueError("img_orient: method %d is not one of 0..4" % m[(m < 0) | (m > 4)][0])
     turn = (m == ROTATE_90) | (m == ROTATE_270)
-    meta_out, total = _layout(np.where(turn, mt[:, 2], mt[:, 1]), np.where(turn, mt[:, 1], mt[:, 2]))
+    meta_out, total = packed.layout(np.where(turn, mt[:, 2], mt[:, 1]), np.where(turn, mt[:, 1], mt[:, 2]))
     plan = np.ascontiguousarray(np.stack([m.astype(np.int64), meta_out[:, 1], meta_out[:, 2]], 1))
     buf = _up(buf)
     out = torch.empty(total, dtype=torch.uint8, device=buf.device)
@@ -301,7 +273,7 @@ def img_resize(images, sizes, filter=BICUBIC):
     ow, oh = sz[:, 0].astype(np.int64), sz[:, 1].astype(np.int64)
     if ((ow < 1) | (ow > 32767) | (oh < 1) | (oh > 32767)).any():
         raise ValueError("img_resize: an output size is outside 1..32767")
-    meta_out, total = _layout(oh, ow)
+    meta_out, total = packed.layout(oh, ow)
     hostsz = np.ascontiguousarray(np.stack([mt[:, 1], mt[:, 2], oh, ow], 1))
     ws_bytes = _lib.value("msml_img_resize_workspace", hostsz.ctypes.data, n)
     if ws_bytes <= 0:

@@ -19,6 +19,8 @@ import zlib
 import numpy as np
 import torch
 
+from . import _codec, packed
+from ._codec import StreamBatch, pack_streams, pinned
 from ._lib import call, value
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
@@ -181,35 +183,18 @@ def parse_png(data):
     return d
 
 
-class PngBatch:
+class PngBatch(StreamBatch):
     """pack_pngs' result: everything msml_png_decode reads, on the host (pinned when a GPU is present).  streams uint8
     [bytes]: each image's IDAT payloads back to back (ONE zlib stream per image) at 4-byte-aligned offsets; desc int32
     [N, 16]; palettes uint8 [np, 256, 4], each distinct palette once; descriptors; ws_bytes."""
+
+    FIELDS = ("streams", "desc", "palettes")
+    STATUS_WORD = PD_STATUS
 
     def __init__(self, streams, desc, palettes, descriptors, ws_bytes):
         self.streams, self.desc, self.palettes = streams, desc, palettes
         self.descriptors, self.ws_bytes = descriptors, ws_bytes
         self._dev = None
-
-    def __len__(self):
-        return self.desc.shape[0]
-
-    @property
-    def status(self):
-        return self.desc[:, PD_STATUS].numpy()
-
-    @property
-    def sizes(self):
-        return [(d.height, d.width) for d in self.descriptors]
-
-    def to_device(self, device="cuda"):
-        if self._dev is None or self._dev[0].device != torch.device(device):
-            self._dev = tuple(t.to(device, non_blocking=True) for t in (self.streams, self.desc, self.palettes))
-        return self._dev
-
-
-def _pinned(shape, dtype):
-    return torch.empty(shape, dtype=dtype, pin_memory=torch.cuda.is_available())
 
 
 def pack_pngs(streams):
@@ -219,17 +204,16 @@ def pack_pngs(streams):
     n = len(streams)
     descs = [parse_png(s) for s in streams]
     pidx, pals = {}, []
-    desc = _pinned((n, DESC_WORDS), torch.int32)
+    desc = pinned((n, DESC_WORDS), torch.int32)
     dn = desc.numpy()
     dn[...] = 0
-    off, offs = 0, []
-    for i, d in enumerate(descs):
-        offs.append(off)
+    lengths = [sum(b - a for a, b in d.idat) if d.status == 0 else 0 for d in descs]
+    buf, offs = pack_streams(lengths, "pack_pngs")
+    for i, (off, zl, d) in enumerate(zip(offs, lengths, descs)):
         dn[i, PD_STATUS] = d.status
         dn[i, PD_PAL] = -1
         if d.status:
             continue
-        zl = sum(b - a for a, b in d.idat)
         dn[i, PD_BASE], dn[i, PD_END] = off // 4, zl
         dn[i, PD_H], dn[i, PD_W], dn[i, PD_DEPTH], dn[i, PD_CTYPE] = d.height, d.width, d.depth, d.colour_type
         if d.colour_type == 3:
@@ -243,18 +227,13 @@ def pack_pngs(streams):
         if key is not None:
             dn[i, PD_KEY] = 1
             dn[i, PD_KEY0:PD_KEY0 + len(key)] = key
-        off += (zl + 3) & ~3
-        if off >= 2 ** 33:
-            raise ValueError("pack_pngs: more than 8 GiB of streams in one batch")
-    buf = _pinned(max(off, 4), torch.uint8)
     flat = buf.numpy()
-    flat[...] = 0
     for d, o in zip(descs, offs):
         if d.status == 0:
             for a, b in d.idat:
                 flat[o:o + b - a] = np.frombuffer(d.data, np.uint8, b - a, a)
                 o += b - a
-    pal = _pinned((max(len(pals), 1), 256, 4), torch.uint8)
+    pal = pinned((max(len(pals), 1), 256, 4), torch.uint8)
     pal.numpy()[...] = np.stack(pals) if pals else 0
     ws_bytes = 0
     if any(d.status == 0 for d in descs):
@@ -262,13 +241,6 @@ def pack_pngs(streams):
         if ws_bytes <= 0:
             raise RuntimeError("msml_png_workspace refused the descriptors")
     return PngBatch(buf, desc, pal, descs, ws_bytes)
-
-
-def _raise_first(status, what):
-    bad = np.flatnonzero(status)
-    if bad.size:
-        i = int(bad[0])
-        raise ValueError("%s: image %d: %s (status %d)" % (what, i, reason(status[i]), int(status[i])))
 
 
 @torch.no_grad()
@@ -280,15 +252,7 @@ def decode_into(batch, dst, meta, channels=3, order="rgb", ws=None, status=None)
     device (allocated when None), returned."""
     n = len(batch)
     device = dst.device
-    if isinstance(meta, torch.Tensor):
-        if meta.dtype != torch.int64 or tuple(meta.shape) != (n, 4) or meta.device != device or not meta.is_contiguous():
-            raise ValueError("decode_into: a meta tensor must be contiguous int64 [%d][4] on %s" % (n, device))
-        meta_dev = meta
-    else:
-        meta = np.ascontiguousarray(meta, dtype=np.int64)
-        if meta.shape != (n, 4):
-            raise ValueError("decode_into: meta must be [%d][4]" % n)
-        meta_dev = torch.from_numpy(meta).to(device)
+    meta_dev = packed.meta_on_device(meta, n, device, "decode_into")
     streams, desc, palettes = batch.to_device(device)
     if ws is None:
         ws = torch.empty(max(batch.ws_bytes, 16), dtype=torch.uint8, device=device)
@@ -310,44 +274,8 @@ def decode_batch(batch, size=None, order="rgb", strict=True, channels=3, device=
     strict=True: ValueError naming the first failing image and why (this reads the statuses back: a synchronisation);
     strict=False: the int32 status tensor [N] comes back as the last element instead, failing images hold unspecified
     pixels.  A batch with no supported stream launches nothing."""
-    if order not in ("rgb", "bgr"):
-        raise ValueError("decode_batch: order must be 'rgb' or 'bgr'")
-    if channels not in (1, 3, 4):
-        raise ValueError("decode_batch: channels must be 1, 3 or 4")
-    if not isinstance(batch, PngBatch):
-        batch = pack_pngs(batch)
-    n = len(batch)
-    host = batch.status
-    if strict:
-        _raise_first(host, "decode_batch")
-    ok = host == 0
-    hw = np.array([(d.height, d.width) if o else (1, 1) for d, o in zip(batch.descriptors, ok)], np.int64)
-    if channels == 1:
-        for i in np.flatnonzero(ok):
-            if batch.descriptors[i].colour_type not in (0, 4):
-                raise ValueError("decode_batch: channels=1 takes gray streams; image %d has colour type %d"
-                                 % (i, batch.descriptors[i].colour_type))
-    meta = np.empty((n, 4), np.int64)
-    if size is not None:
-        h, w = int(size[0]), int(size[1])
-        for i in np.flatnonzero(ok):
-            if tuple(hw[i]) != (h, w):
-                raise ValueError("decode_batch: image %d is %d x %d, not %d x %d" % (i, hw[i, 0], hw[i, 1], h, w))
-        out = torch.empty((n, h, w, channels) if channels != 1 else (n, h, w), dtype=torch.uint8, device=device)
-        dst = out
-        meta[:, 0] = np.arange(n, dtype=np.int64) * (h * w * channels)
-        meta[:, 1], meta[:, 2], meta[:, 3] = h, w, w * channels
-    else:
-        pitch = (hw[:, 1] * channels + 3) & ~3
-        ends = np.cumsum(hw[:, 0] * pitch)
-        meta[:, 0], meta[:, 1], meta[:, 2], meta[:, 3] = ends - hw[:, 0] * pitch, hw[:, 0], hw[:, 1], pitch
-        dst = torch.empty(int(ends[-1]), dtype=torch.uint8, device=device)
-        out = (dst, meta)
-    if ok.any():
-        status = decode_into(batch, dst, meta, channels, order)
-    else:
-        status = torch.from_numpy(host.astype(np.int32)).to(device)
-    if strict:
-        _raise_first(status.cpu().numpy(), "decode_batch")
-        return out
-    return (out, status) if size is not None else out + (status,)
+    return _codec.decode_batch(_CODEC, batch, size, order, strict, channels, device)
+
+
+_CODEC = _codec.Codec(pack_pngs, PngBatch, (1, 3, 4),
+                      lambda d: None if d.colour_type in (0, 4) else "colour type %d" % d.colour_type, decode_into, STATUS)

@@ -9,6 +9,8 @@ import struct
 import numpy as np
 
 from msml_amd import jpeg
+from tests import hostcheck
+from tests.hostcheck import host_compiler, sanitizers_link  # noqa: F401 (the tests reach them through this module)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g15_jpeg.npz")
 
@@ -275,34 +277,9 @@ CORRUPT = os.path.join(os.path.dirname(GOLDEN), "g15_jpeg_corrupt.npz")
 HOSTCHECK_SEED = 1515
 
 
-def host_compiler():
-    import shutil
-    for cc in (os.environ.get("CXX"), "g++", "clang++"):
-        if cc and shutil.which(cc):
-            return cc
-    return None
-
-
-def sanitizers_link(tmp_dir):
-    """Whether the host compiler builds and links a trivial program with -fsanitize=address,undefined (a compiler
-    without the sanitizer runtimes does not)."""
-    import subprocess
-    src = os.path.join(tmp_dir, "trivial.cpp")
-    with open(src, "w") as f:
-        f.write("int main() { return 0; }\n")
-    r = subprocess.run([host_compiler(), "-fsanitize=address,undefined", src, "-o", os.path.join(tmp_dir, "trivial")],
-                       capture_output=True)
-    return r.returncode == 0
-
-
 def build_hostcheck(out, sanitize=True):
     """Compile tools/jpeg_hostcheck.cpp with the host compiler (and the sanitizers) -> out."""
-    import subprocess
-    cmd = [host_compiler(), "-std=c++17", "-O1", "-g", HOSTCHECK_SRC, "-o", out]
-    if sanitize:
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    subprocess.run(cmd, check=True)
-    return out
+    return hostcheck.build_hostcheck(HOSTCHECK_SRC, out, sanitize)
 
 
 def write_hostcheck_input(path, cases):

@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 
 from msml_amd import jpeg
-from tests import jpeg_cases
+from tests import hostcheck
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "g16_jpeg_enc.npz")
@@ -228,11 +228,7 @@ def encode(src, sampling="420", quality=75, restart=0):
 # ------------------------------------------------------------------------------------------- the host check
 def build_hostcheck(out, sanitize=True):
     """Compile tools/jpeg_enc_hostcheck.cpp with the host compiler (and the sanitizers) -> out."""
-    cmd = [jpeg_cases.host_compiler(), "-std=c++17", "-O1", "-g", HOSTCHECK_SRC, "-o", out]
-    if sanitize:
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    subprocess.run(cmd, check=True)
-    return out
+    return hostcheck.build_hostcheck(HOSTCHECK_SRC, out, sanitize)
 
 
 def write_hostcheck_input(path, cases, random_cases=HOSTCHECK_RANDOM):

@@ -5,13 +5,14 @@ dynamic-block headers: what zlib's own encoder never emits), and an inflate in p
 exercises.  tests/test_png_cpu.py pins the restatement to the arrays Pillow gave (tests/golden/g17_png.npz) and to
 the installed Pillow; the GPU and host-check tests compare with the fixture."""
 import os
-import shutil
 import struct
 import zlib
 
 import numpy as np
 
 from msml_amd import png
+from tests import hostcheck
+from tests.hostcheck import host_compiler, sanitizers_link  # noqa: F401 (the tests reach them through this module)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "g17_png.npz")
@@ -539,32 +540,8 @@ def with_zlib_stream(data, z):
 
 
 # ------------------------------------------------------------------------------------------------ the host check
-def host_compiler():
-    for cc in (os.environ.get("CXX"), "g++", "clang++"):
-        if cc and shutil.which(cc):
-            return cc
-    return None
-
-
-def sanitizers_link(tmp_dir):
-    import subprocess
-    if host_compiler() is None:
-        return False
-    src = os.path.join(tmp_dir, "trivial.cpp")
-    with open(src, "w") as f:
-        f.write("int main() { return 0; }\n")
-    r = subprocess.run([host_compiler(), "-fsanitize=address,undefined", src, "-o", os.path.join(tmp_dir, "trivial")],
-                       capture_output=True)
-    return r.returncode == 0
-
-
 def build_hostcheck(out, sanitize=True):
-    import subprocess
-    cmd = [host_compiler(), "-std=c++17", "-O1", "-g", HOSTCHECK_SRC, "-o", out]
-    if sanitize:
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    subprocess.run(cmd, check=True)
-    return out
+    return hostcheck.build_hostcheck(HOSTCHECK_SRC, out, sanitize)
 
 
 def write_hostcheck_input(path, cases, muts=()):

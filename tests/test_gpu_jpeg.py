@@ -11,9 +11,10 @@ import torch
 
 from msml_amd import _lib, data, ijb, jpeg, verification
 from tests import jpeg_cases as J
+from tests import jpeg_enc_cases as E
+from tests.packed_cases import FILL, bands_untouched, batch_sizes, decode_at, guarded, packed_meta, unpack
 
 pytestmark = pytest.mark.gpu
-GUARD = 64
 _CACHE = {}
 
 
@@ -24,40 +25,10 @@ def golden():
     return _CACHE["g"]
 
 
-def guarded(total, fill=0xA5):
-    whole = torch.full((total + 2 * GUARD,), fill, dtype=torch.uint8, device="cuda")
-    return whole, whole[GUARD:GUARD + total]
-
-
-def bands_untouched(whole, fill=0xA5):
-    h = whole.cpu().numpy()
-    return bool((h[:GUARD] == fill).all() and (h[-GUARD:] == fill).all())
-
-
-def packed_meta(batch, channels=3):
-    hw = np.array([(d.height, d.width) if d.status == 0 else (1, 1) for d in batch.descriptors], np.int64)
-    pitch = (hw[:, 1] * channels + 3) & ~3
-    ends = np.cumsum(hw[:, 0] * pitch)
-    return np.stack([ends - hw[:, 0] * pitch, hw[:, 0], hw[:, 1], pitch], 1), int(ends[-1])
-
-
-def unpack(buf, meta, channels=3, check_pad=True):
-    """The images of a packed output; the bytes between the row and its pitch must be 0."""
-    flat = buf.cpu().numpy()
-    out = []
-    for off, h, w, pitch in np.asarray(meta):
-        rows = flat[off:off + h * pitch].reshape(h, pitch)
-        if check_pad:
-            assert (rows[:, w * channels:] == 0).all()
-        img = rows[:, :w * channels]
-        out.append(img.reshape(h, w, 3) if channels == 3 else img.reshape(h, w))
-    return out
-
-
 def decode_guarded(streams, channels=3, order="rgb"):
     """One packed launch into guarded dst and workspace -> (images, status numpy); asserts the guard bands."""
     batch = jpeg.pack_jpegs(streams)
-    meta, total = packed_meta(batch, channels)
+    meta, total = packed_meta(batch_sizes(batch), channels)
     dwhole, dst = guarded(total)
     wwhole, ws = guarded(batch.ws_bytes, 0x5C)
     status = jpeg.decode_into(batch, dst, meta, channels, order, ws=ws)
@@ -202,10 +173,37 @@ def test_corrupt_streams_as_the_host_check():
         jpeg.decode_batch([neighbours[1]["data"], cut[5], neighbours[2]["data"]])
 
 
+def test_unaligned_destinations_inside_canaries():
+    """The byte path of the store (an offset or a pitch that is no multiple of 4) next to canaries: rectangles at offset
+    5 with pitch = row bytes + 3 get the fixture's pixels and leave every byte between a row's end and its pitch alone;
+    at offset 8 with whole dwords per row those bytes are 0.  Every W mod 4 and W < 4; the fixture has no width = 2
+    (mod 4), so those streams are made here by the restated encoder and decoder (tests/jpeg_enc_cases.py,
+    tests/jpeg_cases.py), which the CPU tests pin to Pillow."""
+    _, sup, by = golden()
+    picked = [c for c in sup if c["name"].startswith(("1x1_", "9x1_", "5x2_", "3x40_", "8x8_"))]
+    assert len(picked) == 80 and {c["pixels"].shape[1] % 4 for c in picked} == {0, 1, 3}
+    cases = [(c["data"], c["pixels"]) for c in picked + [by["mcu1_17x23_420_q75_r1"]]]
+    rng = np.random.RandomState(18)
+    for h, w in ((3, 6), (2, 2)):
+        src = rng.randint(0, 256, (h, w, 3)).astype(np.uint8)
+        for sampling in ("444", "422", "420", "gray"):
+            data = E.encode(src, sampling, 75)
+            cases.append((data, J.decode(data)))
+    assert {px.shape[1] % 4 for _, px in cases} == {0, 1, 2, 3}
+    gray = [(data, px) for data, px in cases if px.ndim == 2]
+    assert len(gray) == 22
+    for channels, cs in ((3, cases), (1, gray)):
+        batch = jpeg.pack_jpegs([data for data, _ in cs])
+        for offset, extra, pad in ((5, 3, FILL), (8, None, 0)):
+            imgs = decode_at(batch, jpeg.decode_into, channels, offset, extra, pad)
+            for i, ((_, px), img) in enumerate(zip(cs, imgs)):
+                assert np.array_equal(img, J.as_rgb(px) if channels == 3 else px), (channels, offset, i)
+
+
 def test_abi_errors():
     _, sup, by = golden()
     batch = jpeg.pack_jpegs([by["face0_112x112_420_q95_r3"]["data"], by["9x3_422_q75_r3"]["data"]])
-    meta, total = packed_meta(batch)
+    meta, total = packed_meta(batch_sizes(batch))
     streams, desc, qt, ht = batch.to_device(torch.device("cuda", 0))
     dst = torch.zeros(total + 8, dtype=torch.uint8, device="cuda")
     ws = torch.zeros(batch.ws_bytes + 16, dtype=torch.uint8, device="cuda")

@@ -10,9 +10,9 @@ import torch
 from msml_amd import _lib, jpeg
 from tests import jpeg_cases as J
 from tests import jpeg_enc_cases as E
+from tests.packed_cases import bands_untouched, guarded
 
 pytestmark = pytest.mark.gpu
-GUARD = 64
 _CACHE = {}
 
 
@@ -28,16 +28,6 @@ def uniform_faces():
     cs = [c for c in cases if c["name"].startswith("uniform")]
     assert len(cs) == 4
     return cs
-
-
-def guarded(total, fill=0xA5):
-    whole = torch.full((total + 2 * GUARD,), fill, dtype=torch.uint8, device="cuda")
-    return whole, whole[GUARD:GUARD + total]
-
-
-def bands_untouched(whole, fill=0xA5):
-    h = whole.cpu().numpy()
-    return bool((h[:GUARD] == fill).all() and (h[-GUARD:] == fill).all())
 
 
 def encode_guarded(cases, caps=None, meta_edit=None, src_cut=0):

@@ -249,7 +249,7 @@ def _check(det_boxes, det_marks, want, tol):
 
 
 @pytest.mark.parametrize("which", ["small", "large"])
-def test_detect_faces_end_to_end(which):
+def test_detect_faces_end_to_end(which, monkeypatch):
     g, w, det = fixtures()
     mfs = float(g["mfs_" + which])
     gray = np.full((40, 40, 3), 128, np.uint8)
@@ -271,6 +271,18 @@ def test_detect_faces_end_to_end(which):
         assert np.array_equal(one.boxes[0], res.boxes[i]) and np.array_equal(one.landmarks[0], res.landmarks[i]), i
     pts, found = detect.first_landmarks(res.landmarks)
     assert found.tolist() == [True, True, False] and pts[0, 0, 0] == res.landmarks[0][0, 0]
+    # a caller's (buf, meta) with a row past the buffer is refused on the host, before anything is uploaded or launched
+    from msml_amd import ijb
+
+    def no_call(*a, **k):
+        raise AssertionError("a launch for a meta row that is not an image inside the buffer")
+
+    buf, meta = ijb.pack_images([g["face"]])
+    assert len(det.detect_faces((buf.cuda(), meta), min_face_size=mfs).boxes[0]) == 1
+    meta[0, 1] += 1
+    monkeypatch.setattr(detect, "call", no_call)
+    with pytest.raises(ValueError, match="detect_faces: meta row 0"):
+        det.detect_faces((buf.cuda(), meta), min_face_size=mfs)
 
 
 def test_candidate_capacity_overflow_is_an_error():

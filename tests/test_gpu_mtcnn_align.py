@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 import torch
 
-from msml_amd import _lib, detect, ijb, mtcnn_align as MA
+from msml_amd import _lib, detect, ijb, mtcnn_align as MA, packed
 from tests import align_cases as A
 from tests import mtcnn_align_cases as C
+from tests import packed_cases as P
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -45,25 +46,18 @@ def ulp_bound(m):
 
 
 def guarded(total):
-    """A 0xA5 buffer with `total` bytes between two guard bands, and the view of the middle."""
-    whole = torch.full((total + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    return whole, whole[GUARD:GUARD + total]
+    return P.guarded(total, guard=GUARD)
 
 
 def bands_untouched(whole):
-    h = whole.cpu().numpy()
-    return bool((h[:GUARD] == 0xA5).all() and (h[-GUARD:] == 0xA5).all())
+    return P.bands_untouched(whole, guard=GUARD)
 
 
 def unpack_checked(buf, meta):
-    """The images of a packed output; the bytes between 3 W and the pitch must be 0."""
-    flat = buf.cpu().numpy()
-    out = []
+    """The images of a packed output with rows of whole dwords; the bytes between 3 W and the pitch must be 0."""
     for o, h, w, p in meta:
-        rows = flat[o:o + h * p].reshape(h, p)
-        assert p % 4 == 0 and o % 4 == 0 and 0 <= p - 3 * w < 4 and not rows[:, 3 * w:].any()
-        out.append(rows[:, :3 * w].reshape(h, w, 3).copy())
-    return out
+        assert p % 4 == 0 and o % 4 == 0 and 0 <= p - 3 * w < 4
+    return P.unpack(buf, meta)
 
 
 def test_orient_every_method_bit_exact_with_guard_bands():
@@ -77,7 +71,7 @@ def test_orient_every_method_bit_exact_with_guard_bands():
     for shift in range(5):                                      # every (image, method) pair; methods differ inside a launch
         methods = np.array([(shift + k) % 5 for k in range(3)], np.int64)
         turn = (methods == 2) | (methods == 4)
-        meta_out, total = MA._layout(np.where(turn, meta[:, 2], meta[:, 1]), np.where(turn, meta[:, 1], meta[:, 2]))
+        meta_out, total = packed.layout(np.where(turn, meta[:, 2], meta[:, 1]), np.where(turn, meta[:, 1], meta[:, 2]))
         plan = np.ascontiguousarray(np.stack([methods, meta_out[:, 1], meta_out[:, 2]], 1))
         whole, out = guarded(total)
         _lib.call("msml_img_orient", src, src.numel(), dev(meta), dev(methods.astype(np.int32)), out, dev(meta_out),
@@ -128,7 +122,7 @@ def test_resize_guard_bands_and_workspace():
     images = [g["face"], A.smooth_image(37, 53)]
     sizes = np.array([(31, 50), (97, 30)], np.int64)
     buf, meta = ijb.pack_images(images)
-    meta_out, total = MA._layout(sizes[:, 1], sizes[:, 0])
+    meta_out, total = packed.layout(sizes[:, 1], sizes[:, 0])
     hostsz = np.ascontiguousarray(np.stack([meta[:, 1], meta[:, 2], sizes[:, 1], sizes[:, 0]], 1))
     ws_bytes = _lib.value("msml_img_resize_workspace", hostsz.ctypes.data, 2)
     assert ws_bytes == 112 * 96 + 37 * 292

@@ -13,10 +13,9 @@ import torch
 from msml_amd import _lib, ijb, imageio, jpeg, png, verification
 from tests import jpeg_cases as J
 from tests import png_cases as P
+from tests.packed_cases import FILL, bands_untouched, batch_sizes, canaries_intact, decode_at, guarded, packed_meta, unpack
 
 pytestmark = pytest.mark.gpu
-GUARD = 64
-FILL = 0xA5
 _CACHE = {}
 
 
@@ -27,54 +26,10 @@ def golden():
     return _CACHE["g"]
 
 
-def guarded(total, fill=FILL):
-    whole = torch.full((total + 2 * GUARD,), fill, dtype=torch.uint8, device="cuda")
-    return whole, whole[GUARD:GUARD + total]
-
-
-def bands_untouched(whole, fill=FILL):
-    h = whole.cpu().numpy()
-    return bool((h[:GUARD] == fill).all() and (h[-GUARD:] == fill).all())
-
-
-def packed_meta(batch, channels=3, gap=32):
-    """Rectangles `gap` bytes apart (a canary between every two of them), pitches rounded up to dwords."""
-    hw = np.array([(d.height, d.width) if d.status == 0 else (1, 1) for d in batch.descriptors], np.int64)
-    pitch = (hw[:, 1] * channels + 3) & ~3
-    ends = np.cumsum(hw[:, 0] * pitch + gap)
-    return np.stack([ends - hw[:, 0] * pitch, hw[:, 0], hw[:, 1], pitch], 1), int(ends[-1])
-
-
-def canaries_intact(buf, meta):
-    """Every byte of buf outside the rectangles of meta still holds the fill."""
-    flat = buf.cpu().numpy()
-    outside = np.ones(flat.size, bool)
-    for off, h, w, pitch in np.asarray(meta):
-        outside[off:off + h * pitch] = False
-    return bool((flat[outside] == FILL).all()) and int(outside.sum()) >= 32 * len(meta)
-
-
-def unpack(buf, meta, channels=3, ok=None):
-    """The images of a packed output.  Of an image that decoded, the bytes between the row and its pitch must be 0; of
-    one with a status (ok[i] false), every byte of the rectangle must still hold the fill."""
-    flat = buf.cpu().numpy()
-    out = []
-    for i, (off, h, w, pitch) in enumerate(np.asarray(meta)):
-        rows = flat[off:off + h * pitch].reshape(h, pitch)
-        if ok is not None and not ok[i]:
-            assert (rows == FILL).all(), "image %d has a status, yet its rectangle was written" % i
-            out.append(None)
-            continue
-        assert (rows[:, w * channels:] == 0).all()
-        img = rows[:, :w * channels]
-        out.append(img.reshape(h, w, channels) if channels != 1 else img.reshape(h, w))
-    return out
-
-
 def decode_guarded(streams, channels=3, order="rgb"):
     """One packed launch into a guarded, pre-filled dst and a guarded workspace -> ((dst, meta), status numpy)."""
     batch = png.pack_pngs(streams)
-    meta, total = packed_meta(batch, channels)
+    meta, total = packed_meta(batch_sizes(batch), channels, gap=32)
     dwhole, dst = guarded(total)
     wwhole, ws = guarded(batch.ws_bytes, 0x5C)
     status = png.decode_into(batch, dst, meta, channels, order, ws=ws)
@@ -205,10 +160,28 @@ def test_unsupported_streams(monkeypatch):
         png.decode_batch(bad)
 
 
+def test_unaligned_destinations_inside_canaries():
+    """The byte path of the store (an offset or a pitch that is no multiple of 4) next to canaries: rectangles at offset
+    5 with pitch = row bytes + 3 get the fixture's pixels and leave every byte between a row's end and its pitch alone;
+    at offset 8 with whole dwords per row those bytes are 0.  Every W mod 4 and W < 4."""
+    _, sup, by = golden()
+    picked = [c for c in sup if any(k in c["name"] for k in ("_1x1_", "_7x1_", "_3x5_", "_1x7_"))]
+    picked += [by["paeth_ties_8x8"], by["rgb_150x150_level0"]]
+    assert len(picked) == 20 and {c["RGB"].shape[1] % 4 for c in picked} == {0, 1, 2, 3}
+    for channels, mode in ((1, "L"), (3, "RGB"), (4, "RGBA")):
+        cs = [c for c in picked if mode in c]
+        assert len(cs) >= 7
+        batch = png.pack_pngs([c["data"] for c in cs])
+        for offset, extra, pad in ((5, 3, FILL), (8, None, 0)):
+            imgs = decode_at(batch, png.decode_into, channels, offset, extra, pad)
+            for c, img in zip(cs, imgs):
+                assert np.array_equal(img, c[mode]), (mode, offset, c["name"])
+
+
 def test_abi_errors():
     _, sup, by = golden()
     batch = png.pack_pngs([by["rgb_112x112_pillow"]["data"], by["ct3_d4_17x13_cycle"]["data"]])
-    meta, total = packed_meta(batch, gap=0)
+    meta, total = packed_meta(batch_sizes(batch))
     streams, desc, pal = batch.to_device(torch.device("cuda", 0))
     dst = torch.zeros(total + 8, dtype=torch.uint8, device="cuda")
     ws = torch.zeros(batch.ws_bytes + 16, dtype=torch.uint8, device="cuda")

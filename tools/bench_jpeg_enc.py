@@ -24,7 +24,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from bench_jpeg import kernel_shares, timed  # noqa: E402
-from msml_amd import jpeg  # noqa: E402
+from msml_amd import jpeg, packed  # noqa: E402
 
 
 def make_faces(distinct, seed=5):
@@ -74,7 +74,7 @@ def main():
         ws = torch.empty(plan.ws_bytes, dtype=torch.uint8, device="cuda")
         length = torch.empty(n, dtype=torch.int32, device="cuda")
         status = torch.empty(n, dtype=torch.int32, device="cuda")
-        meta = jpeg._uniform_meta(n, 112, 112, 3, src.device)
+        meta = packed.uniform_meta(n, 112, 112, 3, src.device)
         sdev = torch.from_numpy(slots).cuda()
         flat = src.reshape(-1)
 

@@ -7,7 +7,8 @@
 // Every workspace and every slot is a heap block of exactly its size, so a write outside one is an ASan report.  After
 // the fixture's cases come `random` images of random sizes, samplings, restart intervals, channel counts and pitches,
 // each encoded into a slot of the bound (checked: status 0, length within the bound, two runs equal) and into a slot one
-// byte too small (checked: status 2, length 0).  stdout: "R <random cases> <failures>".
+// byte too small (checked: status 2, length 0).  Last, the rules of img_rect_ok on hand-made meta rows.
+// stdout: "R <random cases> <failures>".
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,7 +47,7 @@ static int encode_one(const int* d, const unsigned char* src, long src_bytes, co
   uint32_t div[2][64], rcp[2][64];
   for (int t = 0; t < 2; ++t)
     for (int k = 0; k < 64; ++k) {
-      div[t][k] = 8u * (uint32_t)qtabs[(long)d[JE_QT + t] * 64 + jpe_natural(k)];
+      div[t][k] = 8u * (uint32_t)qtabs[(long)d[JE_QT + t] * 64 + img_zigzag(k)];
       rcp[t][k] = jpe_recip(div[t][k]);
     }
   // k_jpeg_enc_dct
@@ -71,7 +72,7 @@ static int encode_one(const int* d, const unsigned char* src, long src_bytes, co
             jpe_fdct(blk);
             const int tb = comp ? 1 : 0;
             for (int k = 0; k < 64; ++k)
-              out[k] = (int16_t)jpe_quant(blk[jpe_natural(k)], div[tb][k], rcp[tb][k], k ? 1023 : 1024);
+              out[k] = (int16_t)jpe_quant(blk[img_zigzag(k)], div[tb][k], rcp[tb][k], k ? 1023 : 1024);
             dc[t] = out[0];
             memset(ubuf + b * (JPE_BLOCK_BYTES / 4), 0, JPE_BLOCK_BYTES);
           } else if (pass == 1 && dummy) {
@@ -221,6 +222,39 @@ int main(int argc, char** argv) {
       ++failures;
       fprintf(stderr, "random case %d failed: samp %d %dx%d ri %d status %d %d length %d %d\n", i, d[JE_SAMP], d[JE_W],
               d[JE_H], d[JE_RI], sa, sb, la, lb);
+    }
+  }
+  // img_rect_ok (csrc/packed_image.h), the rule behind jpe_source_ok and the decoders' destination check: a 5 x 7 image
+  // with rows of 21 bytes at offset 8 with pitch 24 ends at byte 8 + 4 * 24 + 21 = 125 for a reader, at 128 for a
+  // writer that fills its rows up to the pitch.
+  {
+    struct Rect { long mt[4]; long last, bytes; bool ok; };
+    const long huge = 0x7fffffffL;
+    const Rect rects[] = {
+        {{8, 5, 7, 24}, 21, 125, true},        {{8, 5, 7, 24}, 21, 124, false},      // the last row one byte past the buffer
+        {{8, 5, 7, 24}, 24, 128, true},        {{8, 5, 7, 24}, 24, 127, false},      // the same for a writer
+        {{5, 5, 7, 24}, 21, 122, true},        {{5, 5, 7, 24}, 21, 121, false},      // any offset: alignment is the caller's
+        {{-4, 5, 7, 24}, 21, 4096, false},     {{4100, 5, 7, 24}, 21, 4096, false},  // an offset outside the buffer
+        {{8, 5, 7, 20}, 21, 4096, false},      {{8, 5, 7, 21}, 21, 4096, true},      // pitch < row bytes
+        {{0, 5, 7, huge}, 21, 0x7fffffffffffL, true},
+        {{0, 5, 7, huge + 1}, 21, 0x7fffffffffffL, false},                           // pitch >= 2^31
+        {{8, 0, 7, 24}, 21, 4096, false},      {{8, 5, 0, 24}, 21, 4096, false},     // H or W that is not the image's
+        {{8, 32768, 7, 24}, 21, 0x7fffffffffffL, false}, {{8, 5, 32768, 98304}, 21, 0x7fffffffffffL, false},
+        {{0, 5, 7, 24}, 21, 0, false},         {{0x7ffffffffffffff0L, 5, 7, 24}, 21, 0x7fffffffffffffffL, false},
+    };
+    for (const Rect& r : rects)
+      if (img_rect_ok(r.mt, 5, 7, 21, r.last, r.bytes) != r.ok) {
+        ++failures;
+        fprintf(stderr, "img_rect_ok(offset %ld, %ld x %ld, pitch %ld; last row %ld, buffer %ld) is not %d\n", r.mt[0],
+                r.mt[1], r.mt[2], r.mt[3], r.last, r.bytes, (int)r.ok);
+      }
+    // H or W of 0 and of 32768 as the image's own size never reach the device (the descriptor checks refuse them);
+    // the sizes the subtraction argument allows do not overflow at their largest
+    const long big[4] = {0, 32767, 32767, huge};
+    if (!img_rect_ok(big, 32767, 32767, 32767L * 4, huge, 32767L * huge) ||
+        img_rect_ok(big, 32767, 32767, 32767L * 4, huge, 32767L * huge - 1)) {
+      ++failures;
+      fprintf(stderr, "img_rect_ok fails at the largest sizes\n");
     }
   }
   printf("R %d %d\n", nrandom, failures);

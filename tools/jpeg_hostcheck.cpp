@@ -24,7 +24,7 @@ struct HostSink {
   int16_t* coef;
   int16_t blk[64];
   void begin() { memset(blk, 0, sizeof(blk)); }
-  void put(int k, int v) { blk[jpg_natural(k)] = (int16_t)v; }
+  void put(int k, int v) { blk[img_zigzag(k)] = (int16_t)v; }
   void end(long b) { memcpy(coef + b * 64, blk, sizeof(blk)); }
 };
 
