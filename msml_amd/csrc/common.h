@@ -220,6 +220,10 @@ __device__ __forceinline__ Vec8 round8<unsigned short>(const Vec8& v) {
   return r;
 }
 
+// Low part of a split-bf16 value (x3.hip) whose high part is hi = bf16(v): v - hi, and 0 where hi is infinite (inf - inf is
+// a NaN: the pair would read back as a NaN where the f32 path keeps the infinity).  A NaN hi keeps its NaN.
+__device__ __forceinline__ float x3_lo(float v, float hi) { return __builtin_isinf(hi) ? 0.f : v - hi; }
+
 // ---- BatchNorm(+PReLU) applied to a conv operand while it sits in LDS ----------------------------
 // The halo kernels (conv_halo / conv_ws / wgrad_halo) keep the input image in LDS for all 9 taps, so
 // a training-mode BatchNorm in front of the conv can be applied there (each wave transforms the 16-B

@@ -469,7 +469,7 @@ __global__ void __launch_bounds__(WGM * WGN * 64, FUSE ? 2 : 1) k_conv_fast(cons
           const Vec8 hi = round8<unsigned short>(a);
           Vec8 lo;
 #pragma unroll
-          for (int q = 0; q < 8; q++) lo.v[q] = a.v[q] - hi.v[q];
+          for (int q = 0; q < 8; q++) lo.v[q] = x3_lo(a.v[q], hi.v[q]);
           store8<unsigned short>(o16 + o, hi);
           store8<unsigned short>(o16 + o + p.coutp, lo);
           store8<unsigned short>(o16 + o + 2 * p.coutp, hi);

@@ -88,6 +88,7 @@ static inline int fm_grid(long n8) {
 extern "C" int msml_fm_fuse_fwd(const void* x, const void* yf, void* z, long n, int act,
                                 int arith, int dtype, void* stream) {
   MSML_CHECK(n > 0 && n % 8 == 0, MSML_ERR_SHAPE, "fm_fuse_fwd: n=%ld must be a positive multiple of 8", n);
+  MSML_CHECK(x && yf && z, MSML_ERR_SHAPE, "fm_fuse_fwd: null pointer");
   MSML_CHECK(act >= 0 && act <= 1 && arith >= 0 && arith <= 3, MSML_ERR_UNSUPPORTED,
              "fm_fuse_fwd: act=%d arith=%d", act, arith);
   long n8 = n / 8;
@@ -102,6 +103,7 @@ extern "C" int msml_fm_fuse_fwd(const void* x, const void* yf, void* z, long n, 
 extern "C" int msml_fm_fuse_bwd(const void* dz, const void* x, const void* yf, void* dx, void* dyf,
                                 long n, int act, int arith, int dtype, void* stream) {
   MSML_CHECK(n > 0 && n % 8 == 0, MSML_ERR_SHAPE, "fm_fuse_bwd: n=%ld must be a positive multiple of 8", n);
+  MSML_CHECK(dz && x && yf && dx && dyf, MSML_ERR_SHAPE, "fm_fuse_bwd: null pointer");
   MSML_CHECK(act >= 0 && act <= 1 && arith >= 0 && arith <= 3, MSML_ERR_UNSUPPORTED,
              "fm_fuse_bwd: act=%d arith=%d", act, arith);
   long n8 = n / 8;
@@ -245,9 +247,13 @@ __global__ void __launch_bounds__(256) k_dropout(const T* __restrict__ x, T* __r
 }
 
 #define EW_CHECK(name) MSML_CHECK(n > 0 && n % 8 == 0, MSML_ERR_SHAPE, name ": n=%ld must be a positive multiple of 8", n)
+#define EW_PTRS(name, ok) MSML_CHECK(ok, MSML_ERR_SHAPE, name ": null pointer")
+#define EW_ACT(name) MSML_CHECK(act >= 0 && act <= 1, MSML_ERR_UNSUPPORTED, name ": act=%d", act)
 
 extern "C" int msml_fm_act_fwd(const void* x, void* m, long n, int act, int dtype, void* stream) {
   EW_CHECK("fm_act_fwd");
+  EW_PTRS("fm_act_fwd", x && m);
+  EW_ACT("fm_act_fwd");
   MSML_DISPATCH_DTYPE(dtype, "fm_act_fwd",
                       (k_act_fwd<DT>)<<<fm_grid(n / 8), 256, 0, (hipStream_t)stream>>>((const DT*)x, (DT*)m, n / 8, act);)
   MSML_LAUNCH_OK("fm_act_fwd");
@@ -255,6 +261,8 @@ extern "C" int msml_fm_act_fwd(const void* x, void* m, long n, int act, int dtyp
 }
 extern "C" int msml_fm_act_bwd(const void* dm, const void* x, void* dx, long n, int act, int dtype, void* stream) {
   EW_CHECK("fm_act_bwd");
+  EW_PTRS("fm_act_bwd", dm && x && dx);
+  EW_ACT("fm_act_bwd");
   MSML_DISPATCH_DTYPE(dtype, "fm_act_bwd", (k_act_bwd<DT>)<<<fm_grid(n / 8), 256, 0, (hipStream_t)stream>>>(
                                                (const DT*)dm, (const DT*)x, (DT*)dx, n / 8, act);)
   MSML_LAUNCH_OK("fm_act_bwd");
@@ -262,6 +270,7 @@ extern "C" int msml_fm_act_bwd(const void* dm, const void* x, void* dx, long n, 
 }
 extern "C" int msml_mul_fwd(const void* a, const void* b, void* out, long n, int dtype, void* stream) {
   EW_CHECK("mul_fwd");
+  EW_PTRS("mul_fwd", a && b && out);
   MSML_DISPATCH_DTYPE(dtype, "mul_fwd", (k_mul_fwd<DT>)<<<fm_grid(n / 8), 256, 0, (hipStream_t)stream>>>(
                                             (const DT*)a, (const DT*)b, (DT*)out, n / 8);)
   MSML_LAUNCH_OK("mul_fwd");
@@ -270,6 +279,7 @@ extern "C" int msml_mul_fwd(const void* a, const void* b, void* out, long n, int
 extern "C" int msml_mul_bwd(const void* g, const void* a, const void* b, void* da, void* db, long n, int dtype,
                             void* stream) {
   EW_CHECK("mul_bwd");
+  EW_PTRS("mul_bwd", g && a && b);                     // da, db: either may be null
   MSML_DISPATCH_DTYPE(dtype, "mul_bwd", (k_mul_bwd<DT>)<<<fm_grid(n / 8), 256, 0, (hipStream_t)stream>>>(
                                             (const DT*)g, (const DT*)a, (const DT*)b, (DT*)da, (DT*)db, n / 8);)
   MSML_LAUNCH_OK("mul_bwd");
@@ -277,6 +287,7 @@ extern "C" int msml_mul_bwd(const void* g, const void* a, const void* b, void* d
 }
 extern "C" int msml_axpb(const void* x, void* y, long n, float a, float b, int dtype, void* stream) {
   EW_CHECK("axpb");
+  EW_PTRS("axpb", x && y);
   MSML_DISPATCH_DTYPE(dtype, "axpb",
                       (k_axpb<DT>)<<<fm_grid(n / 8), 256, 0, (hipStream_t)stream>>>((const DT*)x, (DT*)y, n / 8, a, b);)
   MSML_LAUNCH_OK("axpb");
@@ -285,6 +296,7 @@ extern "C" int msml_axpb(const void* x, void* y, long n, float a, float b, int d
 extern "C" int msml_mse_fwd(const void* a, const void* b, long n, double count, float* loss, double* workspace,
                             long ws_doubles, int dtype, void* stream) {
   EW_CHECK("mse_fwd");
+  EW_PTRS("mse_fwd", a && b);
   const int nb = fm_grid(n / 8);
   MSML_CHECK(loss && workspace && ws_doubles >= nb && count > 0, MSML_ERR_WORKSPACE, "mse_fwd: workspace of %ld doubles, need %d",
              ws_doubles, nb);
@@ -297,6 +309,8 @@ extern "C" int msml_mse_fwd(const void* a, const void* b, long n, double count, 
 extern "C" int msml_mse_bwd(const void* a, const void* b, const float* g, double count, void* da, void* db, long n,
                             int dtype, void* stream) {
   EW_CHECK("mse_bwd");
+  EW_PTRS("mse_bwd", a && b && g);                     // da, db: either may be null
+  MSML_CHECK(count > 0, MSML_ERR_SHAPE, "mse_bwd: count=%f", count);
   MSML_DISPATCH_DTYPE(dtype, "mse_bwd", (k_mse_bwd<DT>)<<<fm_grid(n / 8), 256, 0, (hipStream_t)stream>>>(
                                             (const DT*)a, (const DT*)b, g, (float)(2.0 / count), (DT*)da, (DT*)db, n / 8);)
   MSML_LAUNCH_OK("mse_bwd");
@@ -304,6 +318,7 @@ extern "C" int msml_mse_bwd(const void* a, const void* b, const float* g, double
 }
 extern "C" int msml_dropout(const void* x, void* y, long n, float p, long seed, int dtype, void* stream) {
   EW_CHECK("dropout");
+  EW_PTRS("dropout", x && y);
   MSML_CHECK(p >= 0.f && p < 1.f, MSML_ERR_SHAPE, "dropout: p=%f", p);
   MSML_DISPATCH_DTYPE(dtype, "dropout", (k_dropout<DT>)<<<fm_grid(n / 8), 256, 0, (hipStream_t)stream>>>(
                                             (const DT*)x, (DT*)y, n / 8, p, (unsigned long long)seed, nullptr);)
@@ -312,6 +327,7 @@ extern "C" int msml_dropout(const void* x, void* y, long n, float p, long seed, 
 }
 extern "C" int msml_dropout_dev(const void* x, void* y, long n, float p, const long* seed, int dtype, void* stream) {
   EW_CHECK("dropout_dev");
+  EW_PTRS("dropout_dev", x && y);
   MSML_CHECK(seed && p >= 0.f && p < 1.f, MSML_ERR_SHAPE, "dropout_dev: p=%f", p);
   MSML_DISPATCH_DTYPE(dtype, "dropout_dev", (k_dropout<DT>)<<<fm_grid(n / 8), 256, 0, (hipStream_t)stream>>>(
                                                 (const DT*)x, (DT*)y, n / 8, p, 0ULL, seed);)

@@ -122,6 +122,10 @@ __global__ void __launch_bounds__(256) k_seg_sums(const float* __restrict__ logi
 // mean_all: the blob mean divides by H * W instead of the blob's pixel count (reduce_pixel = 'all',
 // consensus_loss.py:131-133); kl_all: the consensus term is averaged over N * H * W instead of the non-zero entries
 // (reduce_pixel_kl = 'all', :159-160).
+// Domain.  Mask values are 0 or 1.  Without kl_all the consensus term is divided by 2 * sup (two classes per pixel of the
+// blob) where the reference counts the non-zero entries of p * I: the two agree while no f32 softmax probability of a
+// pixel underflows to 0, i.e. for |logit_0 - logit_1| < 87 (the probabilities are >= 9e-14 at |difference| <= 30, the
+// range the direct tests draw); beyond it the reference's count shrinks and log p = -inf enters both.
 __global__ void k_seg_loss(const float* __restrict__ sums, int N, float alpha, float beta,
                            float* __restrict__ loss, float* __restrict__ coef, int HW, int mean_all, int kl_all) {
   __shared__ double sh_sup[2], sh_nll[2], sh_kl[2];

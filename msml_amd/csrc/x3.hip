@@ -20,11 +20,15 @@ __device__ __forceinline__ Vec8 x3_load(const unsigned short* __restrict__ base,
   for (int j = 0; j < 8; j++) h.v[j] += l.v[j];
   return h;
 }
+// hi = bf16(v), lo = bf16(v - hi), hi again.  v = +-inf, and a finite |v| >= 2^128 - 2^119 (0x7F7F8000 up, FLT_MAX among
+// them: it rounds to the bf16 infinity), give an infinite hi: lo is 0 there (x3_lo, common.h), so the pair reads back as
+// the infinity the f32 path keeps.  A NaN stays a NaN in all three planes.  hi + lo carries 16 significant bits of a
+// normal v; an f32 subnormal v (and a lo below 2^-126) goes through the device's bf16 conversion like any other store.
 __device__ __forceinline__ void x3_store(unsigned short* __restrict__ base, long pix, int C, int c, const Vec8& v) {
   unsigned short* p = base + pix * (3L * C) + c;
   Vec8 h = round8<unsigned short>(v), l;
 #pragma unroll
-  for (int j = 0; j < 8; j++) l.v[j] = v.v[j] - h.v[j];
+  for (int j = 0; j < 8; j++) l.v[j] = x3_lo(v.v[j], h.v[j]);
   store8<unsigned short>(p, h);
   store8<unsigned short>(p + C, l);
   store8<unsigned short>(p + 2 * C, h);
@@ -153,6 +157,7 @@ extern "C" int msml_x3_bn_act_fwd(const void* x, const float* scale, const float
 extern "C" int msml_x3_fm_fuse_fwd(const void* x, const void* yf, void* z, long M, int C, int act, int arith,
                                    void* stream) {
   X3_SHAPE("x3_fm_fuse_fwd");
+  MSML_CHECK(x && yf && z, MSML_ERR_SHAPE, "x3_fm_fuse_fwd: null pointer");
   MSML_CHECK(act >= 0 && act <= 1 && arith >= 0 && arith <= 3, MSML_ERR_UNSUPPORTED, "x3_fm_fuse_fwd: act=%d arith=%d",
              act, arith);
   k_x3_fm_fwd<<<x3_grid(M * (C / 8)), 256, 0, (hipStream_t)stream>>>(
@@ -163,6 +168,7 @@ extern "C" int msml_x3_fm_fuse_fwd(const void* x, const void* yf, void* z, long 
 
 extern "C" int msml_x3_add(const void* a, const void* b, void* out, long M, int C, void* stream) {
   X3_SHAPE("x3_add");
+  MSML_CHECK(a && b && out, MSML_ERR_SHAPE, "x3_add: null pointer");
   k_x3_add<<<x3_grid(M * (C / 8)), 256, 0, (hipStream_t)stream>>>((const unsigned short*)a, (const unsigned short*)b,
                                                                   (unsigned short*)out, M, C);
   MSML_LAUNCH_OK("x3_add");
@@ -171,6 +177,7 @@ extern "C" int msml_x3_add(const void* a, const void* b, void* out, long M, int 
 
 extern "C" int msml_x3_from_f32(const float* src, void* dst, long M, int C, void* stream) {
   X3_SHAPE("x3_from_f32");
+  MSML_CHECK(src && dst, MSML_ERR_SHAPE, "x3_from_f32: null pointer");
   k_x3_from_f32<<<x3_grid(M * (C / 8)), 256, 0, (hipStream_t)stream>>>(src, (unsigned short*)dst, M, C);
   MSML_LAUNCH_OK("x3_from_f32");
   return MSML_OK;
@@ -178,6 +185,7 @@ extern "C" int msml_x3_from_f32(const float* src, void* dst, long M, int C, void
 
 extern "C" int msml_x3_to_f32(const void* src, float* dst, long M, int C, void* stream) {
   X3_SHAPE("x3_to_f32");
+  MSML_CHECK(src && dst, MSML_ERR_SHAPE, "x3_to_f32: null pointer");
   k_x3_to_f32<<<x3_grid(M * (C / 8)), 256, 0, (hipStream_t)stream>>>((const unsigned short*)src, dst, M, C);
   MSML_LAUNCH_OK("x3_to_f32");
   return MSML_OK;

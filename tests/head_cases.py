@@ -45,7 +45,7 @@ EPS_CLIP = 1e-6
 CMAX = 1.0 - 2.0 ** -10
 LIBM_FACTOR = 4.0
 # worst |f32 function - f64 function| / (u32 |f64 function|) of torch's CPU kernels over measure_libm()'s ranges
-LIBM_MEASURED = {"acos": 1.49, "cos": 1.09, "sin": 1.09, "sqrt": 1.05, "exp": 1.02}
+LIBM_MEASURED = {"acos": 1.49, "cos": 1.09, "sin": 1.09, "sqrt": 1.05, "exp": 1.02, "tanh": 1.07, "log": 1.02}
 ARC, COS = 0, 1
 S = 64.0
 M_OF = {ARC: 0.5, COS: 0.4}
@@ -65,7 +65,9 @@ def measure_libm():
     g = torch.linspace(0.0, 1.0, n, dtype=torch.float64)
     rng = {"acos": ((2.0 * g - 1.0) * CMAX, torch.acos), "cos": (g * (math.pi + 1.0), torch.cos),
            "sin": (g * (math.pi + 1.0), torch.sin), "sqrt": (g * 4.0 + 2.0 ** -20, torch.sqrt),
-           "exp": (-87.0 * g, torch.exp)}
+           "exp": (-87.0 * g, torch.exp),
+           # tests/ew_cases.py: the FM masks over [-12, 12], log(1 + exp(-|l0 - l1|)) of the segmentation loss over [1, 2]
+           "tanh": ((2.0 * g - 1.0) * 12.0, torch.tanh), "log": (1.0 + g, torch.log)}
     out = {}
     for fn, (x, f) in rng.items():
         x32 = x.float()

@@ -14,13 +14,11 @@ import torch
 
 from msml_amd import _lib
 from tests import head_cases as H
+from tests.abi_harness import DTC, GUARD, SENTINEL, GuardedDevice  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 REP = H.Report()
 T0 = time.time()
-GUARD = 64
-SENTINEL = -1232.0
-DTC = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
 UNSUP, SHAPE, WORKSPACE = -4, -1, -5
 
 
@@ -33,40 +31,8 @@ def _offset_copy(t):
     return v
 
 
-class Device:
+class Device(GuardedDevice):
     """The entry points with the interface of head_cases.Restatement."""
-    name = "device"
-
-    def __init__(self):
-        self.bufs, self.pending = [], []
-
-    def out(self, shape, dtype, init=None):
-        n = 1
-        for s in shape:
-            n *= s
-        buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=dtype, device="cuda")
-        v = buf[GUARD:GUARD + n].view(shape)
-        if init is None:
-            v.fill_(float("nan"))
-        elif torch.is_tensor(init):
-            v.copy_(init)
-        else:
-            v.fill_(init)
-        self.bufs.append((buf, n))
-        self.pending.append((buf.data_ptr(), buf.data_ptr() + buf.numel() * buf.element_size()))
-        return v
-
-    def call(self, name, *args):
-        def is_out(a):
-            return any(lo <= a.data_ptr() < hi for lo, hi in self.pending)
-        ins = [(a, a.clone()) for a in args if torch.is_tensor(a) and not is_out(a)]
-        _lib.call(name, *args)
-        for a, c in ins:
-            assert torch.equal(a.contiguous().view(torch.uint8), c.contiguous().view(torch.uint8)), "%s modified an input" % name
-        for buf, n in self.bufs:
-            assert bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[GUARD + n:] == SENTINEL).all()), \
-                "%s wrote outside an output buffer" % name
-        self.pending = []
 
     def rownorm_fwd(self, wt, Rp, ld, dtype, misalign=False):
         R, E = wt.shape
