@@ -976,6 +976,31 @@ int msml_jpeg_decode(const unsigned char* streams, long stream_bytes, const int*
                      const long* meta_out, int channels, int swap_rb, int* status, unsigned char* ws, long ws_bytes,
                      int N, void* stream);
 
+/* ---------------------------------------------------------------- progressive JPEG decoding ----------------------
+ * msml_jpeg_decode for a batch that may also hold progressive (SOF2, 8-bit, Huffman) streams, baseline and progressive
+ * in any mix: the pixels libjpeg writes for a file whose scans bring every coefficient down to bit 0 (its inter-block
+ * smoothing stays off for those; the host parser refuses every other progression).  Every argument msml_jpeg_decode
+ * has means the same; the workspace is the same (msml_jpeg_workspace), and so are the two passes behind the
+ * coefficients.  A progressive image is walked by one wavefront, scan after scan in file order.
+ *
+ *   desc word 22: the scans of image n (0: a baseline image, decoded as msml_jpeg_decode does), word 23: its first
+ *     record in the scan table.
+ *   scans / scans_host [nscan][16] int32: the same table on the device and on the HOST (csrc/jpeg_prog_core.h names the
+ *     words: byte range of the entropy-coded segment, components, one Huffman table per component -- DC for Ss = 0,
+ *     else AC --, Ss, Se, Ah, Al, the restart interval at that scan).  The library checks scans_host before it
+ *     launches: records inside the table, at most 4096 per image, byte ranges inside the stream and in ascending
+ *     order, component indices ascending and below the frame's, table indices below nh, 0 <= Ss <= Se <= 63, Se = 0
+ *     with Ss = 0, one component when Ss > 0, Ah and Al in 0..13.  Whether the scans form a complete progression is
+ *     the parser's question (msml_amd/jpeg.py): for ANY records that pass these checks the device reads only inside
+ *     the byte ranges and the tables and writes only the image's own workspace and rectangle.
+ *   status: as msml_jpeg_decode; 3 is also a refinement symbol whose size is not 1.
+ *   MSML_ERR_SHAPE also for a null or misaligned scan table, nscan < 1, and inconsistent records. */
+int msml_jpeg_decode_scans(const unsigned char* streams, long stream_bytes, const int* desc, const int* desc_host,
+                           const int* scans, const int* scans_host, long nscan, const int* qtabs, int nq,
+                           const int* htabs, int nh, unsigned char* dst, long dst_bytes, const long* meta_out,
+                           int channels, int swap_rb, int* status, unsigned char* ws, long ws_bytes, int N,
+                           void* stream);
+
 /* ---------------------------------------------------------------- baseline JPEG encoding -------------------------
  * PIL.Image.save on the device (eval/align_dataset.py:52-75, iterate_pku.py) and the JPEG inside mx.recordio.pack_img
  * (datasets/3d_tools/cvt_casia_webface.py:57, cvt_casia_webface_masked.py:108-114): N images of any sizes, samplings,

@@ -5,60 +5,18 @@
 //                   wave-uniform) out of LDS: the image's Huffman tables and a window of its stream.  Lane k keeps the
 //                   k-th coefficient of the current block, so a finished block leaves as one 128-byte vector store.
 //                   Writes status[n].
+//                   (csrc/jpeg_entropy_kernel.h; for a batch with progressive images msml_jpeg_decode_scans hands this
+//                   pass to csrc/jpeg_prog.hip, which also walks those images: k_jpeg_prog)
 //   k_jpeg_idct     one thread per 8 x 8 block: dequantise, IDCT, into the component planes of the workspace
 //   k_jpeg_store    one thread per 4 output pixels: upsample, convert, store into the packed destination
 // No atomics, one writer per byte: two runs give the same bits.  An image whose status is not 0 is skipped by the two
 // later passes: its output rectangle is left as it was.
 #include "common.h"
-#include "jpeg_core.h"
+#include "jpeg_entropy_kernel.h"
 
-// lane k keeps the k-th coefficient (zigzag order) of the current block and stores it at its natural index
-struct JpgWaveSink {
-  int16_t* coef;
-  int lane, nat;
-  int c;
-  __device__ void begin() { c = 0; }
-  __device__ void put(int k, int v) {
-    if (lane == k) c = v;
-  }
-  __device__ void end(long blk) { coef[blk * 64 + nat] = (int16_t)c; }
-};
-
-__global__ void __launch_bounds__(64) k_jpeg_entropy(const unsigned char* __restrict__ streams,
-                                                     const int* __restrict__ desc, const int* __restrict__ huff,
-                                                     unsigned char* __restrict__ ws, int* __restrict__ status) {
-  __shared__ int s_tab[6 * JPG_HUFF_WORDS];                  // the DC and AC table of each component
-  __shared__ unsigned int s_win[IMG_CHUNK / 4];
-  const int n = blockIdx.x;
-  const int* d = desc + (long)n * JPG_DESC_WORDS;
-  int st = d[JD_STATUS];
-  if (st == 0) {
-    const int nc = d[JD_NCOMP];
-    const int* dctab[3];
-    const int* actab[3];
-    for (int c = 0; c < 3; ++c) {
-      dctab[c] = s_tab + (2 * c) * JPG_HUFF_WORDS;
-      actab[c] = s_tab + (2 * c + 1) * JPG_HUFF_WORDS;
-      if (c < nc) {
-        const int* gd = huff + (long)d[JD_DC + c] * JPG_HUFF_WORDS;
-        const int* ga = huff + (long)d[JD_AC + c] * JPG_HUFF_WORDS;
-        for (int k = threadIdx.x; k < JPG_HUFF_WORDS; k += 64) {
-          s_tab[(2 * c) * JPG_HUFF_WORDS + k] = gd[k];
-          s_tab[(2 * c + 1) * JPG_HUFF_WORDS + k] = ga[k];
-        }
-      }
-    }
-    __syncthreads();
-    JpgWaveSink sink;
-    sink.coef = reinterpret_cast<int16_t*>(ws + (long)d[JD_WS] * JPG_WS_ALIGN);
-    sink.lane = threadIdx.x;
-    sink.nat = img_zigzag(threadIdx.x);
-    sink.c = 0;
-    LdsStreamSrc src = {streams + (long)d[JD_BASE] * 4, s_win, -IMG_CHUNK, d[JD_END], (int)threadIdx.x};
-    st = jpg_entropy(d, src, dctab, actab, sink);
-  }
-  if (threadIdx.x == 0) status[n] = st;
-}
+// jpeg_prog.hip: the entropy pass of a batch that holds progressive images
+int jpeg_prog_entropy(const unsigned char* streams, const int* desc, const int* scans, const int* htabs,
+                      unsigned char* ws, int* status, int N, int progressive, hipStream_t stream);
 
 __global__ void __launch_bounds__(256) k_jpeg_idct(const int* __restrict__ desc, const int* __restrict__ qtabs,
                                                    unsigned char* __restrict__ ws, const int* __restrict__ status) {
@@ -146,10 +104,12 @@ extern "C" long msml_jpeg_workspace(int* desc, int N) {
   return units * JPG_WS_ALIGN;
 }
 
-extern "C" int msml_jpeg_decode(const unsigned char* streams, long stream_bytes, const int* desc, const int* desc_host,
-                                const int* qtabs, int nq, const int* htabs, int nh, unsigned char* dst, long dst_bytes,
-                                const long* meta_out, int channels, int swap_rb, int* status, unsigned char* ws,
-                                long ws_bytes, int N, void* stream) {
+// msml_jpeg_decode (scans == nullptr: every image is baseline) and msml_jpeg_decode_scans
+static int jpeg_decode_any(const unsigned char* streams, long stream_bytes, const int* desc, const int* desc_host,
+                           const int* scans, const int* scans_host, long nscan, const int* qtabs, int nq,
+                           const int* htabs, int nh, unsigned char* dst, long dst_bytes, const long* meta_out,
+                           int channels, int swap_rb, int* status, unsigned char* ws, long ws_bytes, int N,
+                           void* stream) {
   MSML_CHECK(N >= 1 && N <= 65535, MSML_ERR_UNSUPPORTED, "jpeg_decode: N=%d outside 1..65535", N);
   MSML_CHECK(channels == 1 || channels == 3, MSML_ERR_UNSUPPORTED, "jpeg_decode: channels=%d (1 or 3)", channels);
   MSML_CHECK(streams && desc && desc_host && qtabs && htabs && dst && meta_out && status && ws, MSML_ERR_SHAPE,
@@ -164,10 +124,16 @@ extern "C" int msml_jpeg_decode(const unsigned char* streams, long stream_bytes,
              "jpeg_decode: stream_bytes=%ld dst_bytes=%ld ws_bytes=%ld nq=%d nh=%d", stream_bytes, dst_bytes, ws_bytes,
              nq, nh);
   long units = 0, max_blk = 0, max_grp = 0;
+  int progressive = 0;
   for (int n = 0; n < N; ++n) {
     const int* d = desc_host + (long)n * JPG_DESC_WORDS;
     MSML_CHECK(jpg_desc_ok(d, stream_bytes, nq, nh) == 1, MSML_ERR_SHAPE, "jpeg_decode: descriptor %d is inconsistent", n);
     if (d[JD_STATUS] != 0) continue;
+    if (scans) {
+      MSML_CHECK(jpg_scans_ok(d, scans_host, nscan, nh), MSML_ERR_SHAPE,
+                 "jpeg_decode_scans: the scan records of image %d are inconsistent", n);
+      progressive += d[JD_NSCAN] > 0;
+    }
     MSML_CHECK(channels == 3 || d[JD_NCOMP] == 1, MSML_ERR_UNSUPPORTED,
                "jpeg_decode: image %d has 3 components, channels=1 takes gray streams", n);
     JpgLayout L;
@@ -181,8 +147,13 @@ extern "C" int msml_jpeg_decode(const unsigned char* streams, long stream_bytes,
     max_blk = L.nblk > max_blk ? L.nblk : max_blk;
     max_grp = grp > max_grp ? grp : max_grp;
   }
-  k_jpeg_entropy<<<N, 64, 0, (hipStream_t)stream>>>(streams, desc, htabs, ws, status);
-  MSML_LAUNCH_OK("jpeg_entropy");
+  if (scans) {
+    const int rc = jpeg_prog_entropy(streams, desc, scans, htabs, ws, status, N, max_blk ? progressive : 0, (hipStream_t)stream);
+    if (rc != MSML_OK) return rc;
+  } else {
+    k_jpeg_entropy<false><<<N, 64, 0, (hipStream_t)stream>>>(streams, desc, htabs, ws, status);
+    MSML_LAUNCH_OK("jpeg_entropy");
+  }
   if (max_blk == 0) return MSML_OK;                          // only refused streams: their statuses are written
   k_jpeg_idct<<<dim3(cdiv(max_blk, 256), N), 256, 0, (hipStream_t)stream>>>(desc, qtabs, ws, status);
   MSML_LAUNCH_OK("jpeg_idct");
@@ -190,4 +161,23 @@ extern "C" int msml_jpeg_decode(const unsigned char* streams, long stream_bytes,
                                                                              channels, swap_rb, status);
   MSML_LAUNCH_OK("jpeg_store");
   return MSML_OK;
+}
+
+extern "C" int msml_jpeg_decode(const unsigned char* streams, long stream_bytes, const int* desc, const int* desc_host,
+                                const int* qtabs, int nq, const int* htabs, int nh, unsigned char* dst, long dst_bytes,
+                                const long* meta_out, int channels, int swap_rb, int* status, unsigned char* ws,
+                                long ws_bytes, int N, void* stream) {
+  return jpeg_decode_any(streams, stream_bytes, desc, desc_host, nullptr, nullptr, 0, qtabs, nq, htabs, nh, dst,
+                         dst_bytes, meta_out, channels, swap_rb, status, ws, ws_bytes, N, stream);
+}
+
+extern "C" int msml_jpeg_decode_scans(const unsigned char* streams, long stream_bytes, const int* desc,
+                                      const int* desc_host, const int* scans, const int* scans_host, long nscan,
+                                      const int* qtabs, int nq, const int* htabs, int nh, unsigned char* dst,
+                                      long dst_bytes, const long* meta_out, int channels, int swap_rb, int* status,
+                                      unsigned char* ws, long ws_bytes, int N, void* stream) {
+  MSML_CHECK(scans && scans_host && nscan >= 1 && ((uintptr_t)scans & 3) == 0, MSML_ERR_SHAPE,
+             "jpeg_decode_scans: needs a scan table of at least one record, 4-byte aligned (nscan=%ld)", nscan);
+  return jpeg_decode_any(streams, stream_bytes, desc, desc_host, scans, scans_host, nscan, qtabs, nq, htabs, nh, dst,
+                         dst_bytes, meta_out, channels, swap_rb, status, ws, ws_bytes, N, stream);
 }

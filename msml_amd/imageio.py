@@ -37,12 +37,13 @@ def reason(kind, status):
 
 
 @torch.no_grad()
-def decode_images(blobs, order="rgb", strict=True, device="cuda"):
+def decode_images(blobs, order="rgb", strict=True, device="cuda", progressive=False):
     """A list of JPEG / PNG byte strings -> (buf, meta): the packed 3-channel form ijb.align_faces, mtcnn_align and
     detect.Detector take (buf uint8 on the device, meta int64 numpy [N][4] = byte offset, H, W, pitch), in the caller's
     order.  order "rgb" or "bgr".  strict=True: ValueError naming the first image that cannot be decoded and why (reads
     the statuses back: a synchronisation); strict=False: (buf, meta, status) with status int32 [N] on the device -- the
-    decoder's own status word (jpeg.STATUS / png.STATUS), or UNKNOWN_FORMAT; failing images hold unspecified pixels."""
+    decoder's own status word (jpeg.STATUS / png.STATUS), or UNKNOWN_FORMAT; failing images hold unspecified pixels.
+    progressive=True: progressive JPEG streams decode too (jpeg.pack_jpegs); by default they are status 17."""
     if order not in ("rgb", "bgr"):
         raise ValueError("decode_images: order must be 'rgb' or 'bgr'")
     if not isinstance(blobs, (list, tuple)) or len(blobs) == 0:
@@ -55,7 +56,7 @@ def decode_images(blobs, order="rgb", strict=True, device="cuda"):
     batches = {}
     for k, mod, pack in (("jpeg", jpeg, jpeg.pack_jpegs), ("png", png, png.pack_pngs)):
         if rows[k]:
-            batches[k] = pack([blobs[i] for i in rows[k]])
+            batches[k] = pack([blobs[i] for i in rows[k]], **({"progressive": True} if progressive and k == "jpeg" else {}))
             host[rows[k]] = batches[k].status
             hw[rows[k]] = _codec.extents(batches[k])
     if strict:

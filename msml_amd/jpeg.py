@@ -1,11 +1,13 @@
-"""Baseline JPEG decoding on the device, bit-exact with libjpeg (csrc/jpeg.hip), and the MXNet RecordIO reader in
-front of it: what mx.image.imdecode / cv2.imread do for every input path of the reference (datasets/load_dataset.py,
-eval/verification.py:202-236).
+"""Baseline JPEG decoding on the device, bit-exact with libjpeg (csrc/jpeg.hip), progressive JPEG behind the keyword
+progressive=True (csrc/jpeg_prog.hip), and the MXNet RecordIO reader in front of them: what mx.image.imdecode /
+cv2.imread do for every input path of the reference (datasets/load_dataset.py, eval/verification.py:202-236).
 
-The host parses headers only (parse_jpeg never walks the entropy-coded bytes); the compressed bytes go to the device
-and msml_jpeg_decode writes the uint8 pixels libjpeg writes with its defaults (JDCT_ISLOW, fancy upsampling), either as
-one [N, H, W, 3] tensor (the DeviceLoaderX / data.augment input) or in the packed (buf, meta) form ijb.align_faces,
-mtcnn_align and detect.Detector take.  tests/jpeg_cases.py restates the arithmetic in numpy.
+The host parses headers only (parse_jpeg never walks the entropy-coded bytes; for a progressive file it looks for the
+marker that ends each scan); the compressed bytes go to the device and msml_jpeg_decode / msml_jpeg_decode_scans write
+the uint8 pixels libjpeg writes with its defaults (JDCT_ISLOW, fancy upsampling), either as one [N, H, W, 3] tensor
+(the DeviceLoaderX / data.augment input) or in the packed (buf, meta) form ijb.align_faces, mtcnn_align and
+detect.Detector take.  tests/jpeg_cases.py restates the arithmetic in numpy, tests/jpeg_prog_cases.py the progressive
+scans.
 """
 import os
 import struct
@@ -21,7 +23,9 @@ from ._lib import call, value
 DESC_WORDS = 32
 HUFF_WORDS = 832
 (JD_BASE, JD_BEGIN, JD_END, JD_H, JD_W, JD_NCOMP, JD_HMAX, JD_VMAX, JD_QT, JD_DC, JD_AC, JD_RI, JD_STATUS, JD_MCUX,
- JD_MCUY, JD_WS) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 11, 14, 17, 18, 19, 20, 21
+ JD_MCUY, JD_WS, JD_NSCAN, JD_SCAN0) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 11, 14, 17, 18, 19, 20, 21, 22, 23
+SCAN_WORDS = 16      # one record of the scan table (csrc/jpeg_prog_core.h)
+(JS_BEGIN, JS_END, JS_NCOMP, JS_COMP, JS_TAB, JS_SS, JS_SE, JS_AH, JS_AL, JS_RI) = 0, 1, 2, 3, 6, 9, 10, 11, 12, 13
 
 # status[n] of a decode: 1-6 from the device (csrc/jpeg_core.h), 16.. from the parser
 STATUS = {
@@ -34,9 +38,11 @@ STATUS = {
     22: "only one scan over all components is supported", 23: "a table the scan selects is missing or invalid",
     24: "image size outside 1..32767", 25: "unsupported frame type (extended, lossless or hierarchical)",
     26: "the components are RGB, not YCbCr (Adobe transform 0, or ids 'R' 'G' 'B' without JFIF): unsupported",
+    27: "a progressive scan libjpeg rejects or warns about (parameters, order of the scans, or its components)",
+    28: "an incomplete progression: not every coefficient reaches bit 0 before the file ends",
 }
-(BAD_HEADER, PROGRESSIVE, ARITHMETIC, PRECISION, COMPONENTS, SAMPLING, SCAN, TABLES, SIZE, FRAME, COLORSPACE) = \
-    range(16, 27)
+(BAD_HEADER, PROGRESSIVE, ARITHMETIC, PRECISION, COMPONENTS, SAMPLING, SCAN, TABLES, SIZE, FRAME, COLORSPACE,
+ PROGRESSION, INCOMPLETE) = range(16, 29)
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,
                    7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31,
@@ -57,10 +63,25 @@ class JpegDescriptor:
         self.restart_interval = 0
         self.qtables = {}                   # id -> int32 [64], natural order
         self.huffman = {}                   # (class, id) -> (counts [16], symbols)
+        self.progressive = False            # an SOF2 frame, read with parse_jpeg(progressive=True)
+        self.scans = []                     # its JpegScans in file order; empty for a baseline stream
+        self.coef_bits = None               # [component][64]: the Al each coefficient was last left at, -1 = never sent
 
     @property
     def reason(self):
         return STATUS[self.status]
+
+
+class JpegScan:
+    """One scan of a progressive stream: components (frame indices), dcsel / acsel (the SOS's selectors), ss, se, ah,
+    al, restart_interval (as DRI stood at this SOS), begin / end (byte range of the entropy-coded segment) and tables:
+    per component the (counts, symbols) the scan decodes with as DHT stood at this SOS -- the DC table of a first DC
+    scan, the AC table of an AC scan, None for a DC refinement, which reads plain bits."""
+
+    def __init__(self, components, dcsel, acsel, ss, se, ah, al, restart_interval, begin, end, tables):
+        self.components, self.dcsel, self.acsel = components, dcsel, acsel
+        self.ss, self.se, self.ah, self.al = ss, se, ah, al
+        self.restart_interval, self.begin, self.end, self.tables = restart_interval, begin, end, tables
 
 
 def _refuse(d, status):
@@ -68,12 +89,86 @@ def _refuse(d, status):
     return d
 
 
-def parse_jpeg(data):
+def _bad(d, n):
+    """A header that cannot be read: BAD_HEADER in front of the first scan; behind one the file counts as ending there."""
+    return _finish(d, n) if d.scans else _refuse(d, BAD_HEADER)
+
+
+def _finish(d, n):
+    """EOI, or the end of what can be read, of a progressive stream: supported when every coefficient reached bit 0
+    (jdcoefct.c smoothing_ok then keeps libjpeg's inter-block smoothing off)."""
+    d.begin, d.end = d.scans[0].begin, n
+    if any(b != 0 for comp in d.coef_bits for b in comp):
+        return _refuse(d, INCOMPLETE)
+    return d
+
+
+def _segment_end(data, pos):
+    """The first marker at or behind pos that is neither FF 00 nor RSTn: where an entropy-coded segment ends."""
+    n = len(data)
+    while True:
+        pos = data.find(b"\xff", pos)
+        if pos < 0 or pos + 1 >= n:
+            return n
+        m = data[pos + 1]
+        if m == 0 or 0xD0 <= m <= 0xD7:
+            pos += 2
+        elif m == 0xFF:
+            pos += 1                        # a fill byte: the marker code follows
+        else:
+            return pos
+
+
+def _progressive_scan(d, data, seg, ids, begin):
+    """SOS of a progressive stream, by jdmarker.c get_sos and jdphuff.c start_pass_phuff_decoder: the scan is taken
+    only with parameters libjpeg accepts without a warning.  -> status (0: appended to d.scans)."""
+    ns = seg[0]
+    if len(seg) != 4 + 2 * ns:
+        return BAD_HEADER
+    if not 1 <= ns <= d.components:
+        return PROGRESSION
+    comps = [ids.index(seg[1 + 2 * c]) if seg[1 + 2 * c] in ids else -1 for c in range(ns)]
+    if any(c < 0 for c in comps) or any(b <= a for a, b in zip(comps, comps[1:])):
+        return PROGRESSION                  # not of the frame, repeated, or out of frame order
+    ss, se, ah, al = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
+    if ss > se or se > 63 or (ss == 0 and se != 0) or (ss != 0 and ns != 1) or al > 13 or (ah != 0 and al != ah - 1):
+        return PROGRESSION
+    for c in comps:
+        bits = d.coef_bits[c]
+        if ss != 0 and bits[0] < 0:
+            return PROGRESSION              # AC before the component's DC
+        if bits[ss:se + 1].count(ah if ah else -1) != se + 1 - ss:
+            return PROGRESSION              # a refinement without its first scan, a repeated or a skipped pass
+    dcsel = tuple(seg[2 + 2 * c] >> 4 for c in range(ns))
+    acsel = tuple(seg[2 + 2 * c] & 15 for c in range(ns))
+    tables = []
+    for i in range(ns):
+        if ss == 0 and ah != 0:
+            tables.append(None)
+            continue
+        key = (0, dcsel[i]) if ss == 0 else (1, acsel[i])
+        if key not in d.huffman or huffman_lookup(*d.huffman[key]) is None:
+            return TABLES
+        tables.append(d.huffman[key])
+    for c in comps:
+        d.coef_bits[c][ss:se + 1] = [al] * (se + 1 - ss)
+    d.scans.append(JpegScan(tuple(comps), dcsel, acsel, ss, se, ah, al, d.restart_interval, begin,
+                            _segment_end(data, begin), tables))
+    return 0
+
+
+def parse_jpeg(data, progressive=False):
     """Walk the marker segments in front of the scan (SOI, APPn / COM, DQT, SOF0, DHT, DRI, SOS) -> JpegDescriptor.
     Never reads the entropy-coded bytes and never guesses: anything but 8-bit baseline Huffman with one interleaved
     scan in gray / 4:4:4 / 4:2:2 / 4:2:0 comes back with a nonzero status.  Three components are YCbCr as libjpeg
     decides it (jdapimin.c default_decompress_parms): a JFIF marker says so; without one, an Adobe APP14 segment with
-    transform 0, or the component ids 'R' 'G' 'B', mean RGB stored as it is, which is refused."""
+    transform 0, or the component ids 'R' 'G' 'B', mean RGB stored as it is, which is refused.
+
+    progressive=True: an SOF2 frame is read like SOF0 and every scan is walked to EOI: `scans` holds each SOS with the
+    tables and the restart interval as they stood there, and the byte range of its entropy-coded segment (found by
+    looking for the next marker, never by decoding).  Supported when every scan is one libjpeg takes without a warning
+    (else PROGRESSION) and every coefficient of every component has reached bit 0 by the end (else INCOMPLETE: libjpeg
+    would smooth such a file, differently from version to version)."""
     data = bytes(data)
     d = JpegDescriptor()
     n = len(data)
@@ -83,21 +178,23 @@ def parse_jpeg(data):
     frame = None
     jfif, adobe = False, None              # adobe: the transform byte of an APP14 "Adobe" segment
     while True:
+        if d.scans and pos + 2 <= n and data[pos] == 0xFF and data[pos + 1] == 0xD9:
+            return _finish(d, n)
         if pos + 2 > n or data[pos] != 0xFF:
-            return _refuse(d, BAD_HEADER)
+            return _bad(d, n)
         while pos < n and data[pos] == 0xFF:
             pos += 1
         if pos >= n:
-            return _refuse(d, BAD_HEADER)
+            return _bad(d, n)
         m = data[pos]
         pos += 1
         if m == 0x01 or 0xD0 <= m <= 0xD7:
             continue
         if m in (0xD8, 0xD9, 0x00) or pos + 2 > n:
-            return _refuse(d, BAD_HEADER)
+            return _bad(d, n)
         ln = (data[pos] << 8) | data[pos + 1]
         if ln < 2 or pos + ln > n:
-            return _refuse(d, BAD_HEADER)
+            return _bad(d, n)
         seg = data[pos + 2:pos + ln]
         if m == 0xDB:
             i = 0
@@ -105,7 +202,7 @@ def parse_jpeg(data):
                 pq, tq = seg[i] >> 4, seg[i] & 15
                 size = 64 * (2 if pq else 1)
                 if pq > 1 or tq > 3 or i + 1 + size > len(seg):
-                    return _refuse(d, BAD_HEADER)
+                    return _bad(d, n)
                 raw = np.frombuffer(seg, dtype=">u2" if pq else np.uint8, count=64, offset=i + 1).astype(np.int32)
                 q = np.zeros(64, np.int32)
                 q[ZIGZAG] = raw
@@ -115,12 +212,12 @@ def parse_jpeg(data):
             i = 0
             while i < len(seg):
                 if i + 17 > len(seg):
-                    return _refuse(d, BAD_HEADER)
+                    return _bad(d, n)
                 tc, th = seg[i] >> 4, seg[i] & 15
                 counts = list(seg[i + 1:i + 17])
                 total = sum(counts)
                 if tc > 1 or th > 3 or total > 256 or i + 17 + total > len(seg):
-                    return _refuse(d, BAD_HEADER)
+                    return _bad(d, n)
                 d.huffman[(tc, th)] = (counts, bytes(seg[i + 17:i + 17 + total]))
                 i += 17 + total
         elif m == 0xE0 and seg[:5] == b"JFIF\x00":
@@ -129,12 +226,13 @@ def parse_jpeg(data):
             adobe = seg[11]
         elif m == 0xDD:
             if len(seg) != 2:
-                return _refuse(d, BAD_HEADER)
+                return _bad(d, n)
             d.restart_interval = (seg[0] << 8) | seg[1]
-        elif m == 0xC0:
+        elif m == 0xC0 or (m == 0xC2 and progressive):
             if frame is not None or len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
-                return _refuse(d, BAD_HEADER)
+                return _bad(d, n)
             frame = seg
+            d.progressive = m == 0xC2
             d.height, d.width, d.components = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
             d.sampling = tuple((seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15) for c in range(seg[5]))
             d.qsel = tuple(seg[8 + 3 * c] for c in range(seg[5]))
@@ -146,7 +244,7 @@ def parse_jpeg(data):
             return _refuse(d, FRAME)
         elif m == 0xDA:
             if frame is None or len(seg) < 1:
-                return _refuse(d, BAD_HEADER)
+                return _bad(d, n)
             if frame[0] != 8:
                 return _refuse(d, PRECISION)
             if d.components not in (1, 3):
@@ -156,11 +254,21 @@ def parse_jpeg(data):
             if d.sampling not in (((1, 1),), ((1, 1),) * 3, ((2, 1), (1, 1), (1, 1)), ((2, 2), (1, 1), (1, 1))):
                 return _refuse(d, SAMPLING)
             ns = seg[0]
-            if len(seg) != 4 + 2 * ns:
-                return _refuse(d, BAD_HEADER)
             ids = [frame[6 + 3 * c] for c in range(d.components)]
             if d.components == 3 and not jfif and (adobe == 0 or (adobe is None and ids == [0x52, 0x47, 0x42])):
                 return _refuse(d, COLORSPACE)
+            if d.progressive:
+                if d.coef_bits is None:
+                    if any(q not in d.qtables for q in d.qsel):
+                        return _refuse(d, TABLES)
+                    d.coef_bits = [[-1] * 64 for _ in range(d.components)]
+                st = _progressive_scan(d, data, seg, ids, pos + ln)
+                if st:
+                    return _bad(d, n) if st == BAD_HEADER else _refuse(d, st)
+                pos = d.scans[-1].end
+                continue
+            if len(seg) != 4 + 2 * ns:
+                return _bad(d, n)
             if ns != d.components or [seg[1 + 2 * c] for c in range(ns)] != ids:
                 return _refuse(d, SCAN)
             if (seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns]) != (0, 63, 0):
@@ -184,14 +292,15 @@ class HeaderCache:
     for byte (same size, same tables), so all but the first cost one slice and one dictionary lookup per distinct
     header length.  Holds at most `capacity` headers; past that it parses without remembering (`full` counts those).
     The descriptors it hands out share their table dictionaries: they are read, never written.  Owned by whoever
-    packs many batches (RecordFaceSource has one); pack_jpegs without one parses every header."""
+    packs many batches (RecordFaceSource has one); pack_jpegs without one parses every header.  A progressive stream
+    (progressive=True) passes through uncached: its headers run through the whole file."""
 
     def __init__(self, capacity=256):
         self.capacity, self.full = capacity, 0
         self.headers = {}
         self.lengths = []
 
-    def parse(self, data):
+    def parse(self, data, progressive=False):
         import copy
         data = bytes(data)
         for ln in self.lengths:
@@ -200,8 +309,8 @@ class HeaderCache:
                 d = copy.copy(d)
                 d.end = len(data)
                 return d
-        d = parse_jpeg(data)
-        if d.status == 0:
+        d = parse_jpeg(data, progressive)
+        if d.status == 0 and not d.progressive:
             if len(self.headers) < self.capacity:
                 self.headers[data[:d.begin]] = d
                 if d.begin not in self.lengths:
@@ -248,25 +357,31 @@ class JpegBatch(StreamBatch):
     """pack_jpegs' result: everything msml_jpeg_decode reads, on the host (pinned when a GPU is present).
     streams uint8 [bytes]: the byte strings back to back at 4-byte-aligned offsets; desc int32 [N, 32]; qtabs int32
     [nq, 64] (natural order) and htabs int32 [nh, 832] (lookup form), each distinct table once; descriptors: the
-    JpegDescriptor of every stream; ws_bytes: the workspace the decode needs."""
+    JpegDescriptor of every stream; ws_bytes: the workspace the decode needs.  scans int32 [ns, 16]: the scan table
+    of the progressive streams (pack_jpegs(progressive=True) found some), else None."""
 
     FIELDS = ("streams", "desc", "qtabs", "htabs")
     STATUS_WORD = JD_STATUS
 
-    def __init__(self, streams, desc, qtabs, htabs, descriptors, ws_bytes):
+    def __init__(self, streams, desc, qtabs, htabs, descriptors, ws_bytes, scans=None):
         self.streams, self.desc, self.qtabs, self.htabs = streams, desc, qtabs, htabs
-        self.descriptors, self.ws_bytes = descriptors, ws_bytes
+        self.descriptors, self.ws_bytes, self.scans = descriptors, ws_bytes, scans
+        if scans is not None:
+            self.FIELDS = JpegBatch.FIELDS + ("scans",)
         self._dev = None
 
 
-def pack_jpegs(streams, cache=None):
+def pack_jpegs(streams, cache=None, progressive=False):
     """A list of JPEG byte strings -> JpegBatch.  Streams the parser refuses keep their place with their status.
-    cache: a HeaderCache, for callers that pack batch after batch of one dataset."""
+    cache: a HeaderCache, for callers that pack batch after batch of one dataset.  progressive=True: progressive
+    streams are taken too (parse_jpeg), baseline and progressive in any mix; their scans go into one table beside
+    `desc`, one record per scan, with table selectors as indices into the deduplicated htabs."""
     if not isinstance(streams, (list, tuple)) or len(streams) == 0:
         raise ValueError("pack_jpegs: needs a non-empty list of byte strings")
     n = len(streams)
     parse = cache.parse if cache is not None else parse_jpeg
-    descs = [parse(s) for s in streams]
+    descs = [parse(s, progressive) for s in streams] if progressive else [parse(s) for s in streams]
+    records = []
     qidx, hidx, qtabs, htabs = {}, {}, [], []
 
     def q_index(q):
@@ -296,8 +411,18 @@ def pack_jpegs(streams, cache=None):
         dn[i, JD_H], dn[i, JD_W], dn[i, JD_NCOMP], dn[i, JD_HMAX], dn[i, JD_VMAX] = d.height, d.width, d.components, hm, vm
         for c in range(d.components):
             dn[i, JD_QT + c] = q_index(d.qtables[d.qsel[c]])
-            dn[i, JD_DC + c] = h_index(d.huffman[(0, d.dcsel[c])])
-            dn[i, JD_AC + c] = h_index(d.huffman[(1, d.acsel[c])])
+            if not d.scans:
+                dn[i, JD_DC + c] = h_index(d.huffman[(0, d.dcsel[c])])
+                dn[i, JD_AC + c] = h_index(d.huffman[(1, d.acsel[c])])
+        if d.scans:
+            dn[i, JD_NSCAN], dn[i, JD_SCAN0] = len(d.scans), len(records)
+            for sc in d.scans:
+                r = [0] * SCAN_WORDS
+                r[JS_BEGIN], r[JS_END], r[JS_NCOMP] = sc.begin, sc.end, len(sc.components)
+                for c, (comp, t) in enumerate(zip(sc.components, sc.tables)):
+                    r[JS_COMP + c], r[JS_TAB + c] = comp, (h_index(t) if t is not None else 0)
+                r[JS_SS], r[JS_SE], r[JS_AH], r[JS_AL], r[JS_RI] = sc.ss, sc.se, sc.ah, sc.al, sc.restart_interval
+                records.append(r)
         dn[i, JD_RI] = d.restart_interval
         dn[i, JD_MCUX], dn[i, JD_MCUY] = -(-d.width // (8 * hm)), -(-d.height // (8 * vm))
     flat = buf.numpy()
@@ -313,12 +438,17 @@ def pack_jpegs(streams, cache=None):
         ws_bytes = value("msml_jpeg_workspace", desc.data_ptr(), n)
         if ws_bytes <= 0:
             raise RuntimeError("msml_jpeg_workspace refused the descriptors")
-    return JpegBatch(buf, desc, qt, ht, descs, ws_bytes)
+    scans = None
+    if records:
+        scans = pinned((len(records), SCAN_WORDS), torch.int32)
+        scans.numpy()[...] = np.array(records, np.int32)
+    return JpegBatch(buf, desc, qt, ht, descs, ws_bytes, scans)
 
 
 @torch.no_grad()
-def decode_into(batch, dst, meta, channels=3, order="rgb", ws=None, status=None):
-    """msml_jpeg_decode of a JpegBatch into the caller's buffers, on the current stream: dst a uint8 tensor on the
+def decode_into(batch, dst, meta, channels=3, order="rgb", ws=None, status=None, progressive=False):
+    """msml_jpeg_decode (msml_jpeg_decode_scans when the batch carries a scan table, which only a batch packed with
+    progressive=True does; the keyword itself changes nothing for a packed batch) of a JpegBatch into the caller's buffers, on the current stream: dst a uint8 tensor on the
     device, meta int64 [N][4] = byte offset in dst, H, W, pitch -- numpy (uploaded here: a copy from pageable memory,
     for which the host waits) or a tensor already on the device (the device checks every row against its stream and
     against dst.numel(): a row that does not fit gives status 6 and writes nothing).  ws: uint8 on the device, at
@@ -326,18 +456,23 @@ def decode_into(batch, dst, meta, channels=3, order="rgb", ws=None, status=None)
     n = len(batch)
     device = dst.device
     meta_dev = packed.meta_on_device(meta, n, device, "decode_into")
-    streams, desc, qtabs, htabs = batch.to_device(device)
+    streams, desc, qtabs, htabs = batch.to_device(device)[:4]
     if ws is None:
         ws = torch.empty(max(batch.ws_bytes, 16), dtype=torch.uint8, device=device)
     if status is None:
         status = torch.empty(n, dtype=torch.int32, device=device)
+    if batch.scans is not None:
+        call("msml_jpeg_decode_scans", streams, streams.numel(), desc, batch.desc.data_ptr(), batch.to_device(device)[4],
+             batch.scans.data_ptr(), batch.scans.shape[0], qtabs, qtabs.shape[0], htabs, htabs.shape[0], dst, dst.numel(),
+             meta_dev, channels, 1 if order == "bgr" else 0, status, ws, ws.numel(), n)
+        return status
     call("msml_jpeg_decode", streams, streams.numel(), desc, batch.desc.data_ptr(), qtabs, qtabs.shape[0], htabs,
          htabs.shape[0], dst, dst.numel(), meta_dev, channels, 1 if order == "bgr" else 0, status, ws, ws.numel(), n)
     return status
 
 
 @torch.no_grad()
-def decode_batch(batch, size=None, order="rgb", strict=True, channels=3, device="cuda"):
+def decode_batch(batch, size=None, order="rgb", strict=True, channels=3, device="cuda", progressive=False):
     """Decode a JpegBatch (or a list of byte strings) on the device, on the current stream.
 
     size=(H, W): uint8 [N, H, W, 3] ([N, H, W] for channels=1); an image of another size is a ValueError.
@@ -345,7 +480,10 @@ def decode_batch(batch, size=None, order="rgb", strict=True, channels=3, device=
     order: "rgb" (imdecode) or "bgr" (cv2.imread); a gray stream replicates Y.  channels=1 takes gray streams only.
     strict=True: ValueError naming the first failing image and why (this reads the statuses back: a synchronisation);
     strict=False: the int32 status tensor [N] comes back as the last element instead, failing images hold unspecified
-    pixels.  A batch with no supported stream launches nothing."""
+    pixels.  A batch with no supported stream launches nothing.  progressive=True: a list of byte strings is packed
+    with pack_jpegs(progressive=True), so progressive streams decode too, in any mix with baseline ones."""
+    if progressive and not isinstance(batch, JpegBatch):
+        batch = pack_jpegs(batch, progressive=True)
     return _codec.decode_batch(_CODEC, batch, size, order, strict, channels, device)
 
 
@@ -431,7 +569,8 @@ class RecordFaceSource:
     flags DeviceLoaderX(seed=seed, p_mask=p_mask) draws for batch k of the pass.  close() (or `with`) closes the
     record files."""
 
-    def __init__(self, root, batch, steps=None, shuffle=False, seed=1, masks=False, p_mask=0.2):
+    def __init__(self, root, batch, steps=None, shuffle=False, seed=1, masks=False, p_mask=0.2, progressive=False):
+        self.progressive = progressive       # records may be progressive JPEG (pack_jpegs)
         self.rec = RecordFile(os.path.join(root, "train.rec"), os.path.join(root, "train.idx"))
         self.batch, self.steps, self.shuffle, self.seed = batch, steps, shuffle, seed
         self.masks, self.p_mask = masks, p_mask
@@ -471,14 +610,14 @@ class RecordFaceSource:
                 (_, label, _, _), body = self.rec.read_idx(int(i))
                 streams.append(body)
                 labels.append(int(label if np.isscalar(label) else label[0]))
-            item = (pack_jpegs(streams, self.headers), torch.tensor(labels, dtype=torch.int64))
+            item = (pack_jpegs(streams, self.headers, self.progressive), torch.tensor(labels, dtype=torch.int64))
             if self.masks:
                 flags = data.mask_flags(self.seed, k * self.batch, self.batch, self.p_mask)
                 rows = np.full(self.batch, -1, np.int32)
                 rows[flags] = np.arange(int(flags.sum()), dtype=np.int32)
                 sel = [int(i) for i in idx[flags]]
-                mo = pack_jpegs([self.mask_out.read_idx(i)[1] for i in sel], self.headers) if sel else None
-                mk = pack_jpegs([self.mask.read_idx(i)[1] for i in sel], self.headers) if sel else None
+                mo = pack_jpegs([self.mask_out.read_idx(i)[1] for i in sel], self.headers, self.progressive) if sel else None
+                mk = pack_jpegs([self.mask.read_idx(i)[1] for i in sel], self.headers, self.progressive) if sel else None
                 item = (item[0], mo, mk, torch.from_numpy(rows), item[1])
             if torch.cuda.is_available():
                 item = tuple(t.pin_memory() if isinstance(t, torch.Tensor) else t for t in item)

@@ -260,11 +260,11 @@ def list_folder(root):
     return out
 
 
-def load_folder(root, device="cuda"):
+def load_folder(root, device="cuda", progressive=False):
     """The file I/O read_pairs_txt leaves out (qeval_folder.py:42-49, Image.open(...).convert('RGB') of every file of
     every identity): -> (files_by_identity, buf, meta), the images decoded on the device (imageio.decode_images: JPEG
     and PNG files, mixed freely) in pairs_file_order -- row k of meta is the image read_pairs_txt's index k names.
-    ValueError naming the file for one that cannot be decoded."""
+    ValueError naming the file for one that cannot be decoded.  progressive=True: progressive JPEG files decode too."""
     import os
     from . import imageio
     files = list_folder(root)
@@ -276,7 +276,7 @@ def load_folder(root, device="cuda"):
         with open(os.path.join(root, ident, f), "rb") as fh:
             blobs.append(fh.read())
     try:
-        buf, meta = imageio.decode_images(blobs, order="rgb", strict=True, device=device)
+        buf, meta = imageio.decode_images(blobs, order="rgb", strict=True, device=device, progressive=progressive)
     except imageio.DecodeError as e:
         raise ValueError("load_folder: %s: %s" % (os.path.join(*order[e.index]), e)) from None
     return files, buf, meta
