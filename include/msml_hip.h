@@ -1073,6 +1073,39 @@ int msml_png_decode(const unsigned char* streams, long stream_bytes, const int* 
                     const long* meta_out, int channels, int swap_rb, int* status, unsigned char* ws, long ws_bytes,
                     int N, void* stream);
 
+/* ---------------------------------------------------------------- PNG encoding -----------------------------------
+ * PIL.Image.save of a .png name on the device (eval/align_dataset.py:52-75, the '.png' payloads of
+ * datasets/3d_tools/cvt_casia_webface.py:35): N images of any sizes to N complete PNG files (signature, IHDR, one IDAT,
+ * IEND) that Pillow, zlib and msml_png_decode read back to exactly the source pixels.  The bytes are not Pillow's: the
+ * row filters are libpng's heuristic, the deflate stream is the device's own (one block per 65535 filtered bytes, each
+ * the cheapest of stored / fixed / dynamic / dynamic with literals only).  Integer arithmetic, order-independent LDS
+ * atomics only, one writer per output byte: two runs, and any batch composition, give the same bytes.  The mirror of
+ * msml_jpeg_encode; every argument it shares means the same.
+ *
+ *   src / meta [N][4] int64 (device) = byte offset, H, W, row pitch; channels 1 (colour type 0), 2 (4: gray + alpha),
+ *     3 (2) or 4 (6), 8-bit samples; swap_rb: the sources are B, G, R(, A) (channels 3 or 4 only).
+ *   filter: 0 none, 1 sub, 2 up, 3 average, 4 Paeth for every row; 5 adaptive: per row the filter with the smallest sum
+ *     of abs((int8) byte), ties to the lowest number.
+ *   desc / desc_host [N][4] int32: the same descriptors on the device and on the HOST (H, W, workspace offset, 0).
+ *   dst / out_meta [N][2] int64 (device) = byte offset and capacity of each image's slot; length [N] int32: the bytes
+ *     written (0 for an image with a status).
+ *   status [N] int32: 0, 1 a meta row that is not this image inside src, 2 a slot outside dst or too small, 3 an
+ *     unsupported geometry (a size outside 1..32767 or more than 2^30 - 1 filtered bytes).  Such an image writes
+ *     nothing outside its own workspace and slot; the other images are unaffected.
+ *   msml_png_encode_ws_bytes(desc, channels, N): on the HOST descriptors, writes each image's workspace offset into its
+ *     descriptor and returns the bytes msml_png_encode needs (0 for arguments it would refuse).
+ *   msml_png_encode_bound(H, W, channels): the all-stored worst case, which no file exceeds (0 for an unsupported
+ *     geometry): 8 signature + 25 IHDR + 12 IDAT overhead + 2 zlib header + n = H (W channels + 1) filtered bytes +
+ *     5 ceil(n / 65535) stored-block headers + 4 Adler-32 + 12 IEND.
+ *   MSML_ERR_UNSUPPORTED before any launch for N outside 1..65535, channels outside 1..4, a filter outside 0..5,
+ *   swap_rb with fewer than 3 channels; MSML_ERR_SHAPE for null or misaligned pointers (4 bytes; meta, out_meta 8, ws
+ *   16) and an inconsistent descriptor; MSML_ERR_WORKSPACE for a workspace that is too small. */
+long msml_png_encode_ws_bytes(int* desc, int channels, int N);
+long msml_png_encode_bound(int H, int W, int channels);
+int msml_png_encode(const unsigned char* src, long src_bytes, const long* meta, int channels, int swap_rb, int filter,
+                    const int* desc, const int* desc_host, unsigned char* dst, long dst_bytes, const long* out_meta,
+                    int* length, int* status, unsigned char* ws, long ws_bytes, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,3 +75,101 @@ def decode_images(blobs, order="rgb", strict=True, device="cuda", progressive=Fa
             raise DecodeError(i, kinds[i], got[i])
         return buf, meta
     return buf, meta, status
+
+
+# ------------------------------------------------------------------------------------------------------------ writing
+# PIL.Image.save(path) of eval/align_dataset.py:52-75 for a batch on the device: the format comes from the file name's
+# suffix as Pillow takes it, the JPEG and the PNG subsets each go out in one launch (jpeg.encode_batch,
+# png.encode_batch), and one device-to-host copy brings every file over.
+SUFFIXES = {".jpg": "jpeg", ".jpeg": "jpeg", ".jpe": "jpeg", ".jfif": "jpeg", ".png": "png"}
+
+
+def format_of(name):
+    """'jpeg' or 'png' from a format name ('png', 'JPEG', 'jpg') or a path / suffix ('.png', 'a/b.JPG'), as
+    PIL.Image.save reads it; ValueError for anything else."""
+    s = str(name).lower()
+    if s in ("jpeg", "jpg", "png"):
+        return "png" if s == "png" else "jpeg"
+    dot = s.rfind(".")
+    kind = SUFFIXES.get(s[dot:]) if dot >= 0 else None
+    if kind is None:
+        raise ValueError("unknown image format or suffix %r (JPEG: .jpg .jpeg .jpe .jfif, PNG: .png)" % (name,))
+    return kind
+
+
+class EncodedImages:
+    """encode_images' result: the JPEG and the PNG subset as jpeg.EncodedBatch each (None for an empty one) and the rows
+    of the caller's list each holds.  to_bytes() -> the files in the caller's order, after ONE device-to-host copy."""
+
+    def __init__(self, n, batches):
+        self.n, self.batches = n, batches                 # batches: [(kind, rows, EncodedBatch)]
+
+    def __len__(self):
+        return self.n
+
+    def to_bytes(self, strict=True):
+        parts, spans, o = [], [], 0
+        for kind, rows, b in self.batches:
+            tail = torch.stack([b.length, b.status]).view(torch.uint8).reshape(-1)
+            parts += [b.buf.reshape(-1), tail]
+            spans.append((o, o + b.buf.numel()))
+            o += b.buf.numel() + tail.numel()
+        host = torch.cat(parts).cpu().numpy()
+        out = [b""] * self.n
+        for (kind, rows, b), (lo, hi) in zip(self.batches, spans):
+            ls = host[hi:hi + 8 * len(rows)].view(np.int32).reshape(2, len(rows))
+            for k, i in enumerate(rows):
+                if ls[1, k] and strict:
+                    table = jpeg.ENCODE_STATUS if kind == "jpeg" else png.ENCODE_STATUS
+                    raise ValueError("encode_images: image %d: %s (status %d)" % (i, table.get(int(ls[1, k]), "?"), ls[1, k]))
+                s = lo + int(b.slots_host[k, 0])
+                out[i] = host[s:s + int(ls[0, k])].tobytes()
+        return out
+
+
+@torch.no_grad()
+def encode_images(images, formats, order="rgb", filter="adaptive", device="cuda", **jpeg_options):
+    """One door for writing: images uint8 [N, H, W, 3] (or [N, H, W]) or the packed 3-channel (buf, meta); formats one
+    name / suffix / path for all or one per image (format_of).  The JPEG rows go through jpeg.encode_batch with
+    jpeg_options (quality, sampling, restart), the PNG rows through png.encode_batch with `filter`: one launch sequence
+    per codec, the same bytes as the two codecs called on their rows.  -> EncodedImages.  No synchronisation."""
+    if isinstance(images, torch.Tensor):
+        if images.dtype != torch.uint8 or images.dim() not in (3, 4) or (images.dim() == 4 and images.shape[3] != 3):
+            raise ValueError("encode_images: images must be a uint8 [N, H, W, 3] or [N, H, W] tensor, or the packed (buf, meta)")
+        n, h, w = (int(v) for v in images.shape[:3])
+        channels = 3 if images.dim() == 4 else 1
+        meta = np.empty((n, 4), np.int64)
+        meta[:, 0] = np.arange(n, dtype=np.int64) * (h * w * channels)
+        meta[:, 1], meta[:, 2], meta[:, 3] = h, w, w * channels
+        buf = images.to(device).contiguous().reshape(-1)
+    else:
+        buf, meta = images
+        meta = np.ascontiguousarray(meta.cpu().numpy() if isinstance(meta, torch.Tensor) else meta, dtype=np.int64)
+        n, channels = len(meta), 3
+    kinds = [format_of(formats)] * n if isinstance(formats, str) else [format_of(f) for f in formats]
+    if len(kinds) != n:
+        raise ValueError("encode_images: %d formats for %d images" % (len(kinds), n))
+    batches = []
+    for kind in ("jpeg", "png"):
+        rows = [i for i in range(n) if kinds[i] == kind]
+        if not rows:
+            continue
+        sub = (buf, meta[rows])
+        if kind == "jpeg":
+            opts = {k: (v if isinstance(v, (str, int, np.integer)) else [v[i] for i in rows]) for k, v in jpeg_options.items()}
+            b = jpeg.encode_batch(sub, order=order, device=device, channels=channels, **opts)
+        else:
+            b = png.encode_batch(sub, order=order, filter=filter, device=device, channels=channels)
+        batches.append((kind, rows, b))
+    return EncodedImages(n, batches)
+
+
+def save_images(images, paths, order="rgb", filter="adaptive", device="cuda", **jpeg_options):
+    """PIL.Image.save(path) for every image: the format from each path's suffix (format_of), encode_images, one
+    device-to-host copy for which the host waits, then the file writes.  The directories must exist.  -> the paths."""
+    paths = [str(p) for p in paths]
+    files = encode_images(images, paths, order, filter, device, **jpeg_options).to_bytes()
+    for p, data in zip(paths, files):
+        with open(p, "wb") as f:
+            f.write(data)
+    return paths

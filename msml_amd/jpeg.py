@@ -567,10 +567,15 @@ class RecordFaceSource:
     faces, JpegBatch of the mask_out records, JpegBatch of the mask records, rows int32 [B], labels) with the renders
     of the samples data.mask_flags(seed, k * B, B, p_mask) selects only, rows[n] = the render of face n or -1 -- the
     flags DeviceLoaderX(seed=seed, p_mask=p_mask) draws for batch k of the pass.  close() (or `with`) closes the
-    record files."""
+    record files.  raw=True: yields (list of byte strings, labels) instead, for records whose payloads are PNG files
+    (png.encode_batch through write_faces) or a mix: imageio.decode_images reads those."""
 
-    def __init__(self, root, batch, steps=None, shuffle=False, seed=1, masks=False, p_mask=0.2, progressive=False):
+    def __init__(self, root, batch, steps=None, shuffle=False, seed=1, masks=False, p_mask=0.2, progressive=False,
+                 raw=False):
         self.progressive = progressive       # records may be progressive JPEG (pack_jpegs)
+        self.raw = raw                       # yield the payloads as byte strings (PNG or mixed records: imageio.decode_images)
+        if raw and masks:
+            raise ValueError("RecordFaceSource: raw=True yields the face payloads only (no masks)")
         self.rec = RecordFile(os.path.join(root, "train.rec"), os.path.join(root, "train.idx"))
         self.batch, self.steps, self.shuffle, self.seed = batch, steps, shuffle, seed
         self.masks, self.p_mask = masks, p_mask
@@ -610,6 +615,10 @@ class RecordFaceSource:
                 (_, label, _, _), body = self.rec.read_idx(int(i))
                 streams.append(body)
                 labels.append(int(label if np.isscalar(label) else label[0]))
+            if self.raw:
+                yield streams, torch.tensor(labels, dtype=torch.int64)
+                k += 1
+                continue
             item = (pack_jpegs(streams, self.headers, self.progressive), torch.tensor(labels, dtype=torch.int64))
             if self.masks:
                 flags = data.mask_flags(self.seed, k * self.batch, self.batch, self.p_mask)
@@ -857,7 +866,8 @@ class EncodedBatch:
             bad = np.flatnonzero(ls[1])
             if bad.size:
                 i = int(bad[0])
-                raise ValueError("encode: image %d: %s (status %d)" % (i, ENCODE_STATUS.get(int(ls[1, i]), "?"), ls[1, i]))
+                table = getattr(self.plan, "STATUS", ENCODE_STATUS)       # a PNG plan brings its own reasons
+                raise ValueError("encode: image %d: %s (status %d)" % (i, table.get(int(ls[1, i]), "?"), ls[1, i]))
         return [host[o:o + l].tobytes() for o, l in zip(self.slots_host[:, 0], ls[0])]
 
 
@@ -1005,7 +1015,8 @@ class RecordWriter:
 
 def write_faces(writer, encoded, labels, first_key=1, header0=None):
     """What datasets/3d_tools/cvt_casia_webface.py:40-60 does with a batch: record first_key + n holds IRHeader(0,
-    labels[n], 0, 0) and the JPEG stream of image n (one synchronising copy, EncodedBatch.to_bytes).  header0 = (count,
+    labels[n], 0, 0) and the JPEG stream of image n (one synchronising copy, EncodedBatch.to_bytes), or the PNG file when
+    `encoded` comes from png.encode_batch (that script's img_fmt='.png', line 35).  header0 = (count,
     classes): also write record 0 as that script's lines 31-37 do, with the labels (count + 1, classes) and id 1, which is
     what load_dataset.py:51-57 (and RecordFile) read the number of samples from; its image (a PNG of zeros there, never
     decoded) is left empty.  -> the next free key."""

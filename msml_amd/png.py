@@ -279,3 +279,165 @@ def decode_batch(batch, size=None, order="rgb", strict=True, channels=3, device=
 
 _CODEC = _codec.Codec(pack_pngs, PngBatch, (1, 3, 4),
                       lambda d: None if d.colour_type in (0, 4) else "colour type %d" % d.colour_type, decode_into, STATUS)
+
+
+# ---------------------------------------------------------------------------------------------------------- encoding
+# PNG files from pixels on the device (csrc/png_enc.hip, csrc/png_enc_core.h): what PIL.Image.save writes for the .png
+# names of eval/align_dataset.py:52-75 and the '.png' payloads of datasets/3d_tools/cvt_casia_webface.py:35 -- files
+# Pillow, zlib and msml_png_decode read back to exactly the source pixels.  The bytes are NOT Pillow's (PNG is lossless,
+# and zlib's lazy matcher is sequential): 8-bit samples, colour type 0 / 4 / 2 / 6 for 1 / 2 / 3 / 4 channels, no
+# interlace, one IDAT chunk, no ancillary chunks.  tests/png_enc_cases.py restates the filter pass and the container.
+ENC_DESC_WORDS = 4
+(PE_H, PE_W, PE_WS) = 0, 1, 2
+FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+COLOUR_TYPE_OF = {1: 0, 2: 4, 3: 2, 4: 6}
+ENCODE_STATUS = {0: "ok", 1: "the meta row is not this image inside the source buffer",
+                 2: "the slot is outside the output buffer or too small for the file",
+                 3: "unsupported geometry (a size outside 1..32767, or more than 2^30 - 1 filtered bytes)"}
+
+
+def encode_bound(height, width, channels):
+    """msml_png_encode_bound: the all-stored worst case, which no file exceeds (0 for an unsupported geometry)."""
+    return value("msml_png_encode_bound", int(height), int(width), int(channels))
+
+
+class PngEncodePlan:
+    """What msml_png_encode reads besides the pixels: desc int32 [N, 4] (pinned) = H, W, workspace offset; bounds int64
+    [N] = msml_png_encode_bound of every image rounded up to 4; ws_bytes.  The twin of jpeg.EncodePlan."""
+
+    STATUS = ENCODE_STATUS
+
+    def __init__(self, sizes, channels):
+        n = len(sizes)
+        if n == 0:
+            raise ValueError("encode: needs at least one image")
+        self.n, self.sizes, self.channels = n, [(int(h), int(w)) for h, w in sizes], int(channels)
+        self.desc = pinned((n, ENC_DESC_WORDS), torch.int32)
+        dn = self.desc.numpy()
+        dn[...] = 0
+        self.bounds = np.zeros(n, np.int64)
+        for i, (h, w) in enumerate(self.sizes):
+            if not (1 <= h <= 32767 and 1 <= w <= 32767):
+                raise ValueError("encode: image %d is %d x %d, sizes must be 1..32767" % (i, h, w))
+            b = encode_bound(h, w, channels)
+            if b <= 0:
+                raise ValueError("encode: image %d (%d x %d x %d) holds more than 2^30 - 1 filtered bytes" % (i, h, w, channels))
+            dn[i, PE_H], dn[i, PE_W] = h, w
+            self.bounds[i] = (b + 3) & ~3
+        self.ws_bytes = value("msml_png_encode_ws_bytes", self.desc.data_ptr(), self.channels, n)
+        if self.ws_bytes <= 0:
+            raise RuntimeError("msml_png_encode_ws_bytes refused the descriptors")
+        self._dev = None
+
+    def to_device(self, device="cuda"):
+        if self._dev is None or self._dev.device != torch.device(device):
+            self._dev = self.desc.to(device, non_blocking=True)
+        return self._dev
+
+
+_PLANS = {}
+
+
+def _plan(sizes, channels):
+    if len(set(sizes)) == 1:
+        key = (len(sizes), sizes[0], channels)
+        if key not in _PLANS:
+            if len(_PLANS) >= 16:
+                _PLANS.clear()
+            _PLANS[key] = PngEncodePlan(sizes, channels)
+        return _PLANS[key]
+    return PngEncodePlan(sizes, channels)
+
+
+def _check_options(channels, order, filter, who):
+    if channels not in (1, 2, 3, 4):
+        raise ValueError("%s: channels must be 1..4, got %r" % (who, channels))
+    if order not in ("rgb", "bgr"):
+        raise ValueError("%s: order must be 'rgb' or 'bgr'" % who)
+    if order == "bgr" and channels < 3:
+        raise ValueError("%s: order 'bgr' needs 3 or 4 channels, got %d" % (who, channels))
+    if filter not in FILTERS:
+        raise ValueError("%s: filter must be one of %s, got %r" % (who, sorted(FILTERS), filter))
+
+
+def _source(images, channels):
+    """-> (src uint8 tensor, meta int64 numpy [N][4] or None for a contiguous tensor, sizes, channels), nothing moved."""
+    if isinstance(images, (tuple, list)) and len(images) == 2 and isinstance(images[0], torch.Tensor) and images[0].dim() == 1:
+        buf, meta = images
+        meta = np.ascontiguousarray(meta.cpu().numpy() if isinstance(meta, torch.Tensor) else meta, dtype=np.int64)
+        if buf.dtype != torch.uint8 or meta.ndim != 2 or meta.shape[1] != 4:
+            raise ValueError("encode: the packed form is (uint8 buffer, int64 meta [N][4])")
+        return buf, meta, [(int(h), int(w)) for h, w in meta[:, 1:3]], channels
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() not in (3, 4):
+        raise ValueError("encode: images must be a uint8 [N, H, W] or [N, H, W, C] tensor, or the packed (buf, meta)")
+    c = int(images.shape[3]) if images.dim() == 4 else 1
+    if images.dim() == 4 and not 2 <= c <= 4:
+        raise ValueError("encode: [N, H, W, C] takes C in 2..4, got %d" % c)
+    return images, None, [(int(images.shape[1]), int(images.shape[2]))] * images.shape[0], c
+
+
+@torch.no_grad()
+def encode_into(src, meta, dst, slots, channels=3, order="rgb", filter="adaptive", length=None, status=None, ws=None,
+                plan=None):
+    """msml_png_encode with the caller's buffers, on the current stream.  src: uint8 on the device; meta: int64 [N][4] on
+    the device = byte offset, H, W, pitch of each source, or the same in numpy (uploaded here); dst: uint8 on the device;
+    slots: int64 [N][2] on the device = byte offset and capacity of each image's slot.  length / status int32 [N] and ws
+    are allocated when None.  plan: a PngEncodePlan of the sizes (needed when meta is on the device only, where the host
+    cannot read the sizes).  -> (length, status).  The device checks every meta row against src and every slot against
+    dst: an image that does not fit gets a status (ENCODE_STATUS) and length 0 and writes nothing outside its slot."""
+    _check_options(channels, order, filter, "encode_into")
+    device = dst.device
+    if plan is None:
+        if isinstance(meta, torch.Tensor):
+            raise ValueError("encode_into: a meta tensor on the device needs plan= (the host lays out the workspace)")
+        meta = np.ascontiguousarray(meta, dtype=np.int64)
+        plan = _plan([(int(h), int(w)) for h, w in meta[:, 1:3]], channels)
+    n = plan.n
+    if plan.channels != channels:
+        raise ValueError("encode_into: the plan is for %d channels, not %d" % (plan.channels, channels))
+    meta = packed.meta_on_device(meta, n, device, "encode_into")
+    if not isinstance(slots, torch.Tensor) or slots.dtype != torch.int64 or tuple(slots.shape) != (n, 2) or \
+            slots.device != device or not slots.is_contiguous():
+        raise ValueError("encode_into: slots must be a contiguous int64 [%d, 2] tensor on %s" % (n, device))
+    desc = plan.to_device(device)
+    if length is None:
+        length = torch.empty(n, dtype=torch.int32, device=device)
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=device)
+    if ws is None:
+        ws = torch.empty(plan.ws_bytes, dtype=torch.uint8, device=device)
+    call("msml_png_encode", src, src.numel(), meta, channels, 1 if order == "bgr" else 0, FILTERS[filter], desc,
+         plan.desc.data_ptr(), dst, dst.numel(), slots, length, status, ws, ws.numel(), n)
+    return length, status
+
+
+@torch.no_grad()
+def encode_batch(images, order="rgb", filter="adaptive", device="cuda", channels=3, slot_bytes=None):
+    """Encode N images on the device to PNG files -> jpeg.EncodedBatch (to_bytes, write_faces and imageio.save_images
+    take it as they take a JPEG one; its plan is a PngEncodePlan).  No synchronisation.
+
+    images: uint8 [N, H, W] (gray), [N, H, W, C] with C 2 (gray + alpha), 3 (RGB) or 4 (RGBA), or the packed (buf, meta)
+    of ijb.pack_images / decode_batch with `channels` bytes per pixel.  order "bgr": the sources are B, G, R(, A).
+    filter: "adaptive" (per row the filter with the smallest sum of abs((int8) byte), ties to the lowest number: the
+    libpng / Pillow heuristic) or one of "none", "sub", "up", "average", "paeth" for every row.  slot_bytes: the capacity
+    of every slot; the default is msml_png_encode_bound, the all-stored worst case no file exceeds (photographs take
+    about 0.65 of it), so a caller that knows its data may pass less (an image that does not fit gets status 2)."""
+    from .jpeg import EncodedBatch
+    src, meta, sizes, channels = _source(images, channels)
+    _check_options(channels, order, filter, "encode")
+    plan = _plan(sizes, channels)
+    n = plan.n
+    src = src.to(device).contiguous()
+    if meta is None:
+        h, w = sizes[0]
+        meta_dev = packed.uniform_meta(n, h, w, channels, src.device)
+    else:
+        meta_dev = torch.from_numpy(meta).to(src.device)
+    caps = plan.bounds if slot_bytes is None else np.full(n, (int(slot_bytes) + 3) & ~3, np.int64)
+    slots = np.empty((n, 2), np.int64)
+    slots[:, 1] = caps
+    slots[:, 0] = np.cumsum(caps) - caps
+    dst = torch.empty(int(caps.sum()), dtype=torch.uint8, device=src.device)
+    slots_dev = torch.from_numpy(slots).to(src.device)
+    length, status = encode_into(src.reshape(-1), meta_dev, dst, slots_dev, channels, order, filter, plan=plan)
+    return EncodedBatch(dst, slots_dev, slots, length, status, plan)

@@ -282,6 +282,21 @@ def load_folder(root, device="cuda", progressive=False):
     return files, buf, meta
 
 
+def save_folder(root, names, images, order="rgb", **options):
+    """The writing twin of load_folder, the layout eval/align_dataset.py:52-75 produces: image k goes to
+    root/<identity>/<file> for names[k] = (identity, file) or "identity/file", its format taken from the file's suffix as
+    PIL.Image.save takes it (imageio.save_images: .png files are PNG, .jpg / .jpeg files JPEG with `options` = quality,
+    sampling, restart, filter).  images: uint8 [N, H, W, 3] on the device or the packed (buf, meta).  -> the paths."""
+    import os
+    from . import imageio
+    pairs = [tuple(n.split("/", 1)) if isinstance(n, str) else tuple(n) for n in names]
+    if any(len(p) != 2 or not p[0] or not p[1] or "/" in p[1] or os.sep in p[1] for p in pairs):
+        raise ValueError("save_folder: names are (identity, file) pairs or 'identity/file' strings")
+    for ident in sorted({p[0] for p in pairs}):
+        os.makedirs(os.path.join(root, ident), exist_ok=True)
+    return imageio.save_images(images, [os.path.join(root, i, f) for i, f in pairs], order, **options)
+
+
 def _no_block(lo, hi):
     return (lo is None and hi is None) or (lo == 0 and hi == 1)
 
