@@ -267,6 +267,20 @@ int msml_bn_act_bwd(const void* dy, const void* x, const float* scale, const flo
                     const void* residual_first, void* dx, void* dres, float* dgamma, float* dbeta,
                     float* dalpha, int accumulate, long M, int C, float* workspace, long ws_floats,
                     int dtype, void* stream);
+/* Backward through an EVAL-mode (frozen) BatchNorm: (scale, shift) come from the running statistics and are constants
+ * of the graph.  With z = x * scale + shift [+ residual_first] and g = dy * (z <= 0 ? alpha : 1) (g = dy without alpha):
+ *   dx = scale * g, dres = g, dbeta = sum g, dgamma = sum g * (x - mean) * invstd, dalpha = sum dy * min(z, 0)
+ * (mean / invstd: the running mean and 1 / sqrt(running_var + eps), needed for dgamma only).  One streaming pass; dgamma,
+ * dbeta and dalpha are each optional, and with none of them there is no reduction, no second launch and `workspace` may
+ * be null.  With any of them: workspace >= msml_bn_eval_act_bwd_rows(M, C) * 3 * C floats (MSML_ERR_WORKSPACE
+ * otherwise); accumulate as in msml_bn_act_bwd.  C % 8 == 0, C <= 2048 (MSML_ERR_SHAPE), C / 8 divides 256
+ * (MSML_ERR_UNSUPPORTED); every refusal comes before any launch. */
+int msml_bn_eval_act_bwd_rows(long M, int C);
+int msml_bn_eval_act_bwd(const void* dy, const void* x, const float* scale, const float* shift,
+                         const float* alpha, const float* mean, const float* invstd,
+                         const void* residual_first, void* dx, void* dres, float* dgamma, float* dbeta,
+                         float* dalpha, int accumulate, long M, int C, float* workspace, long ws_floats,
+                         int dtype, void* stream);
 /* db[c] = sum over pixels of dy (biased GCM convs, backbones/osb/unet.py:23-30);
  * workspace >= msml_bn_stats_rows(M,Cp)*2*Cp floats. */
 int msml_bias_grad(const void* dy, long M, int Cp, int Creal, float* db, int accumulate,

@@ -35,7 +35,8 @@ class resblock_bottle(nn.Module):
 
     def forward(self, x):
         if self.training and x.dtype == torch.bfloat16 and torch.is_grad_enabled() and ops.BLOCK_FUNCTION \
-                and ops.BOTTLE_FUNCTION and self.stored_as_is:
+                and ops.BOTTLE_FUNCTION and self.stored_as_is \
+                and self.bn1.training and self.bn2.training and self.bn3.training:    # a frozen BatchNorm: unfused path
             return blocks.bottleneck(self, x)      # one autograd node, fused backward (blocks.py)
         out = conv_bn(self.conv1, self.bn1, x, prelu=self.prelu1)
         out = conv_bn(self.conv2, self.bn2, out, prelu=self.prelu2)

@@ -43,7 +43,11 @@ class IBasicBlock(nn.Module):
         self.stride = stride
 
     def forward(self, x):
-        if self.training and x.dtype == torch.bfloat16 and torch.is_grad_enabled() and ops.BLOCK_FUNCTION:
+        # (the one-node block normalises with batch statistics: only when EVERY BatchNorm of the block is live -- a frozen
+        # one (bn.eval() under a training block) takes the launch-by-launch path below, which reads each BatchNorm's own flag)
+        if self.training and x.dtype == torch.bfloat16 and torch.is_grad_enabled() and ops.BLOCK_FUNCTION \
+                and self.bn1.training and self.bn2.training and self.bn3.training \
+                and (self.downsample is None or self.downsample[1].training):
             return blocks.iblock(self, x)          # one autograd node, fused backward (blocks.py)
         out = Fh.bn_conv_bn_eval_x3(x, self.bn1, self.conv1, self.bn2, self.prelu) if isinstance(x, Fh.SplitT) else None
         if out is None:

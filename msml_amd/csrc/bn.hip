@@ -1047,3 +1047,133 @@ extern "C" int msml_add(const void* a, const void* b, void* out, long n, int dty
   MSML_LAUNCH_OK("add");
   return MSML_OK;
 }
+
+// ------------------------------------------------------------------ backward, eval mode (frozen BatchNorm) -------
+// y = prelu(x * scale + shift [+ res]) [+ res] with (scale, shift) from the RUNNING statistics: constants of the graph,
+// not functions of x.  With z the pre-activation and g = dy * (z <= 0 ? alpha : 1):
+//   dx = scale * g, dres = g (res_first), dbeta = sum g, dgamma = sum g * (x - running_mean) * invstd,
+//   dalpha = sum dy * min(z, 0).
+// The mean(g) / xhat * mean(g * xhat) terms of the training formula are absent, so dx needs no sums: ONE streaming pass
+// (read dy, x [, res]; write dx [, dres]) against the two passes over dy and x of msml_bn_act_bwd.  SUMS: the three sums
+// ride on that pass -- registers, LDS fold per workgroup as the NEXT branch of k_bn_bwd_apply, one [3][C] row per
+// workgroup -- and k_bn_eval_bwd_finalize folds the rows in f64.  Without SUMS: no LDS, no workspace, no second launch.
+template <typename T, bool SUMS>
+__global__ void __launch_bounds__(256) k_bn_eval_bwd(const T* __restrict__ dy, const T* __restrict__ x,
+                                                     const float* __restrict__ scale,
+                                                     const float* __restrict__ shift,
+                                                     const float* __restrict__ alpha,
+                                                     const float* __restrict__ mean,
+                                                     const float* __restrict__ invstd,
+                                                     const T* __restrict__ res, T* __restrict__ dx,
+                                                     T* __restrict__ dres, long n8, int C8,
+                                                     float* __restrict__ partial) {
+  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const int c0 = (int)(tid % C8) * 8;
+  const Coef8 sc = ldc8(scale, c0, 1.f), sh = ldc8(shift, c0, 0.f), al = ldc8(alpha, c0, 1.f);
+  const Coef8 mu = ldc8(SUMS ? mean : nullptr, c0, 0.f), is = ldc8(SUMS ? invstd : nullptr, c0, 1.f);
+  float q0[8], q1[8], q2[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) q0[j] = q1[j] = q2[j] = 0.f;
+  for (long i = tid; i < n8; i += (long)gridDim.x * blockDim.x) {
+    Vec8 g = load8<T>(dy + i * 8);
+    Vec8 v = load8<T>(x + i * 8);
+    Vec8 rr;
+    if (res) rr = load8<T>(res + i * 8);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      float gg = g.v[j];
+      if (alpha) {
+        float z = v.v[j] * sc.v[j] + sh.v[j];
+        if (res) z += rr.v[j];
+        if (z <= 0.f) {
+          if (SUMS) q2[j] += gg * z;
+          gg *= al.v[j];
+        }
+      }
+      if (SUMS) {
+        q0[j] += gg;
+        q1[j] += gg * ((v.v[j] - mu.v[j]) * is.v[j]);
+      }
+      v.v[j] = sc.v[j] * gg;
+      g.v[j] = gg;
+    }
+    store8<T>(dx + i * 8, v);
+    if (dres) store8<T>(dres + i * 8, g);
+  }
+  if (SUMS) {
+    // threads t, t + C8, ... of the block share a channel chunk: fixed-order sum through LDS
+    __shared__ float red[3][256][9];
+    const int t = threadIdx.x, C = C8 * 8;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      red[0][t][j] = q0[j];
+      red[1][t][j] = q1[j];
+      red[2][t][j] = q2[j];
+    }
+    __syncthreads();
+    for (int i = t; i < 3 * C; i += 256) {
+      const int q = i / C, c = i % C, cx = c >> 3, j = c & 7;
+      float sum = 0.f;
+      for (int k = cx; k < 256; k += C8) sum += red[q][k][j];
+      partial[((long)blockIdx.x * 3 + q) * C + c] = sum;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(1024) k_bn_eval_bwd_finalize(const float* __restrict__ partial, int rows, int C,
+                                                               float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                               float* __restrict__ dalpha, int accumulate) {
+  const int c = blockIdx.x * FIN_CPB + (threadIdx.x & (FIN_CPB - 1));
+  const bool cok = c < C;
+  double s[3];
+  fin_reduce<3>(partial, rows, C, c, cok, s);
+  if (threadIdx.x >= FIN_CPB || !cok) return;
+  if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s[0];
+  if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)s[1];
+  if (dalpha) dalpha[c] = (accumulate ? dalpha[c] : 0.f) + (float)s[2];
+}
+
+extern "C" int msml_bn_eval_act_bwd_rows(long M, int C) {
+  if (M <= 0 || C <= 0 || C % 8) return 0;
+  return ew_grid_c(M * (C / 8), C / 8);
+}
+
+extern "C" int msml_bn_eval_act_bwd(const void* dy, const void* x, const float* scale, const float* shift,
+                                    const float* alpha, const float* mean, const float* invstd,
+                                    const void* residual_first, void* dx, void* dres, float* dgamma, float* dbeta,
+                                    float* dalpha, int accumulate, long M, int C, float* workspace, long ws_floats,
+                                    int dtype, void* stream) {
+  MSML_CHECK(dy && x && dx && scale && shift && M > 0 && C > 0 && C % 8 == 0 && C <= 2048, MSML_ERR_SHAPE,
+             "bn_eval_act_bwd: bad args M=%ld C=%d", M, C);
+  MSML_CHECK(!dgamma || (mean && invstd), MSML_ERR_SHAPE, "bn_eval_act_bwd: dgamma needs mean and invstd");
+  MSML_CHECK(!dalpha || alpha, MSML_ERR_SHAPE, "bn_eval_act_bwd: dalpha without alpha");
+  MSML_CHECK(!dres || residual_first, MSML_ERR_SHAPE, "bn_eval_act_bwd: dres without residual_first");
+  // a thread's coefficients live in registers: needs (threads in grid) % (C/8) == 0, see ew_grid_c
+  MSML_CHECK(256 % (C / 8) == 0, MSML_ERR_UNSUPPORTED, "bn_eval_act_bwd: C/8 = %d must divide 256", C / 8);
+  MSML_CHECK(dtype == MSML_F32 || dtype == MSML_BF16, MSML_ERR_DTYPE, "bn_eval_act_bwd: unsupported dtype %d", dtype);
+  const bool sums = dgamma || dbeta || dalpha;
+  const long n8 = M * (C / 8);
+  const int grid = ew_grid_c(n8, C / 8);
+  if (sums) {
+    const long need = (long)grid * 3 * C;
+    MSML_CHECK(workspace && ws_floats >= need, MSML_ERR_WORKSPACE, "bn_eval_act_bwd: workspace %ld < %ld floats",
+               workspace ? ws_floats : 0L, need);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  MSML_DISPATCH_DTYPE(
+      dtype, "bn_eval_act_bwd",
+      if (sums)
+        (k_bn_eval_bwd<DT, true>)<<<grid, 256, 0, st>>>((const DT*)dy, (const DT*)x, scale, shift, alpha, mean, invstd,
+                                                        (const DT*)residual_first, (DT*)dx, (DT*)dres, n8, C / 8,
+                                                        workspace);
+      else
+        (k_bn_eval_bwd<DT, false>)<<<grid, 256, 0, st>>>((const DT*)dy, (const DT*)x, scale, shift, alpha, nullptr,
+                                                         nullptr, (const DT*)residual_first, (DT*)dx, (DT*)dres, n8,
+                                                         C / 8, nullptr);)
+  MSML_LAUNCH_OK("bn_eval_bwd");
+  if (sums) {
+    k_bn_eval_bwd_finalize<<<cdiv(C, FIN_CPB), 1024, 0, st>>>(workspace, grid, C, dgamma, dbeta, dalpha, accumulate);
+    MSML_LAUNCH_OK("bn_eval_bwd_finalize");
+  }
+  return MSML_OK;
+}

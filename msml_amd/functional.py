@@ -282,7 +282,7 @@ class _BnAct(torch.autograd.Function):
     def backward(ctx, dy, *_dacc):
         x, coef, alpha, res = ctx.saved_tensors
         if not ctx.training:
-            raise RuntimeError("msml_amd: backward through eval-mode BatchNorm is not supported")
+            return _BnAct._backward_eval(ctx, dy, x, coef, alpha, res)
         c = x.shape[-1]
         m = x.numel() // c
         dtype = DTYPE_OF[x.dtype]
@@ -314,6 +314,46 @@ class _BnAct(torch.autograd.Function):
             dy = dres
         if inplace:
             ops.grad_ready(*[prm for w, prm in zip(want, (gamma, beta, alpha_p)) if w])
+        return (dx, None,
+                pg[0] if want[0] and not inplace else None,
+                pg[1] if want[1] and not inplace else None,
+                pg[2] if want[2] and not inplace else None,
+                dy if has_r else None, None, None, None, None, None, None, None)
+
+    @staticmethod
+    def _backward_eval(ctx, dy, x, coef, alpha, res):
+        """Backward through a frozen BatchNorm (eval mode: scale / shift come from the running statistics and are
+        constants of the graph): one streaming pass, msml_bn_eval_act_bwd.  Only the parameter gradients somebody asked
+        for are reduced; with none (every affine parameter frozen) the call has no reduction and no workspace."""
+        c = x.shape[-1]
+        m = x.numel() // c
+        dtype = DTYPE_OF[x.dtype]
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        dres = torch.empty_like(x) if ctx.res_first else None
+        has_g, has_b, has_a, has_r = ctx.has
+        params = ctx.params
+        want = (has_g and ctx.needs_input_grad[2], has_b and ctx.needs_input_grad[3],
+                has_a and ctx.needs_input_grad[4])
+        # parameter gradients go straight into the flat arena when FlatSGD owns the .grad views
+        inplace = any(want) and all((not w) or ops.inplace(prm) for w, prm in zip(want, params))
+        pg, ws = None, None
+        if inplace:
+            tg = [prm.grad if w else None for w, prm in zip(want, params)]
+        elif any(want):
+            pg = torch.empty(3, c, dtype=torch.float32, device=x.device)
+            tg = [pg[i] if w else None for i, w in enumerate(want)]
+        else:
+            tg = [None, None, None]
+        if any(want):
+            ws = ops.workspace(_lib.value("msml_bn_eval_act_bwd_rows", m, c) * 3 * c * 4, x.device)
+        with ops.PROFILE.rec("bn_eval_act_bwd", 0.0, x.numel() * x.element_size() * (3 + (2 if ctx.res_first else 0))):
+            call("msml_bn_eval_act_bwd", dy, x, coef[0], coef[1], alpha, coef[2], coef[3], res, dx, dres,
+                 tg[0], tg[1], tg[2], int(inplace), m, c, ws, ws.numel() // 4 if ws is not None else 0, dtype)
+        if ctx.res_first:
+            dy = dres
+        if inplace:
+            ops.grad_ready(*[prm for w, prm in zip(want, params) if w])
         return (dx, None,
                 pg[0] if want[0] and not inplace else None,
                 pg[1] if want[1] and not inplace else None,
