@@ -103,26 +103,28 @@ __global__ void __launch_bounds__(256) k_bn_stats(const T* __restrict__ x, long 
 
 extern "C" int msml_bn_stats_rows(long M, int C) { return red_rows(M, C); }
 
-extern "C" int msml_bn_stats(const void* x, long M, int C, float* partial, int dtype, void* stream) {
+// msml_bn_stats and msml_bn_stats_acc: partial rows or, with acc_mode, an accumulator (common.h)
+static int bn_stats(const void* x, long M, int C, float* partial, int acc_mode, int dtype, void* stream) {
   MSML_CHECK(x && partial && M > 0 && C > 0 && C % 8 == 0 && C <= 2048, MSML_ERR_SHAPE,
              "bn_stats: bad shape M=%ld C=%d", M, C);
   int rows = red_rows(M, C);
   MSML_DISPATCH_DTYPE(dtype, "bn_stats",
                       if (rows <= RED_PIPE_MAX_ROWS)
-                        (k_bn_stats<DT, true>)<<<rows, 256, red_lds(2, C), (hipStream_t)stream>>>((const DT*)x, M, C, partial, msml_tl_stats_acc);
+                        (k_bn_stats<DT, true>)<<<rows, 256, red_lds(2, C), (hipStream_t)stream>>>((const DT*)x, M, C, partial, acc_mode);
                       else
-                        (k_bn_stats<DT, false>)<<<rows, 256, red_lds(2, C), (hipStream_t)stream>>>((const DT*)x, M, C, partial, msml_tl_stats_acc);)
+                        (k_bn_stats<DT, false>)<<<rows, 256, red_lds(2, C), (hipStream_t)stream>>>((const DT*)x, M, C, partial, acc_mode);)
   MSML_LAUNCH_OK("bn_stats");
   return MSML_OK;
+}
+
+extern "C" int msml_bn_stats(const void* x, long M, int C, float* partial, int dtype, void* stream) {
+  return bn_stats(x, M, C, partial, 0, dtype, stream);
 }
 
 // msml_bn_stats into an accumulator (zero-initialised double[8][2][C], common.h) for msml_bn_fin_act_fwd
 extern "C" int msml_bn_stats_acc(const void* x, long M, int C, double* acc, int dtype, void* stream) {
   MSML_CHECK(acc, MSML_ERR_SHAPE, "bn_stats_acc: null accumulator");
-  msml_tl_stats_acc = 1;
-  const int rc = msml_bn_stats(x, M, C, reinterpret_cast<float*>(acc), dtype, stream);
-  msml_tl_stats_acc = 0;
-  return rc;
+  return bn_stats(x, M, C, reinterpret_cast<float*>(acc), 1, dtype, stream);
 }
 
 // ------------------------------------------------------------------ finalize (forward) -------

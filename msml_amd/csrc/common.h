@@ -10,16 +10,15 @@
 // producer is a zero-initialised double[MSML_ACC_ROWS][2][C] and every workgroup adds its per-channel (sum, sumsq)
 // with f64 atomics into row (workgroup index % MSML_ACC_ROWS) instead of storing a partial row of its own.  The
 // f64 sum of f32 partials is exact unless two partials differ by more than 2^29, so the result does not depend on
-// the order of the adds (and equals the fixed-order f64 sum of the row format).  The mode travels from the C entry
-// point to the launch sites in a thread-local (set and reset inside one call: the library stays reentrant).
+// the order of the adds (and equals the fixed-order f64 sum of the row format).  The mode is an argument like any
+// other: the `stats_acc` field of a conv call (conv_call.h), set by the C entry point and read at the launch sites, and a
+// plain parameter of the statistics launch in bn.hip.
 #ifndef MSML_ACC_ROWS
 #define MSML_ACC_ROWS 8
 #endif
-extern thread_local int msml_tl_stats_acc;
 // Border-class bias (msml_conv2d_x3_border, conv_igemm.hip): `bias` of a 3x3 / stride-1 / pad-1 forward launch points at
 // float[9][coutp], row (cy * 3 + cx) with cy / cx = 0 on the first row / column of the map, 2 on the last, 1 inside.
-// Travels from the C entry point to the launch sites like msml_tl_stats_acc.
-extern thread_local int msml_tl_bias9;
+// Travels as the `bias9` field of the conv call.
 __device__ __forceinline__ int border_class(int y, int x, int H, int W) {
   return ((y == 0) ? 0 : (y == H - 1 ? 2 : 1)) * 3 + ((x == 0) ? 0 : (x == W - 1 ? 2 : 1));
 }
@@ -51,6 +50,9 @@ void msml_set_error(const char* fmt, ...);
   } while (0)
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Compute units of the current device (core.hip): read once, 256 (an MI355X) where no device answers.
+int msml_num_cus();
 
 // ---- LDS high-water guard --------------------------------------------------------------------
 // Every kernel with dynamic LDS derives its regions (tile rings, transpose tiles, reduction scratch, coefficient tables)

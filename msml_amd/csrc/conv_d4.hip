@@ -15,6 +15,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "conv_call.h"
 #include "options.h"
 
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -152,23 +153,22 @@ __global__ void __launch_bounds__(512) k_deconv4_fwd(const ConvD4Args p) {
 #endif
 }
 
-bool msml_deconv4_applies(int c0p, int c1p, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
-                          int pad_h, int pad_w, int transposed) {
+bool msml_deconv4_applies(const ConvShape& s) {
   const bool off = msml_opt().no_d4_conv;
-  if (off || !transposed || R != 4 || S != 4 || stride != 2 || pad_h != 1 || pad_w != 1) return false;
-  if (c0p != 32 || c1p != 32 || coutp != 32 || H != W || P != 2 * H || Q != 2 * W) return false;
-  if (!(H == 56 || H == 28 || H == 14)) return false;
-  if ((long)N * H * W * 64 >= 0x70000000L) return false;
+  if (off || !s.transposed || s.R != 4 || s.S != 4 || s.stride != 2 || s.pad_h != 1 || s.pad_w != 1) return false;
+  if (s.c0p != 32 || s.c1p != 32 || s.coutp != 32 || s.H != s.W || s.P != 2 * s.H || s.Q != 2 * s.W) return false;
+  if (!(s.H == 56 || s.H == 28 || s.H == 14)) return false;
+  if ((long)s.N * s.H * s.W * 64 >= 0x70000000L) return false;
   return true;
 }
 
-bool msml_deconv4_dispatch(const void* in0, const void* in1, const void* wp, int kop, const float* bias, void* out, int N,
-                           int H, hipStream_t st) {
+bool msml_deconv4_dispatch(const ConvCall& c) {
+  const int N = c.N, H = c.H;
   ConvD4Args a;
-  a.in0 = (const unsigned short*)in0; a.in1 = (const unsigned short*)in1;
+  a.in0 = (const unsigned short*)c.in0; a.in1 = (const unsigned short*)c.in1;
   a.in_bytes = (unsigned int)((long)N * H * H * 64);
-  a.wp = (const unsigned short*)wp; a.w_bytes = (unsigned int)((long)kop * 1024 * 2);
-  a.out = (unsigned short*)out; a.bias = bias;
+  a.wp = (const unsigned short*)c.wp; a.w_bytes = (unsigned int)((long)c.kop * 1024 * 2);
+  a.out = (unsigned short*)c.out; a.bias = c.bias;
   a.N = N; a.H = H; a.ty = cdiv(H, 14); a.tx = cdiv(H, 16);
   a.ntiles = N * a.ty * a.tx;
   const size_t lds = 2 * 16 * 32 * 64 + 2 * 2 * 18 * 1024;
@@ -177,10 +177,9 @@ bool msml_deconv4_dispatch(const void* in0, const void* in1, const void* wp, int
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_deconv4_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
   });
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int cus = msml_num_cus();
   int grid = cus < a.ntiles ? cus : a.ntiles;
-  k_deconv4_fwd<<<dim3(grid), dim3(512), lds, st>>>(a);
+  k_deconv4_fwd<<<dim3(grid), dim3(512), lds, c.st>>>(a);
   return true;
 }
 
@@ -312,8 +311,7 @@ extern "C" int msml_deconv4_bwd_data(const void* dy, const void* wp0, const void
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_deconv4_bwd), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
   });
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int cus = msml_num_cus();
   const int grid = cus < a.ntiles ? cus : a.ntiles;
   k_deconv4_bwd<<<dim3(grid), dim3(512), lds, (hipStream_t)stream>>>(a);
   MSML_LAUNCH_OK("deconv4_bwd_data");

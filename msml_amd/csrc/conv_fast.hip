@@ -21,6 +21,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "conv_call.h"
 #include "options.h"
 
 struct ConvFastArgs {
@@ -564,50 +565,24 @@ static void launch_fast(ConvFastArgs& a, hipStream_t st) {
   k_conv_fast<TOUT, BM, BN, WGM, WGN, NST, FUSE, X3><<<grid, dim3(WGM * WGN * 64), lds, st>>>(a);
 }
 
-bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out,
-                             int coutp, float* stats, int N, int H, int W, int P, int Q, int R, int S,
-                             int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
-                             const float* scale, const float* alpha, const void* residual, int res_first,
-                             const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin = nullptr, int x3 = 0);
-
-// Called by msml_conv2d (conv_igemm.hip) when the fast-path conditions hold.  Returns false if
-// this kernel does not apply.
-bool msml_conv_ws_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out,
-                           int coutp, float* stats, int N, int H, int W, int P, int Q, int R, int S,
-                           int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
-                           const float* scale, const float* alpha, const void* residual, int res_first,
-                           const BnBwdFuse* bnb, int* bnb_rows);
-
-bool msml_conv_r32_dispatch(const void* in0, int c0p, const void* wp, int kop, int ktot, const float* bias, void* out,
-                            int coutp, float* stats, int stats_acc, int N, int H, int W, int P, int Q, int R, int S,
-                            int stride, int pad_h, int pad_w, int transposed, hipStream_t st, const float* scale,
-                            const float* alpha, const void* residual, const BnBwdFuse* bnb);
-
-bool msml_conv_pw_dispatch(const void* in0, int c0p, const void* wp, int kop, int ktot, const float* bias, void* out,
-                           int coutp, float* stats, int stats_acc, int N, int H, int W, int P, int Q, int R, int S,
-                           int stride, int pad_h, int pad_w, hipStream_t st, const float* scale, const float* alpha,
-                           const void* residual, int res_first, const BnBwdFuse* bnb);
-
-bool msml_conv_halo2_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out, int coutp,
-                              float* stats, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
-                              int pad_w, int transposed, hipStream_t st, const float* scale, const float* alpha,
-                              const void* residual, int res_first, const BnBwdFuse* bnb, int* bnb_rows, int x3 = 0);
-
-bool msml_conv_s2r_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out, int coutp,
-                            float* stats, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w,
-                            int transposed, hipStream_t st, const float* scale, const float* alpha, const void* residual,
-                            const BnBwdFuse* bnb, int* bnb_rows);
-
-bool msml_conv_s2r_x3_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out, int coutp, int N,
-                               int H, int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w, int transposed,
-                               hipStream_t st, const float* scale, const float* alpha, const void* residual, int res_first);
-
-bool msml_conv_fast_dispatch(const void* in0, int c0p, const void* in1, int c1p, const void* wp, int kop,
-                             const float* bias, void* out, int coutp, float* stats, int N, int H,
-                             int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w,
-                             int transposed, int in_dtype, int out_dtype, int bn, hipStream_t st,
-                             const float* scale, const float* alpha, const void* residual, int res_first,
-                             const BnBwdFuse* bnb, int* bnb_rows) {
+// Called by msml_conv2d and its variants (conv_igemm.hip) when the fast-path conditions hold.  Returns false if
+// no kernel of the fast path applies.  The families are tried in this order; the im2col kernel of this file is the last.
+bool msml_conv_fast_dispatch(const ConvCall& c) {
+  const void* const in0 = c.in0;
+  const void* const in1 = c.in1;
+  const void* const wp = c.wp;
+  const float* const bias = c.bias;
+  void* const out = c.out;
+  float* const stats = c.stats;
+  const float* const scale = c.scale;
+  const float* const alpha = c.alpha;
+  const void* const residual = c.residual;
+  const BnBwdFuse* const bnb = c.bnb;
+  int* const bnb_rows = c.bnb_rows;
+  hipStream_t st = c.st;
+  const int c0p = c.c0p, c1p = c.c1p, kop = c.kop, coutp = c.coutp, N = c.N, H = c.H, W = c.W, P = c.P, Q = c.Q, R = c.R, S = c.S;
+  const int stride = c.stride, pad_h = c.pad_h, pad_w = c.pad_w, transposed = c.transposed, res_first = c.res_first;
+  const int in_dtype = c.in_dtype, out_dtype = c.out_dtype, bn = msml_conv_tile_n(coutp);
   if (in_dtype != MSML_BF16) return false;
   const bool x3 = out_dtype == MSML_BF16X3;            // split-bf16 output planes (x3.hip)
   if (x3 && (bnb || stats)) return false;
@@ -615,58 +590,30 @@ bool msml_conv_fast_dispatch(const void* in0, int c0p, const void* in1, int c1p,
   if ((scale || alpha || residual) && out_dtype != MSML_BF16 && !x3) return false;
   if (c0p % 32 != 0 || (in1 && c1p % 32 != 0)) return false;
   // 32 -> 32 channel 3x3 layers (conv2 of the first FM stage's bottlenecks): conv_r32.hip
-  if (!in1 && out_dtype == MSML_BF16 &&
-      msml_conv_r32_dispatch(in0, c0p, wp, kop, R * S * c0p, bias, out, coutp, stats, stats ? msml_tl_stats_acc : 0, N, H,
-                             W, P, Q, R, S, stride, pad_h, pad_w, transposed, st, scale, alpha, residual, bnb)) {
+  if (!in1 && out_dtype == MSML_BF16 && msml_conv_r32_dispatch(c)) {
     if (bnb_rows) *bnb_rows = 1;
     return true;
   }
   // 1x1 / stride-1 layers (FM bottlenecks, im2col'd stems and their backward-data convs): conv_pw.hip
-  if (!in1 && out_dtype == MSML_BF16 &&
-      msml_conv_pw_dispatch(in0, c0p, wp, kop, R * S * c0p, bias, out, coutp, stats, stats ? msml_tl_stats_acc : 0, N, H,
-                            W, P, Q, R, S, stride, pad_h, pad_w, st, scale, alpha, residual, res_first, bnb)) {
+  if (!in1 && out_dtype == MSML_BF16 && msml_conv_pw_dispatch(c)) {
     if (bnb_rows) *bnb_rows = 1;
     return true;
   }
   // (64 -> 64 stride-1 forward / plain backward-data: the register-weights kernel first, conv_s2r.hip)
-  if (stride == 1 && !in1 && !bnb && out_dtype == MSML_BF16 &&
-      msml_conv_s2r_dispatch(in0, c0p, wp, kop, bias, out, coutp, stats, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed,
-                             st, scale, alpha, residual, bnb, bnb_rows))
-    return true;
-  if (!in1 && out_dtype == MSML_BF16 &&
-      msml_conv_ws_dispatch(in0, c0p, wp, kop, bias, out, coutp, stats, N, H, W, P, Q, R, S, stride, pad_h,
-                            pad_w, transposed, st, scale, alpha, residual, res_first, bnb, bnb_rows))
-    return true;
-  if (!in1 && out_dtype == MSML_BF16 &&
-      msml_conv_halo_dispatch(in0, c0p, wp, kop, bias, out, coutp, stats, N, H, W, P, Q, R, S, stride, pad_h,
-                              pad_w, transposed, st, scale, alpha, residual, res_first, bnb, bnb_rows))
-    return true;
+  if (stride == 1 && !in1 && !bnb && out_dtype == MSML_BF16 && msml_conv_s2r_dispatch(c)) return true;
+  if (!in1 && out_dtype == MSML_BF16 && msml_conv_ws_dispatch(c)) return true;
+  if (!in1 && out_dtype == MSML_BF16 && msml_conv_halo_dispatch(c)) return true;
   // stride-2 3x3 layers (forward through parity planes, backward-data per output class) and 7x7 maps (2 x 2 image
   // mosaics): conv_halo2.hip
-  if (!in1 && out_dtype == MSML_BF16 &&
-      msml_conv_halo2_dispatch(in0, c0p, wp, kop, bias, out, coutp, stats, N, H, W, P, Q, R, S, stride, pad_h, pad_w,
-                               transposed, st, scale, alpha, residual, res_first, bnb, bnb_rows))
-    return true;
+  if (!in1 && out_dtype == MSML_BF16 && msml_conv_halo2_dispatch(c)) return true;
   // 64 -> 64 channel stride-2 3x3 layers (weights in registers, persistent): conv_s2r.hip
-  if (!in1 && out_dtype == MSML_BF16 &&
-      msml_conv_s2r_dispatch(in0, c0p, wp, kop, bias, out, coutp, stats, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed,
-                             st, scale, alpha, residual, bnb, bnb_rows))
-    return true;
+  if (!in1 && out_dtype == MSML_BF16 && msml_conv_s2r_dispatch(c)) return true;
   // split-bf16 inference: the 64 -> 64 channel 3x3 / stride-1 layers with both weight planes in registers (conv_s2r.hip)
-  if (x3 && !in1 &&
-      msml_conv_s2r_x3_dispatch(in0, c0p, wp, kop, bias, out, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed, st,
-                                scale, alpha, residual, res_first))
-    return true;
+  if (x3 && !in1 && msml_conv_s2r_x3_dispatch(c)) return true;
   // split-bf16 inference: stride-2 layers and 7x7 / 4x4 maps (conv_halo2.hip)
-  if (x3 && !in1 &&
-      msml_conv_halo2_dispatch(in0, c0p, wp, kop, bias, out, coutp, nullptr, N, H, W, P, Q, R, S, stride, pad_h, pad_w,
-                               transposed, st, scale, alpha, residual, res_first, nullptr, nullptr, 1))
-    return true;
+  if (x3 && !in1 && msml_conv_halo2_dispatch(c)) return true;
   // split-bf16 inference: 3x3 / stride-1 layers of the 28x28 / 14x14 stages on the halo kernel (c0p is 3 x logical)
-  if (x3 && !in1 &&
-      msml_conv_halo_dispatch(in0, c0p, wp, kop, bias, out, coutp, stats, N, H, W, P, Q, R, S, stride, pad_h,
-                              pad_w, transposed, st, scale, alpha, residual, res_first, nullptr, nullptr, nullptr, 1))
-    return true;
+  if (x3 && !in1 && msml_conv_halo_dispatch(c)) return true;
   ConvFastArgs a;
   a.in[0] = (const unsigned short*)in0;
   a.in[1] = (const unsigned short*)in1;
@@ -688,9 +635,9 @@ bool msml_conv_fast_dispatch(const void* in0, int c0p, const void* in1, int c1p,
   a.stride_shift = stride == 1 ? 0 : (stride == 2 ? 1 : 2);
   a.pad_h = pad_h; a.pad_w = pad_w; a.transposed = transposed;
   a.wp = (const unsigned short*)wp; a.out = out; a.coutp = coutp; a.bias = bias; a.stats = stats;
-  a.stats_acc = stats ? msml_tl_stats_acc : 0;
+  a.stats_acc = stats ? c.stats_acc : 0;
   a.scale = scale; a.alpha = alpha; a.residual = (const unsigned short*)residual; a.res_first = res_first;
-  a.bias9 = (x3 && bias) ? msml_tl_bias9 : 0;
+  a.bias9 = (x3 && bias) ? c.bias9 : 0;
   a.bnb = BnBwdFuse{};
   if (bnb) a.bnb = *bnb;
   a.M = (long)N * P * Q;

@@ -24,6 +24,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "conv_call.h"
 #include "options.h"
 
 struct ConvHaloArgs {
@@ -940,60 +941,55 @@ static void launch_halo(ConvHaloArgs& a, hipStream_t st) {
   k_conv_halo<BN, NWM, FUSE, XF, X3, M16><<<grid, dim3(512), lds, st>>>(a);
 }
 
-static int halo_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 // Shapes of the persistent 128-channel tile (k_conv_halo_p): 128 output channels, 64 k input channels (ONE 64-channel slab
 // included: 64 -> 128 @ 56x56, conv1 of the first block of layer2, backbones/frb/iresnet.py:166-170 -- the nine-stage K loop
 // whose prologue and epilogue ruled the one-tile kernel out runs back to back there), at least two rounds of tiles.
 // MSML_HALO_PERSIST=0 / MSML_HALO_NO_ONE_SLAB=1: off / 128 input channels and more only.
-int msml_conv_halo_persist_shape(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
-                                 int pad_h, int pad_w) {
+int msml_conv_halo_persist_shape(const ConvShape& s) {
+  const int c0p = s.c0p, kop = s.kop, coutp = s.coutp, N = s.N, H = s.H, W = s.W;
   if (!msml_opt().halo_persist) return 0;
   if (msml_opt().no_halo_conv || msml_opt().halo_wide_only) return 0;   // (the halo conv's own
   // off-switches cover this 128-channel instantiation too)
-  if (R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || P != H || Q != W) return 0;
+  if (s.R != 3 || s.S != 3 || s.stride != 1 || s.pad_h != 1 || s.pad_w != 1 || s.P != H || s.Q != W) return 0;
   if (coutp != 128 || kop < coutp || c0p % 64 != 0 || c0p < 64) return 0;
   if (c0p == 64 && msml_opt().halo_no_one_slab) return 0;
   const long tiles = (long)N * cdiv(H, 14) * cdiv(W, 14);
-  if (tiles < 2L * halo_num_cus() || (long)N * H * W * 10 < tiles * 224 * 7) return 0;
+  if (tiles < 2L * msml_num_cus() || (long)N * H * W * 10 < tiles * 224 * 7) return 0;
   if ((long)N * H * W * c0p * 2 >= 0x70000000L || (long)N * H * W * 128 * 2 >= 0x70000000L || (long)kop * 9 * c0p * 2 >= 0x70000000L)
     return 0;
   return 1;
 }
 
 // Shape test shared by the dispatch and by msml_conv2d_kernel (the name query).
-bool msml_conv_halo_applies(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S,
-                            int stride, int pad_h, int pad_w, bool want_stats) {
+bool msml_conv_halo_applies(const ConvShape& s) {
+  const int c0p = s.c0p, kop = s.kop, coutp = s.coutp, N = s.N, H = s.H, W = s.W, P = s.P, Q = s.Q;
   const bool off = msml_opt().no_halo_conv;
   if (off) return false;
   const bool wide_only = msml_opt().halo_wide_only;    // A/B switch
   if (wide_only && coutp % 256 != 0) return false;
-  if (R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || P != H || Q != W) return false;
+  if (s.R != 3 || s.S != 3 || s.stride != 1 || s.pad_h != 1 || s.pad_w != 1 || P != H || Q != W) return false;
   if (c0p % 64 != 0 || c0p < 128 || coutp % 128 != 0 || kop < coutp) return false;   // (one 64-channel
   // slab = a 9-stage K loop: prologue and epilogue of the single resident workgroup dominate)
   const long tiles = (long)N * cdiv(H, 14) * cdiv(W, 14);
   if ((long)N * H * W * 10 < tiles * 224 * 7) return false;       // < 70 % real GEMM rows: im2col kernel wins
   const int srows = cdiv((long)N * P * Q, msml_conv_tile_m(coutp));
-  if (want_stats && tiles > srows) return false;        // (no batch-size threshold: the kernel choice, and
+  if (s.want_stats && tiles > srows) return false;      // (no batch-size threshold: the kernel choice, and
   // with it the summation order, must not depend on N -- results are batch-composition independent)
   const long in_bytes = (long)N * H * W * c0p * 2, w_bytes = (long)kop * 9 * c0p * 2;
   return in_bytes < 0x70000000L && w_bytes < 0x70000000L;
 }
 
 // Tried first by msml_conv_fast_dispatch; false = shape not covered here.
-bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out,
-                             int coutp, float* stats, int N, int H, int W, int P, int Q, int R, int S,
-                             int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
-                             const float* scale, const float* alpha, const void* residual, int res_first,
-                             const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin, int x3) {
+bool msml_conv_halo_dispatch(const ConvCall& c) {
+  const int c0p = c.c0p, kop = c.kop, coutp = c.coutp, N = c.N, H = c.H, W = c.W, transposed = c.transposed, x3 = c.x3;
+  const float* const bias = c.bias;
+  const float* const scale = c.scale;
+  const float* const alpha = c.alpha;
+  const void* const residual = c.residual;
+  float* const stats = c.stats;
+  const BnBwdFuse* const bnb = c.bnb;
+  const BnIn* const xin = c.xin;
+  hipStream_t st = c.st;
   // the 16x16x32 MFMA variant serves the plain forward / FUSE launches (round 4: +4...8 % on every shape, interleaved
   // A/B on one box, LDS conflicts 0.7 %).  MSML_HALO_M16=0 restores the 32x32x16 kernels, 1 limits
   // the variant to the 256-channel tile.
@@ -1001,10 +997,8 @@ bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, 
   const bool xfp = msml_opt().bnin_acc_persist;
   const bool pshape = m16 >= 2 && !x3 && !bias && !scale && !alpha && !residual &&
                       (!xin || (xfp && xin->acc && !transposed && !bnb && stats && c0p <= 1024)) &&
-                      (!stats || msml_tl_stats_acc) && (!bnb || bnb->acc) &&
-                      msml_conv_halo_persist_shape(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w) != 0;
-  if (!pshape && !msml_conv_halo_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, stats != nullptr))
-    return false;
+                      (!stats || c.stats_acc) && (!bnb || bnb->acc) && msml_conv_halo_persist_shape(c) != 0;
+  if (!pshape && !msml_conv_halo_applies(c)) return false;
   if (x3 && (bnb || xin || stats || transposed)) return false;
   if (bnb && (bias || scale || alpha || residual || stats)) return false;
   if (xin && (bnb || transposed || c0p > 1024)) return false;
@@ -1012,26 +1006,26 @@ bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, 
   a.tpy = cdiv(H, 14); a.tpx = cdiv(W, 14);
   const long tiles = (long)N * a.tpy * a.tpx;
   const long in_bytes = (long)N * H * W * c0p * 2, w_bytes = (long)kop * 9 * c0p * 2;
-  a.in = (const unsigned short*)in0; a.in_bytes = (unsigned int)in_bytes; a.C = c0p;
+  a.in = (const unsigned short*)c.in0; a.in_bytes = (unsigned int)in_bytes; a.C = c0p;
   a.N = N; a.H = H; a.W = W; a.flip = transposed;
-  a.wp = (const unsigned short*)wp; a.w_bytes = (unsigned int)w_bytes; a.Ktot = 9 * c0p;
-  a.out = (unsigned short*)out; a.coutp = coutp;
+  a.wp = (const unsigned short*)c.wp; a.w_bytes = (unsigned int)w_bytes; a.Ktot = 9 * c0p;
+  a.out = (unsigned short*)c.out; a.coutp = coutp;
   a.bias = bias; a.scale = scale; a.alpha = alpha; a.residual = (const unsigned short*)residual;
-  a.res_first = res_first; a.stats = stats;
-  a.bias9 = (x3 && bias) ? msml_tl_bias9 : 0;
-  if (msml_tl_bias9 && !x3) return false;
-  a.stats_rows = cdiv((long)N * P * Q, msml_conv_tile_m(coutp));
-  a.stats_acc = stats ? msml_tl_stats_acc : 0;
+  a.res_first = c.res_first; a.stats = stats;
+  a.bias9 = (x3 && bias) ? c.bias9 : 0;
+  if (c.bias9 && !x3) return false;
+  a.stats_rows = cdiv((long)N * c.P * c.Q, msml_conv_tile_m(coutp));
+  a.stats_acc = stats ? c.stats_acc : 0;
   a.bnb = BnBwdFuse{};
   if (bnb) a.bnb = *bnb;
   a.xin = BnIn{nullptr, nullptr, nullptr};
   if (xin) a.xin = *xin;
-  if (bnb_rows) *bnb_rows = (int)tiles;
+  if (c.bnb_rows) *c.bnb_rows = (int)tiles;
   const bool wide = coutp % 256 == 0;
   // 128-channel tile, several rounds of tiles per launch (128 -> 128 @ 28x28, 64 -> 128 @ 56x56): the persistent kernel
   if (pshape) {
     const size_t lds = 2 * (size_t)256 * 128 + 8 * 8192;
-    const int grid = halo_num_cus();
+    const int grid = msml_num_cus();
     const unsigned int out_bytes = (unsigned int)((long)N * H * W * 128 * 2);
     if (xin) {                           // BatchNorm + PReLU of the input formed in the prologue (accumulator mode)
       const size_t ldsx = lds + 3 * 1024 * sizeof(float);

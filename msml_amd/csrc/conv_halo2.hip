@@ -23,6 +23,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "conv_call.h"
 #include "options.h"
 
 struct ConvHalo2Args {
@@ -539,11 +540,12 @@ static void launch_halo2(ConvHalo2Args& a, hipStream_t st) {
 
 // geom: 0 stride 1, 1 stride-2 forward, 2 stride-2 backward-data.  Returns the tiling (0 none, 1 plain 14 x 14 tiles,
 // 2 mosaic of four 7 x 7 images, 3 mosaic of six 4 x 4 images) this family takes the shape with.
-int msml_conv_halo2_tiling(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
-                           int pad_h, int pad_w, int transposed, int x3) {
+int msml_conv_halo2_tiling(const ConvShape& s) {
+  const int c0p = s.c0p, kop = s.kop, coutp = s.coutp, N = s.N, H = s.H, W = s.W, P = s.P, Q = s.Q, stride = s.stride;
+  const int transposed = s.transposed, x3 = s.out_dtype == MSML_BF16X3;
   const bool off = msml_opt().no_halo2_conv;
   if (off) return 0;
-  if (R != 3 || S != 3 || pad_h != 1 || pad_w != 1) return 0;
+  if (s.R != 3 || s.S != 3 || s.pad_h != 1 || s.pad_w != 1) return 0;
   if (c0p % 64 != 0 || c0p < 128 || coutp % 128 != 0 || kop < coutp) return 0;
   int gh, gw;                                           // the GEMM grid
   if (stride == 1) { if (P != H || Q != W) return 0; gh = H; gw = W; }
@@ -571,43 +573,49 @@ int msml_conv_halo2_tiling(int c0p, int kop, int coutp, int N, int H, int W, int
 }
 
 // Tried by msml_conv_fast_dispatch before the im2col kernel; false = shape / epilogue not covered here.
-bool msml_conv_halo2_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out, int coutp,
-                              float* stats, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
-                              int pad_w, int transposed, hipStream_t st, const float* scale, const float* alpha,
-                              const void* residual, int res_first, const BnBwdFuse* bnb, int* bnb_rows, int x3) {
-  const int tiling = msml_conv_halo2_tiling(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed, x3);
+bool msml_conv_halo2_dispatch(const ConvCall& c) {
+  const int c0p = c.c0p, coutp = c.coutp, N = c.N, H = c.H, W = c.W, P = c.P, Q = c.Q, stride = c.stride;
+  const int transposed = c.transposed, res_first = c.res_first, x3 = c.x3;
+  const float* const bias = c.bias;
+  const float* const scale = c.scale;
+  const float* const alpha = c.alpha;
+  const void* const residual = c.residual;
+  float* const stats = c.stats;
+  const BnBwdFuse* const bnb = c.bnb;
+  hipStream_t st = c.st;
+  const int tiling = msml_conv_halo2_tiling(c);
   if (!tiling) return false;
   // split-bf16 inference (c0p = 3 x the logical channels): forward launches, no statistics; MSML_NO_HALO2_X3=1 (read per
   // call) leaves them on the im2col kernel
   if (x3 && (transposed || bnb || stats || msml_opt().no_halo2_x3)) return false;
   if (x3 && (long)N * P * Q * coutp * 6 >= 0x7fffffffL * 2) return false;
-  if (msml_tl_bias9 && !(x3 && stride == 1)) return false;
+  if (c.bias9 && !(x3 && stride == 1)) return false;
   if (!x3 && (alpha || res_first)) return false;
   if (bnb && (bias || scale)) return false;
-  if (stats && !msml_tl_stats_acc) return false;
+  if (stats && !c.stats_acc) return false;
   if (bnb && (!bnb->acc || residual || stats)) return false;
   if (residual && stats) return false;
   const int geom = stride == 1 ? 0 : (transposed ? 2 : 1);
   ConvHalo2Args a;
-  a.in = (const unsigned short*)in0; a.in_bytes = (unsigned int)((long)N * H * W * c0p * 2); a.C = c0p;
+  a.in = (const unsigned short*)c.in0; a.in_bytes = (unsigned int)((long)N * H * W * c0p * 2); a.C = c0p;
   a.N = N; a.IH = H; a.IW = W;
   a.GH = geom == 1 ? P : H; a.GW = geom == 1 ? Q : W;
   a.OH = P; a.OW = Q;
   a.tpy = cdiv(a.GH, 14); a.tpx = cdiv(a.GW, 14);
   a.flip = transposed;
-  a.wp = (const unsigned short*)wp; a.w_bytes = (unsigned int)((long)kop * 9 * c0p * 2); a.Ktot = 9 * c0p;
-  a.out = (unsigned short*)out; a.coutp = coutp;
+  a.wp = (const unsigned short*)c.wp; a.w_bytes = (unsigned int)((long)c.kop * 9 * c0p * 2); a.Ktot = 9 * c0p;
+  a.out = (unsigned short*)c.out; a.coutp = coutp;
   a.bias = bias; a.scale = scale;
   a.residual = (const unsigned short*)residual;
   a.stats = stats;
   a.bnb = BnBwdFuse{};
   if (bnb) a.bnb = *bnb;
-  a.alpha = alpha; a.res_first = res_first; a.bias9 = (x3 && bias) ? msml_tl_bias9 : 0;
+  a.alpha = alpha; a.res_first = res_first; a.bias9 = (x3 && bias) ? c.bias9 : 0;
   a.zrev = 1;        // (tools/bench_small.py, three interleaved pairs: 256 @ 28 -> 56 79.4 / 79.0 / 78.2 -> 76.7 / 77.7 / 77.9 us,
                      //  128 @ 28 32.0 -> 31.3, the other shapes inside the noise; outputs bit-identical)
   const bool mos = tiling >= 2;
   const bool wide = coutp % 256 == 0 && !mos;           // mosaic: N / 4 tiles -- 128-channel tiles fill the chip sooner
-  if (bnb_rows) *bnb_rows = (mos ? cdiv(N, tiling == 3 ? 6 : 4) : N * a.tpy * a.tpx) * (geom == 2 ? 4 : 1);
+  if (c.bnb_rows) *c.bnb_rows = (mos ? cdiv(N, tiling == 3 ? 6 : 4) : N * a.tpy * a.tpx) * (geom == 2 ? 4 : 1);
 #define H2_CASE(GEOM, MOS)                                                              \
   if (bnb) { if (wide) launch_halo2<256, 1, GEOM, MOS, true>(a, st); else launch_halo2<128, 2, GEOM, MOS, true>(a, st); } \
   else { if (wide) launch_halo2<256, 1, GEOM, MOS, false>(a, st); else launch_halo2<128, 2, GEOM, MOS, false>(a, st); }

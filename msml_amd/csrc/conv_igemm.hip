@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "conv_call.h"
 #include "options.h"
 
 struct ConvArgs {
@@ -350,88 +351,87 @@ static int launch(const ConvArgs& a, hipStream_t stream) {
   return 0;
 }
 
-bool msml_conv_fast_dispatch(const void* in0, int c0p, const void* in1, int c1p, const void* wp, int kop,
-                             const float* bias, void* out, int coutp, float* stats, int N, int H,
-                             int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w,
-                             int transposed, int in_dtype, int out_dtype, int bn, hipStream_t st,
-                             const float* scale, const float* alpha, const void* residual, int res_first,
-                             const BnBwdFuse* bnb, int* bnb_rows);
-
-bool msml_conv_line_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
-                            int pad_w);
-bool msml_conv_line_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out, int coutp,
-                             int N, int H, int W, int R, int S, int transposed, hipStream_t st,
-                             const float* scale = nullptr, const void* residual = nullptr);
-
-bool msml_deconv4_applies(int c0p, int c1p, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
-                          int pad_h, int pad_w, int transposed);
-bool msml_deconv4_dispatch(const void* in0, const void* in1, const void* wp, int kop, const float* bias, void* out, int N,
-                           int H, hipStream_t st);
-
-thread_local int msml_tl_stats_acc = 0;
-thread_local int msml_tl_bias9 = 0;
-
 extern "C" int msml_conv_tile_m(int coutp) { return coutp <= 64 ? 256 : 128; }
 extern "C" int msml_conv_tile_n(int coutp) { return coutp <= 32 ? 32 : (coutp <= 64 ? 64 : 128); }
 
-extern "C" int msml_conv2d(const void* in0, int c0p, const void* in1, int c1p, const void* wp,
-                           int kop, const float* bias, void* out, int coutp, float* stats,
-                           int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
-                           int pad_w, int transposed, int in_dtype, int out_dtype, void* stream) {
-  MSML_CHECK(in0 && wp && out, MSML_ERR_SHAPE, "conv2d: null pointer");
+// Operands, shape and stream of a call as the C entry points receive them; epilogue and mode fields are the caller's.
+static ConvCall conv_call(const void* in0, int c0p, const void* in1, int c1p, const void* wp, int kop, void* out, int coutp,
+                          int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w, int transposed,
+                          void* stream) {
+  ConvCall c;
+  c.in0 = in0; c.c0p = c0p; c.in1 = in1; c.c1p = c1p; c.wp = wp; c.kop = kop; c.out = out; c.coutp = coutp;
+  c.N = N; c.H = H; c.W = W; c.P = P; c.Q = Q; c.R = R; c.S = S;
+  c.stride = stride; c.pad_h = pad_h; c.pad_w = pad_w; c.transposed = transposed;
+  c.st = (hipStream_t)stream;
+  return c;
+}
+static void set_stats(ConvCall& c, float* stats, int acc) {
+  c.stats = stats; c.want_stats = stats != nullptr; c.stats_acc = acc;
+}
+// The shape alone, for the queries: kop = the rows a packed weight of coutp channels has at least.
+static ConvShape conv_shape(int c0p, int c1p, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
+                            int pad_h, int pad_w, int transposed, int want_stats) {
+  ConvShape s = conv_call(nullptr, c0p, nullptr, c1p, nullptr, 0, nullptr, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w,
+                          transposed, nullptr);
+  const int bn = msml_conv_tile_n(coutp);
+  s.kop = cdiv(coutp, bn) * bn;
+  s.want_stats = want_stats;
+  return s;
+}
+
+// msml_conv2d and msml_conv2d_acc: c.stats in the row format or, with c.stats_acc, an accumulator
+static int conv2d(const ConvCall& c) {
+  const int coutp = c.coutp, N = c.N, H = c.H, W = c.W, P = c.P, Q = c.Q, R = c.R, S = c.S, stride = c.stride;
+  const int in_dtype = c.in_dtype, out_dtype = c.out_dtype;
+  MSML_CHECK(c.in0 && c.wp && c.out, MSML_ERR_SHAPE, "conv2d: null pointer");
   MSML_CHECK(N > 0 && H > 0 && W > 0 && P > 0 && Q > 0 && R > 0 && S > 0, MSML_ERR_SHAPE,
              "conv2d: bad dims N=%d H=%d W=%d P=%d Q=%d R=%d S=%d", N, H, W, P, Q, R, S);
-  MSML_CHECK(c0p > 0 && c0p % 8 == 0 && c1p >= 0 && c1p % 8 == 0 && coutp > 0 && coutp % 8 == 0,
+  MSML_CHECK(c.c0p > 0 && c.c0p % 8 == 0 && c.c1p >= 0 && c.c1p % 8 == 0 && coutp > 0 && coutp % 8 == 0,
              MSML_ERR_SHAPE, "conv2d: channel counts must be multiples of 8 (c0p=%d c1p=%d coutp=%d)",
-             c0p, c1p, coutp);
+             c.c0p, c.c1p, coutp);
   MSML_CHECK(stride == 1 || stride == 2 || stride == 4, MSML_ERR_UNSUPPORTED,
              "conv2d: stride %d (power of two <= 4 only)", stride);
-  MSML_CHECK((c1p == 0) == (in1 == nullptr), MSML_ERR_SHAPE, "conv2d: in1/c1p mismatch");
-  if (!transposed) {
-    MSML_CHECK((H + 2 * pad_h - R) / stride + 1 == P && (W + 2 * pad_w - S) / stride + 1 == Q,
+  MSML_CHECK((c.c1p == 0) == (c.in1 == nullptr), MSML_ERR_SHAPE, "conv2d: in1/c1p mismatch");
+  if (!c.transposed) {
+    MSML_CHECK((H + 2 * c.pad_h - R) / stride + 1 == P && (W + 2 * c.pad_w - S) / stride + 1 == Q,
                MSML_ERR_SHAPE, "conv2d: P,Q inconsistent with H,W,R,S,stride,pad");
   } else {
-    MSML_CHECK((H - 1) * stride - 2 * pad_h + R <= P + stride - 1 && (H - 1) * stride - 2 * pad_h + R >= P - (stride - 1) &&
-                   (W - 1) * stride - 2 * pad_w + S <= Q + stride - 1 && (W - 1) * stride - 2 * pad_w + S >= Q - (stride - 1),
+    MSML_CHECK((H - 1) * stride - 2 * c.pad_h + R <= P + stride - 1 && (H - 1) * stride - 2 * c.pad_h + R >= P - (stride - 1) &&
+                   (W - 1) * stride - 2 * c.pad_w + S <= Q + stride - 1 && (W - 1) * stride - 2 * c.pad_w + S >= Q - (stride - 1),
                MSML_ERR_SHAPE, "conv2d(transposed): P,Q inconsistent with H,W,R,S,stride,pad");
   }
   ConvArgs a;
-  a.in[0] = in0; a.in[1] = in1;
-  a.cp[0] = c0p; a.cp[1] = c1p;
-  a.nseg = in1 ? 2 : 1;
-  a.ksteps[0] = (R * S * c0p + 31) / 32;
-  a.ksteps[1] = in1 ? (R * S * c1p + 31) / 32 : 0;
+  a.in[0] = c.in0; a.in[1] = c.in1;
+  a.cp[0] = c.c0p; a.cp[1] = c.c1p;
+  a.nseg = c.in1 ? 2 : 1;
+  a.ksteps[0] = (R * S * c.c0p + 31) / 32;
+  a.ksteps[1] = c.in1 ? (R * S * c.c1p + 31) / 32 : 0;
   a.Ktot = 32 * (a.ksteps[0] + a.ksteps[1]);
   a.N = N; a.H = H; a.W = W; a.P = P; a.Q = Q; a.R = R; a.S = S;
   a.stride = stride;
   a.stride_shift = stride == 1 ? 0 : (stride == 2 ? 1 : 2);
-  a.pad_h = pad_h; a.pad_w = pad_w; a.transposed = transposed;
-  a.wp = wp; a.out = out; a.coutp = coutp; a.bias = bias; a.stats = stats;
-  a.stats_acc = stats ? msml_tl_stats_acc : 0;
+  a.pad_h = c.pad_h; a.pad_w = c.pad_w; a.transposed = c.transposed;
+  a.wp = c.wp; a.out = c.out; a.coutp = coutp; a.bias = c.bias; a.stats = c.stats;
+  a.stats_acc = c.stats ? c.stats_acc : 0;
   a.residual = nullptr; a.sel = nullptr;
   a.M = (long)N * P * Q;
   const int bn = msml_conv_tile_n(coutp);
-  MSML_CHECK(kop >= cdiv(coutp, bn) * bn, MSML_ERR_SHAPE,
-             "conv2d: packed weight has %d rows, need %d", kop, cdiv(coutp, bn) * bn);
-  hipStream_t st = (hipStream_t)stream;
+  MSML_CHECK(c.kop >= cdiv(coutp, bn) * bn, MSML_ERR_SHAPE,
+             "conv2d: packed weight has %d rows, need %d", c.kop, cdiv(coutp, bn) * bn);
+  hipStream_t st = c.st;
   // 7x1 / 1x7 line convs of the OSB's Global-Convolution modules (and their backward-data convs): conv_line.hip
-  if (in_dtype == MSML_BF16 && out_dtype == MSML_BF16 && !in1 && !stats && !msml_opt().no_fast_conv &&
-      msml_conv_line_applies(c0p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w) &&
-      msml_conv_line_dispatch(in0, c0p, wp, kop, bias, out, coutp, N, H, W, R, S, transposed, st)) {
+  if (in_dtype == MSML_BF16 && out_dtype == MSML_BF16 && !c.in1 && !c.stats && !msml_opt().no_fast_conv &&
+      msml_conv_line_applies(c) && msml_conv_line_dispatch(c)) {
     MSML_LAUNCH_OK("conv2d(line)");
     return MSML_OK;
   }
   // 4x4 / stride-2 transposed convs of the OSB decoder on cat(seg, gcm): conv_d4.hip
-  if (in_dtype == MSML_BF16 && out_dtype == MSML_BF16 && in1 && !stats && !msml_opt().no_fast_conv &&
-      msml_deconv4_applies(c0p, c1p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed) &&
-      msml_deconv4_dispatch(in0, in1, wp, kop, bias, out, N, H, st)) {
+  if (in_dtype == MSML_BF16 && out_dtype == MSML_BF16 && c.in1 && !c.stats && !msml_opt().no_fast_conv &&
+      msml_deconv4_applies(c) && msml_deconv4_dispatch(c)) {
     MSML_LAUNCH_OK("conv2d(deconv4)");
     return MSML_OK;
   }
-  if ((out_dtype == MSML_BF16 || out_dtype == MSML_F32) && !msml_opt().no_fast_conv &&
-      msml_conv_fast_dispatch(in0, c0p, in1, c1p, wp, kop, bias, out, coutp, stats, N, H, W, P, Q, R,
-                              S, stride, pad_h, pad_w, transposed, in_dtype, out_dtype, bn, st, nullptr, nullptr,
-                              nullptr, 0, nullptr, nullptr)) {
+  if ((out_dtype == MSML_BF16 || out_dtype == MSML_F32) && !msml_opt().no_fast_conv && msml_conv_fast_dispatch(c)) {
     MSML_LAUNCH_OK("conv2d(fast)");
     return MSML_OK;
   }
@@ -451,6 +451,16 @@ extern "C" int msml_conv2d(const void* in0, int c0p, const void* in1, int c1p, c
   return MSML_OK;
 }
 
+extern "C" int msml_conv2d(const void* in0, int c0p, const void* in1, int c1p, const void* wp,
+                           int kop, const float* bias, void* out, int coutp, float* stats,
+                           int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
+                           int pad_w, int transposed, int in_dtype, int out_dtype, void* stream) {
+  ConvCall c = conv_call(in0, c0p, in1, c1p, wp, kop, out, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed, stream);
+  c.bias = bias; c.in_dtype = in_dtype; c.out_dtype = out_dtype;
+  set_stats(c, stats, 0);
+  return conv2d(c);
+}
+
 
 // msml_conv2d whose per-channel (sum, sumsq) of the output go to an ACCUMULATOR (common.h): acc is a zero-initialised
 // double[MSML_ACC_ROWS][2][coutp]; consumed by msml_bn_fin_act_fwd without a finalize launch in between.
@@ -459,11 +469,10 @@ extern "C" int msml_conv2d_acc(const void* in0, int c0p, const void* in1, int c1
                                int Q, int R, int S, int stride, int pad_h, int pad_w, int transposed, int in_dtype,
                                int out_dtype, void* stream) {
   MSML_CHECK(acc, MSML_ERR_SHAPE, "conv2d_acc: null accumulator");
-  msml_tl_stats_acc = 1;
-  const int rc = msml_conv2d(in0, c0p, in1, c1p, wp, kop, bias, out, coutp, reinterpret_cast<float*>(acc), N, H, W, P, Q,
-                             R, S, stride, pad_h, pad_w, transposed, in_dtype, out_dtype, stream);
-  msml_tl_stats_acc = 0;
-  return rc;
+  ConvCall c = conv_call(in0, c0p, in1, c1p, wp, kop, out, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed, stream);
+  c.bias = bias; c.in_dtype = in_dtype; c.out_dtype = out_dtype;
+  set_stats(c, reinterpret_cast<float*>(acc), 1);
+  return conv2d(c);
 }
 
 
@@ -478,19 +487,16 @@ extern "C" int msml_conv2d_fused(const void* in0, int c0p, const void* in1, int 
   MSML_CHECK(c0p % 32 == 0 && c1p % 32 == 0 && coutp % 8 == 0, MSML_ERR_SHAPE, "conv2d_fused: channel padding");
   const int bn = msml_conv_tile_n(coutp);
   MSML_CHECK(kop >= cdiv(coutp, bn) * bn, MSML_ERR_SHAPE, "conv2d_fused: packed weight rows");
+  ConvCall c = conv_call(in0, c0p, in1, c1p, wp, kop, out, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed, stream);
+  c.bias = shift; c.scale = scale; c.alpha = alpha; c.residual = residual; c.res_first = res_first;
   // 7x1 / 1x7 line convs (the OSB's Global-Convolution modules: the backward-data conv of conv_l1 takes conv_r1's input
   // gradient as its residual, functional.py _ConvTee): conv_line.hip with scale / shift / residual in its epilogue
-  if (!in1 && !alpha && !(residual && res_first) && !msml_opt().no_fast_conv &&
-      msml_conv_line_applies(c0p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w) &&
-      msml_conv_line_dispatch(in0, c0p, wp, kop, shift, out, coutp, N, H, W, R, S, transposed, (hipStream_t)stream, scale,
-                              residual)) {
+  if (!in1 && !alpha && !(residual && res_first) && !msml_opt().no_fast_conv && msml_conv_line_applies(c) &&
+      msml_conv_line_dispatch(c)) {
     MSML_LAUNCH_OK("conv2d_fused(line)");
     return MSML_OK;
   }
-  MSML_CHECK(msml_conv_fast_dispatch(in0, c0p, in1, c1p, wp, kop, shift, out, coutp, nullptr, N, H, W, P, Q,
-                                     R, S, stride, pad_h, pad_w, transposed, MSML_BF16, MSML_BF16, bn,
-                                     (hipStream_t)stream, scale, alpha, residual, res_first, nullptr, nullptr),
-             MSML_ERR_UNSUPPORTED, "conv2d_fused: shape not supported by the fast kernel");
+  MSML_CHECK(msml_conv_fast_dispatch(c), MSML_ERR_UNSUPPORTED, "conv2d_fused: shape not supported by the fast kernel");
   MSML_LAUNCH_OK("conv2d_fused");
   return MSML_OK;
 }
@@ -507,10 +513,11 @@ extern "C" int msml_conv2d_x3(const void* in0, int c0p, const void* in1, int c1p
              "conv2d_x3: channel padding c0p=%d c1p=%d coutp=%d", c0p, c1p, coutp);
   const int bn = msml_conv_tile_n(coutp);
   MSML_CHECK(kop >= cdiv(coutp, bn) * bn, MSML_ERR_SHAPE, "conv2d_x3: packed weight rows");
-  MSML_CHECK(msml_conv_fast_dispatch(in0, 3 * c0p, in1, 3 * c1p, wp, kop, shift, out, coutp, nullptr, N, H, W, P, Q,
-                                     R, S, stride, pad_h, pad_w, transposed, MSML_BF16, MSML_BF16X3, bn,
-                                     (hipStream_t)stream, scale, alpha, residual, res_first, nullptr, nullptr),
-             MSML_ERR_UNSUPPORTED, "conv2d_x3: shape not supported by the fast kernel");
+  ConvCall c = conv_call(in0, 3 * c0p, in1, 3 * c1p, wp, kop, out, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w,
+                         transposed, stream);
+  c.bias = shift; c.scale = scale; c.alpha = alpha; c.residual = residual; c.res_first = res_first;
+  c.out_dtype = MSML_BF16X3; c.x3 = 1;
+  MSML_CHECK(msml_conv_fast_dispatch(c), MSML_ERR_UNSUPPORTED, "conv2d_x3: shape not supported by the fast kernel");
   MSML_LAUNCH_OK("conv2d_x3");
   return MSML_OK;
 }
@@ -529,12 +536,10 @@ extern "C" int msml_conv2d_x3_border(const void* in0, int c0p, const void* wp, i
              "conv2d_x3_border: c0p=%d coutp=%d H=%d W=%d", c0p, coutp, H, W);
   const int bn = msml_conv_tile_n(coutp);
   MSML_CHECK(kop >= cdiv(coutp, bn) * bn, MSML_ERR_SHAPE, "conv2d_x3_border: packed weight rows");
-  msml_tl_bias9 = 1;
-  const bool ok = msml_conv_fast_dispatch(in0, 3 * c0p, nullptr, 0, wp, kop, shift9, out, coutp, nullptr, N, H, W, H, W, 3, 3, 1,
-                                          1, 1, 0, MSML_BF16, MSML_BF16X3, bn, (hipStream_t)stream, scale, alpha, residual,
-                                          res_first, nullptr, nullptr);
-  msml_tl_bias9 = 0;
-  MSML_CHECK(ok, MSML_ERR_UNSUPPORTED, "conv2d_x3_border: shape not supported by the fast kernel");
+  ConvCall c = conv_call(in0, 3 * c0p, nullptr, 0, wp, kop, out, coutp, N, H, W, H, W, 3, 3, 1, 1, 1, 0, stream);
+  c.bias = shift9; c.scale = scale; c.alpha = alpha; c.residual = residual; c.res_first = res_first;
+  c.out_dtype = MSML_BF16X3; c.x3 = 1; c.bias9 = 1;
+  MSML_CHECK(msml_conv_fast_dispatch(c), MSML_ERR_UNSUPPORTED, "conv2d_x3_border: shape not supported by the fast kernel");
   MSML_LAUNCH_OK("conv2d_x3_border");
   return MSML_OK;
 }
@@ -548,26 +553,30 @@ extern "C" int msml_conv2d_bnbwd_rows(int coutp, int N, int P, int Q) {
   return 4 * (cdiv(m, 128) + 4);
 }
 
+// msml_conv2d_bnbwd and msml_conv2d_bnbwd_acc: f.partial in the row format or, with f.acc, an accumulator
+static int conv2d_bnbwd(ConvCall& c, const BnBwdFuse& f, int rows_cap, int* rows_used) {
+  MSML_CHECK(c.in0 && c.wp && c.out && f.x && f.scale && f.shift && f.mean && f.invstd && f.partial && rows_used,
+             MSML_ERR_SHAPE, "conv2d_bnbwd: null pointer");
+  MSML_CHECK(c.c0p % 32 == 0 && c.coutp % 8 == 0, MSML_ERR_SHAPE, "conv2d_bnbwd: channel padding");
+  MSML_CHECK(rows_cap >= msml_conv2d_bnbwd_rows(c.coutp, c.N, c.P, c.Q), MSML_ERR_WORKSPACE,
+             "conv2d_bnbwd: partial buffer has %d rows, need %d", rows_cap, msml_conv2d_bnbwd_rows(c.coutp, c.N, c.P, c.Q));
+  const int bn = msml_conv_tile_n(c.coutp);
+  MSML_CHECK(c.kop >= cdiv(c.coutp, bn) * bn, MSML_ERR_SHAPE, "conv2d_bnbwd: packed weight rows");
+  c.bnb = &f; c.bnb_rows = rows_used; c.stats_acc = f.acc;
+  MSML_CHECK(msml_conv_fast_dispatch(c), MSML_ERR_UNSUPPORTED, "conv2d_bnbwd: shape not supported by the fast kernel");
+  MSML_LAUNCH_OK("conv2d_bnbwd");
+  return MSML_OK;
+}
+
 extern "C" int msml_conv2d_bnbwd(const void* in0, int c0p, const void* wp, int kop, void* out, int coutp,
                                  int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
                                  int pad_w, int transposed, const void* bn_x, const float* bn_scale,
                                  const float* bn_shift, const float* bn_alpha, const float* bn_mean,
                                  const float* bn_invstd, float* partial, int rows_cap, int* rows_used,
                                  void* stream) {
-  MSML_CHECK(in0 && wp && out && bn_x && bn_scale && bn_shift && bn_mean && bn_invstd && partial && rows_used,
-             MSML_ERR_SHAPE, "conv2d_bnbwd: null pointer");
-  MSML_CHECK(c0p % 32 == 0 && coutp % 8 == 0, MSML_ERR_SHAPE, "conv2d_bnbwd: channel padding");
-  MSML_CHECK(rows_cap >= msml_conv2d_bnbwd_rows(coutp, N, P, Q), MSML_ERR_WORKSPACE,
-             "conv2d_bnbwd: partial buffer has %d rows, need %d", rows_cap, msml_conv2d_bnbwd_rows(coutp, N, P, Q));
-  const int bn = msml_conv_tile_n(coutp);
-  MSML_CHECK(kop >= cdiv(coutp, bn) * bn, MSML_ERR_SHAPE, "conv2d_bnbwd: packed weight rows");
-  BnBwdFuse f{(const unsigned short*)bn_x, bn_scale, bn_shift, bn_alpha, bn_mean, bn_invstd, partial, msml_tl_stats_acc};
-  MSML_CHECK(msml_conv_fast_dispatch(in0, c0p, nullptr, 0, wp, kop, nullptr, out, coutp, nullptr, N, H, W, P, Q,
-                                     R, S, stride, pad_h, pad_w, transposed, MSML_BF16, MSML_BF16, bn,
-                                     (hipStream_t)stream, nullptr, nullptr, nullptr, 0, &f, rows_used),
-             MSML_ERR_UNSUPPORTED, "conv2d_bnbwd: shape not supported by the fast kernel");
-  MSML_LAUNCH_OK("conv2d_bnbwd");
-  return MSML_OK;
+  ConvCall c = conv_call(in0, c0p, nullptr, 0, wp, kop, out, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed, stream);
+  const BnBwdFuse f{(const unsigned short*)bn_x, bn_scale, bn_shift, bn_alpha, bn_mean, bn_invstd, partial, 0};
+  return conv2d_bnbwd(c, f, rows_cap, rows_used);
 }
 
 // msml_conv2d_bnbwd with the three backward sums added into an accumulator (zero-initialised double[8][3][coutp])
@@ -579,41 +588,20 @@ extern "C" int msml_conv2d_bnbwd_acc(const void* in0, int c0p, const void* wp, i
                                      void* stream) {
   MSML_CHECK(acc, MSML_ERR_SHAPE, "conv2d_bnbwd_acc: null accumulator");
   int used = 0;
-  msml_tl_stats_acc = 1;
-  const int rc = msml_conv2d_bnbwd(in0, c0p, wp, kop, out, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed,
-                                   bn_x, bn_scale, bn_shift, bn_alpha, bn_mean, bn_invstd, reinterpret_cast<float*>(acc),
-                                   1 << 30, &used, stream);
-  msml_tl_stats_acc = 0;
-  return rc;
+  ConvCall c = conv_call(in0, c0p, nullptr, 0, wp, kop, out, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed, stream);
+  const BnBwdFuse f{(const unsigned short*)bn_x, bn_scale, bn_shift, bn_alpha, bn_mean, bn_invstd, reinterpret_cast<float*>(acc), 1};
+  return conv2d_bnbwd(c, f, 1 << 30, &used);
 }
-
-int msml_conv_halo2_tiling(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
-                           int pad_h, int pad_w, int transposed, int x3);
-int msml_conv_s2r_applies(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
-                          int pad_w, int transposed);
-int msml_conv_halo_persist_shape(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride,
-                                 int pad_h, int pad_w);
-bool msml_conv_halo_applies(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S,
-                            int stride, int pad_h, int pad_w, bool want_stats);
-bool msml_conv_ws_applies(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S,
-                          int stride, int pad_h, int pad_w, bool want_stats);
 
 // Forward conv whose input is X = PReLU(in0 * in_scale + in_shift) -- a training-mode BatchNorm
 // (+PReLU) in front of the conv -- applied to the halo image while it sits in LDS, so X is never
 // written to HBM (zero padding applies to X, as in the unfused graph).  Only the shapes of the
 // halo-tile kernels (conv_halo.hip): 3x3 / stride 1 / pad 1, see
 // msml_conv2d_bnin_applies; MSML_ERR_UNSUPPORTED otherwise.  stats as in msml_conv2d.
-bool msml_conv_halo_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out,
-                             int coutp, float* stats, int N, int H, int W, int P, int Q, int R, int S,
-                             int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
-                             const float* scale, const float* alpha, const void* residual, int res_first,
-                             const BnBwdFuse* bnb, int* bnb_rows, const BnIn* xin, int x3 = 0);
-
 extern "C" int msml_conv2d_bnin_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S,
                                         int stride, int pad_h, int pad_w, int want_stats) {
   if (msml_opt().no_fast_conv || c0p > 1024 || (long)N * P * Q >= (1L << 24)) return 0;
-  const int bn = msml_conv_tile_n(coutp), kop = cdiv(coutp, bn) * bn;
-  return msml_conv_halo_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, want_stats != 0) ? 1 : 0;
+  return msml_conv_halo_applies(conv_shape(c0p, 0, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, 0, want_stats != 0)) ? 1 : 0;
 }
 
 extern "C" int msml_conv2d_bnin(const void* in0, int c0p, const float* in_scale, const float* in_shift,
@@ -628,10 +616,10 @@ extern "C" int msml_conv2d_bnin(const void* in0, int c0p, const float* in_scale,
   MSML_CHECK(msml_conv2d_bnin_applies(c0p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, stats != nullptr),
              MSML_ERR_UNSUPPORTED, "conv2d_bnin: shape not covered by the halo-tile kernels");
   const BnIn xin{in_scale, in_shift, in_alpha};
-  hipStream_t st = (hipStream_t)stream;
-  const bool ok = msml_conv_halo_dispatch(in0, c0p, wp, kop, nullptr, out, coutp, stats, N, H, W, P, Q, R, S, stride,
-                                          pad_h, pad_w, 0, st, nullptr, nullptr, nullptr, 0, nullptr, nullptr, &xin);
-  MSML_CHECK(ok, MSML_ERR_UNSUPPORTED, "conv2d_bnin: launch refused");
+  ConvCall c = conv_call(in0, c0p, nullptr, 0, wp, kop, out, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, 0, stream);
+  c.xin = &xin;
+  set_stats(c, stats, 0);
+  MSML_CHECK(msml_conv_halo_dispatch(c), MSML_ERR_UNSUPPORTED, "conv2d_bnin: launch refused");
   MSML_LAUNCH_OK("conv2d_bnin");
   return MSML_OK;
 }
@@ -640,13 +628,11 @@ extern "C" int msml_conv2d_bnin(const void* in0, int c0p, const float* in_scale,
 extern "C" int msml_conv2d_bnin_acc_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S,
                                             int stride, int pad_h, int pad_w) {
   if (msml_opt().no_fast_conv || c0p > 1024 || c0p % 8 || 256 % (c0p / 8) || (long)N * P * Q >= (1L << 24)) return 0;
-  const int bn = msml_conv_tile_n(coutp), kop = cdiv(coutp, bn) * bn;
+  const ConvShape s = conv_shape(c0p, 0, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, 0, 1);
   // 3: the persistent 128-channel tile takes the launch (round 6: its prologue transform pays from 64 input channels on --
   // the one-slab shape 64 -> 128 @ 56x56, conv1 of a stage's first block, has no one-round kernel to fall back to)
-  if (msml_opt().bnin_acc_persist && msml_opt().halo_m16 >= 2 &&
-      msml_conv_halo_persist_shape(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w))
-    return 3;
-  return msml_conv_halo_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, true) ? 1 : 0;
+  if (msml_opt().bnin_acc_persist && msml_opt().halo_m16 >= 2 && msml_conv_halo_persist_shape(s)) return 3;
+  return msml_conv_halo_applies(s) ? 1 : 0;
 }
 
 // Training-mode BatchNorm (+ PReLU) -> 3x3 / stride-1 / pad-1 conv in ONE launch, accumulator-mode statistics on both
@@ -673,12 +659,10 @@ extern "C" int msml_conv2d_bnin_acc(const void* in0, int c0p, const double* acc_
   xin.acc = acc_in; xin.count = count; xin.gamma = gamma; xin.beta = beta;
   xin.rmean = running_mean; xin.rvar = running_var; xin.momentum = momentum; xin.eps = eps;
   xin.coef_out = coef_out; xin.store = (unsigned short*)act_out;
-  msml_tl_stats_acc = 1;
-  const bool ok = msml_conv_halo_dispatch(in0, c0p, wp, kop, nullptr, out, coutp, reinterpret_cast<float*>(acc_out), N, H,
-                                          W, P, Q, R, S, stride, pad_h, pad_w, 0, (hipStream_t)stream, nullptr, nullptr,
-                                          nullptr, 0, nullptr, nullptr, &xin);
-  msml_tl_stats_acc = 0;
-  MSML_CHECK(ok, MSML_ERR_UNSUPPORTED, "conv2d_bnin_acc: launch refused");
+  ConvCall c = conv_call(in0, c0p, nullptr, 0, wp, kop, out, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, 0, stream);
+  c.xin = &xin;
+  set_stats(c, reinterpret_cast<float*>(acc_out), 1);
+  MSML_CHECK(msml_conv_halo_dispatch(c), MSML_ERR_UNSUPPORTED, "conv2d_bnin_acc: launch refused");
   MSML_LAUNCH_OK("conv2d_bnin_acc");
   return MSML_OK;
 }
@@ -695,29 +679,25 @@ extern "C" const char* msml_conv2d_kernel(int c0p, int c1p, int coutp, int N, in
     return bm == 128 ? "k_conv_igemm<mfm, bf16, 128 x 128>" : (bm == 64 ? "k_conv_igemm<mfm, bf16, 256 x 64>" : "k_conv_igemm<mfm, bf16, 256 x 32>");
   }
   const int bn = msml_conv_tile_n(coutp);
+  ConvShape s = conv_shape(c0p, c1p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed, want_stats != 0);
+  s.in_dtype = in_dtype; s.out_dtype = out_dtype;
   const bool fast = in_dtype == MSML_BF16 && !msml_opt().no_fast_conv && c0p % 32 == 0 && c1p % 32 == 0 &&
                     (c1p == 0 || ((R * S * (c0p / 32)) & 1) == 0) && (long)N * P * Q < (1L << 24);
-  if (fast && out_dtype == MSML_BF16 && !want_stats &&
-      msml_deconv4_applies(c0p, c1p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed))
+  if (fast && out_dtype == MSML_BF16 && !want_stats && msml_deconv4_applies(s))
     return "k_deconv4_fwd<14x16 input tile, 4 parity classes, weights resident>";
-  if (fast && c1p == 0 && out_dtype == MSML_BF16 && !want_stats &&
-      msml_conv_line_applies(c0p, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w))
+  if (fast && c1p == 0 && out_dtype == MSML_BF16 && !want_stats && msml_conv_line_applies(s))
     return "k_conv_line<full lines in LDS, weights resident, persistent>";
-  if (fast && c1p == 0 && out_dtype == MSML_BF16 &&
-      msml_conv_ws_applies(c0p, cdiv(coutp, bn) * bn, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, want_stats != 0))
+  if (fast && c1p == 0 && out_dtype == MSML_BF16 && msml_conv_ws_applies(s))
     return "k_conv_ws<64 -> 64 channels, weights resident, persistent>";    // (or k_conv_s2r<stride 1> without fused sums / residual)
-  if (fast && c1p == 0 && out_dtype == MSML_BF16 &&
-      msml_conv_halo_persist_shape(c0p, cdiv(coutp, bn) * bn, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w))
+  if (fast && c1p == 0 && out_dtype == MSML_BF16 && msml_conv_halo_persist_shape(s))
     return "k_conv_halo_p<14x14 px x 128 ch, persistent>";       // (training launches: no affine epilogue, accumulator-mode sums)
-  if (fast && c1p == 0 && out_dtype == MSML_BF16 &&
-      msml_conv_halo_applies(c0p, cdiv(coutp, bn) * bn, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, want_stats != 0))
+  if (fast && c1p == 0 && out_dtype == MSML_BF16 && msml_conv_halo_applies(s))
     return coutp % 256 == 0 ? "k_conv_halo<14x14 px x 256 ch, 8 waves>" : "k_conv_halo<14x14 px x 128 ch, 8 waves>";
-  if (fast && c1p == 0 && out_dtype == MSML_BF16 &&
-      msml_conv_s2r_applies(c0p, cdiv(coutp, bn) * bn, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed))
+  if (fast && c1p == 0 && out_dtype == MSML_BF16 && msml_conv_s2r_applies(s))
     return transposed ? "k_conv_s2r<64 -> 64 stride-2 backward-data, weights in registers, persistent>"
                       : "k_conv_s2r<64 -> 64 stride-2 forward, 4 parity planes, weights in registers, persistent>";
   if (fast && c1p == 0 && out_dtype == MSML_BF16) {
-    const int t2 = msml_conv_halo2_tiling(c0p, cdiv(coutp, bn) * bn, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed, 0);
+    const int t2 = msml_conv_halo2_tiling(s);
     if (t2 == 3) return "k_conv_halo2<mosaic of six 4x4 images x 128 ch>";
     if (t2 == 2) return stride == 1 ? "k_conv_halo2<mosaic of four 7x7 images x 128 ch>"
                                     : (transposed ? "k_conv_halo2<stride-2 backward-data, 4 classes, 7x7 mosaic x 128 ch>"

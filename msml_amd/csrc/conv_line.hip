@@ -15,6 +15,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "conv_call.h"
 #include "options.h"
 
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -180,15 +181,16 @@ __global__ void __launch_bounds__(512) k_conv_line(const ConvLineArgs p) {
 #endif
 }
 
-bool msml_conv_line_applies(int c0p, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
-                            int pad_w) {
+bool msml_conv_line_applies(const ConvShape& s) {
+  const int c0p = s.c0p, coutp = s.coutp, H = s.H, W = s.W;
   const bool off = msml_opt().no_line_conv;
   if (off) return false;
-  if (!((R == 7 && S == 1 && pad_h == 3 && pad_w == 0) || (R == 1 && S == 7 && pad_h == 0 && pad_w == 3))) return false;
-  if (stride != 1 || H != W || P != H || Q != W) return false;
+  if (!((s.R == 7 && s.S == 1 && s.pad_h == 3 && s.pad_w == 0) || (s.R == 1 && s.S == 7 && s.pad_h == 0 && s.pad_w == 3)))
+    return false;
+  if (s.stride != 1 || H != W || s.P != H || s.Q != W) return false;
   if (!(H == 56 || H == 28)) return false;            // 224 / H lines per tile; smaller maps stay on the generic kernel
   if (!((c0p == 64 && coutp == 32) || (c0p == 32 && coutp == 32) || (c0p == 32 && coutp == 64))) return false;
-  if ((long)N * H * W * c0p * 2 >= 0x70000000L) return false;
+  if ((long)s.N * H * W * c0p * 2 >= 0x70000000L) return false;
   return true;
 }
 
@@ -200,30 +202,27 @@ static void cl_launch(const ConvLineArgs& a, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_line<CIN, COUT>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const int per_cu = lds <= 76 * 1024 ? 2 : 1;
-  int grid = cus * per_cu;
+  int grid = msml_num_cus() * per_cu;
   if (grid > a.ntiles) grid = a.ntiles;
   k_conv_line<CIN, COUT><<<dim3(grid), dim3(512), lds, st>>>(a);
 }
 
-bool msml_conv_line_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out, int coutp,
-                             int N, int H, int W, int R, int S, int transposed, hipStream_t st, const float* scale,
-                             const void* residual) {
+bool msml_conv_line_dispatch(const ConvCall& c) {
+  const int c0p = c.c0p, coutp = c.coutp, N = c.N, H = c.H;
   ConvLineArgs a;
-  a.scale = scale; a.residual = (const unsigned short*)residual;
-  a.in = (const unsigned short*)in0; a.in_bytes = (unsigned int)((long)N * H * W * c0p * 2);
-  a.wp = (const unsigned short*)wp; a.w_bytes = (unsigned int)((long)kop * 7 * c0p * 2);
-  a.out = (unsigned short*)out; a.bias = bias;
+  a.scale = c.scale; a.residual = (const unsigned short*)c.residual;
+  a.in = (const unsigned short*)c.in0; a.in_bytes = (unsigned int)((long)N * H * c.W * c0p * 2);
+  a.wp = (const unsigned short*)c.wp; a.w_bytes = (unsigned int)((long)c.kop * 7 * c0p * 2);
+  a.out = (unsigned short*)c.out; a.bias = c.bias;
   a.N = N; a.L = H; a.B = 224 / H;
   a.tiles_per_img = cdiv(H, a.B);
   a.ntiles = N * a.tiles_per_img;
-  a.vertical = R == 7 ? 1 : 0;
-  a.flip = transposed ? 1 : 0;
-  if (c0p == 64 && coutp == 32) cl_launch<64, 32>(a, st);
-  else if (c0p == 32 && coutp == 32) cl_launch<32, 32>(a, st);
-  else if (c0p == 32 && coutp == 64) cl_launch<32, 64>(a, st);
+  a.vertical = c.R == 7 ? 1 : 0;
+  a.flip = c.transposed ? 1 : 0;
+  if (c0p == 64 && coutp == 32) cl_launch<64, 32>(a, c.st);
+  else if (c0p == 32 && coutp == 32) cl_launch<32, 32>(a, c.st);
+  else if (c0p == 32 && coutp == 64) cl_launch<32, 64>(a, c.st);
   else return false;
   return true;
 }

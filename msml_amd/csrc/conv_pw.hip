@@ -28,6 +28,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "conv_call.h"
 #include "options.h"
 
 struct ConvPwArgs {
@@ -308,12 +309,7 @@ static void pw_launch(const ConvPwArgs& a, hipStream_t st) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
   }
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    cus = n;
-  }
+  const int cus = msml_num_cus();
   // persistent workers: up to 4 workgroups of 4 waves per CU (the register / LDS footprint of the instantiation may
   // allow fewer -- the rest queue behind them); never more workers than units
   const int per_cu = msml_opt().pw_wgs_per_cu;
@@ -344,10 +340,14 @@ static bool pw_shape(const ConvPwArgs& a, int cin, int cout, hipStream_t st) {
 }
 
 // Tried by msml_conv_fast_dispatch before everything else; false = not a case this kernel takes.
-bool msml_conv_pw_dispatch(const void* in0, int c0p, const void* wp, int kop, int ktot, const float* bias, void* out,
-                           int coutp, float* stats, int stats_acc, int N, int H, int W, int P, int Q, int R, int S,
-                           int stride, int pad_h, int pad_w, hipStream_t st, const float* scale, const float* alpha,
-                           const void* residual, int res_first, const BnBwdFuse* bnb) {
+bool msml_conv_pw_dispatch(const ConvCall& c) {
+  const int c0p = c.c0p, coutp = c.coutp, H = c.H, W = c.W, ktot = c.R * c.S * c.c0p;
+  const float* const bias = c.bias;
+  const float* const scale = c.scale;
+  const void* const residual = c.residual;
+  float* const stats = c.stats;
+  const BnBwdFuse* const bnb = c.bnb;
+  hipStream_t st = c.st;
   // Measured against the general kernel on cold data (tools/bench_pw.py, batch 256, one box, us): forward + statistics
   // 32 -> 64 @ 112x112 177 -> 125 (4.9 TB/s; a device copy of the same bytes: 5.2-5.8), @ 56x56 51 -> 41, 64 -> 32 @ 56x56
   // 38 -> 29, the 28x28 layers 28 -> 25-29; backward-data 64 -> 32 @ 56x56 41 -> 29, 32 -> 64 33 -> 27 (5.6 TB/s),
@@ -355,16 +355,16 @@ bool msml_conv_pw_dispatch(const void* in0, int c0p, const void* wp, int kop, in
   // pixels, every 16-B access a memory request of its own -- and only won on the 112x112 stem; see DESIGN section 8 g.)
   // MSML_PW_CONV=0: the general kernel everywhere.
   if (!msml_opt().pw_conv) return false;
-  if (R != 1 || S != 1 || stride != 1 || pad_h != 0 || pad_w != 0 || P != H || Q != W) return false;
-  if (alpha || (residual && res_first)) return false;
-  if (stats && !stats_acc) return false;                // partial-row statistics stay on the general kernel
+  if (c.R != 1 || c.S != 1 || c.stride != 1 || c.pad_h != 0 || c.pad_w != 0 || c.P != H || c.Q != W) return false;
+  if (c.alpha || (residual && c.res_first)) return false;
+  if (stats && !c.stats_acc) return false;              // partial-row statistics stay on the general kernel
   if (bnb && (!bnb->acc || bias || scale || residual || stats)) return false;
   if (stats && residual) return false;
-  if (kop < coutp || ktot < c0p) return false;
-  const long M = (long)N * H * W;
+  if (c.kop < coutp || ktot < c0p) return false;
+  const long M = (long)c.N * H * W;
   if (M * (c0p > coutp ? c0p : coutp) * 2 >= 0x7fffff00L) return false;
   ConvPwArgs a;
-  a.in = (const unsigned short*)in0; a.wp = (const unsigned short*)wp; a.out = (unsigned short*)out;
+  a.in = (const unsigned short*)c.in0; a.wp = (const unsigned short*)c.wp; a.out = (unsigned short*)c.out;
   a.bias = bias; a.scale = scale; a.residual = (const unsigned short*)residual;
   a.stats = reinterpret_cast<double*>(stats);
   a.bnb = BnBwdFuse{};

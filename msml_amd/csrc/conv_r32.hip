@@ -18,6 +18,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "conv_call.h"
 #include "options.h"
 
 struct ConvR32Args {
@@ -261,12 +262,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 
 template <int MODE, bool FLIP>
 static void r32_launch(ConvR32Args& a, hipStream_t st) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    cus = n;
-  }
+  const int cus = msml_num_cus();
   // strips: at least ~8 workers per CU, at most 14 rows each (two halo rows are re-read per strip)
   const int rows_env = msml_opt().r32_rows;
   int rs = 14;
@@ -289,24 +285,27 @@ static void r32_launch(ConvR32Args& a, hipStream_t st) {
 }
 
 // Tried by msml_conv_fast_dispatch first; false = not a case this kernel takes.
-bool msml_conv_r32_dispatch(const void* in0, int c0p, const void* wp, int kop, int ktot, const float* bias, void* out,
-                            int coutp, float* stats, int stats_acc, int N, int H, int W, int P, int Q, int R, int S,
-                            int stride, int pad_h, int pad_w, int transposed, hipStream_t st, const float* scale,
-                            const float* alpha, const void* residual, const BnBwdFuse* bnb) {
+bool msml_conv_r32_dispatch(const ConvCall& c) {
+  const int N = c.N, H = c.H, W = c.W, ktot = c.R * c.S * c.c0p;
+  float* const stats = c.stats;
+  const BnBwdFuse* const bnb = c.bnb;
+  hipStream_t st = c.st;
   if (msml_opt().no_r32_conv) return false;
-  if (c0p != 32 || coutp != 32 || R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || P != H || Q != W) return false;
-  if (bias || scale || alpha || residual) return false;
-  if (stats && !stats_acc) return false;
+  if (c.c0p != 32 || c.coutp != 32 || c.R != 3 || c.S != 3 || c.stride != 1 || c.pad_h != 1 || c.pad_w != 1 || c.P != H ||
+      c.Q != W)
+    return false;
+  if (c.bias || c.scale || c.alpha || c.residual) return false;
+  if (stats && !c.stats_acc) return false;
   if (bnb && (!bnb->acc || stats)) return false;
-  if (W < 8 || W > 62 || H < 2 || kop < 32 || ktot < 288) return false;
+  if (W < 8 || W > 62 || H < 2 || c.kop < 32 || ktot < 288) return false;
   if ((long)N * H * W * 64 >= 0x7fffff00L) return false;
   ConvR32Args a;
-  a.in = (const unsigned short*)in0; a.wp = (const unsigned short*)wp; a.out = (unsigned short*)out;
+  a.in = (const unsigned short*)c.in0; a.wp = (const unsigned short*)c.wp; a.out = (unsigned short*)c.out;
   a.stats = reinterpret_cast<double*>(stats);
   a.bnb = BnBwdFuse{};
   if (bnb) a.bnb = *bnb;
   a.N = N; a.H = H; a.W = W; a.ktot = ktot;
-  if (transposed) {
+  if (c.transposed) {
     if (bnb) r32_launch<R32_BNB, true>(a, st);
     else if (stats) r32_launch<R32_STATS, true>(a, st);
     else r32_launch<R32_PLAIN, true>(a, st);

@@ -21,6 +21,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "conv_call.h"
 #include "options.h"
 
 struct ConvS2rArgs {
@@ -561,21 +562,11 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 #endif
 }
 
-static int s2r_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 // 1 when k_conv_s2r takes the shape: 64 -> 64 channels, 3x3, stride 2, pad 1, even maps, enough real GEMM rows.
-int msml_conv_s2r_applies(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
-                          int pad_w, int transposed) {
+int msml_conv_s2r_applies(const ConvShape& s) {
+  const int N = s.N, H = s.H, W = s.W, P = s.P, Q = s.Q, stride = s.stride, transposed = s.transposed;
   const bool off = msml_opt().no_s2r_conv;
-  if (off || R != 3 || S != 3 || pad_h != 1 || pad_w != 1 || c0p != 64 || coutp != 64 || kop < 64) return 0;
+  if (off || s.R != 3 || s.S != 3 || s.pad_h != 1 || s.pad_w != 1 || s.c0p != 64 || s.coutp != 64 || s.kop < 64) return 0;
   // stride 1 (the layers of conv_ws.hip): forward + statistics and plain backward-data measured faster here (round 5, one box:
   // 64 -> 64 @ 112x112 389 -> 350 us, @ 56x56 87 -> 81 us; backward-data 350 -> 312 / 83 -> 71 us), the fused-BatchNorm
   // backward-data slower (92.6 -> 100.7 us: 16-channel waves touch 32 B per pixel) -- the dispatcher keeps that one on
@@ -603,33 +594,34 @@ static void launch_s2r(ConvS2rArgs& a, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_s2r<MODE, FUSE>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
   });
-  const int wgs = a.ntiles < s2r_num_cus() ? a.ntiles : s2r_num_cus();
+  const int wgs = a.ntiles < msml_num_cus() ? a.ntiles : msml_num_cus();
   k_conv_s2r<MODE, FUSE><<<dim3(wgs), dim3(512), lds, st>>>(a);
 }
 
 // Tried by msml_conv_fast_dispatch before the im2col kernel; false = shape / epilogue not covered here.
-bool msml_conv_s2r_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out, int coutp,
-                            float* stats, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w,
-                            int transposed, hipStream_t st, const float* scale, const float* alpha, const void* residual,
-                            const BnBwdFuse* bnb, int* bnb_rows) {
-  if (!msml_conv_s2r_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, transposed)) return false;
-  if (bias || scale || alpha || residual) return false;
+bool msml_conv_s2r_dispatch(const ConvCall& c) {
+  const int N = c.N, H = c.H, W = c.W, P = c.P, Q = c.Q, stride = c.stride, transposed = c.transposed;
+  float* const stats = c.stats;
+  const BnBwdFuse* const bnb = c.bnb;
+  hipStream_t st = c.st;
+  if (!msml_conv_s2r_applies(c)) return false;
+  if (c.bias || c.scale || c.alpha || c.residual) return false;
   if (stride == 1 && bnb) return false;                 // (see msml_conv_s2r_applies)
-  if (stats && (!msml_tl_stats_acc || (transposed && stride == 2))) return false;
+  if (stats && (!c.stats_acc || (transposed && stride == 2))) return false;
   if (bnb && (!bnb->acc || !transposed || stats)) return false;
   ConvS2rArgs a;
-  a.in = (const unsigned short*)in0; a.in_bytes = (unsigned int)((long)N * H * W * 64 * 2);
+  a.in = (const unsigned short*)c.in0; a.in_bytes = (unsigned int)((long)N * H * W * 64 * 2);
   a.N = N; a.IH = H; a.IW = W;
   a.GH = (transposed || stride == 1) ? H : P; a.GW = (transposed || stride == 1) ? W : Q;
   a.flip = transposed;
   a.OH = P; a.OW = Q;
   a.tpy = cdiv(a.GH, 14); a.tpx = cdiv(a.GW, 14); a.ntiles = N * a.tpy * a.tpx;
-  a.wp = (const unsigned short*)wp;
-  a.out = (unsigned short*)out; a.out_bytes = (unsigned int)((long)N * P * Q * 64 * 2);
+  a.wp = (const unsigned short*)c.wp;
+  a.out = (unsigned short*)c.out; a.out_bytes = (unsigned int)((long)N * P * Q * 64 * 2);
   a.stats = stats;
   a.bnb = BnBwdFuse{};
   if (bnb) a.bnb = *bnb;
-  if (bnb_rows) *bnb_rows = a.ntiles < s2r_num_cus() ? a.ntiles : s2r_num_cus();
+  if (c.bnb_rows) *c.bnb_rows = a.ntiles < msml_num_cus() ? a.ntiles : msml_num_cus();
   if (stride == 1) { if (bnb) launch_s2r<0, true>(a, st); else launch_s2r<0, false>(a, st); }
   else if (!transposed) launch_s2r<1, false>(a, st);
   else if (bnb) launch_s2r<2, true>(a, st);
@@ -639,29 +631,30 @@ bool msml_conv_s2r_dispatch(const void* in0, int c0p, const void* wp, int kop, c
 
 // Split-bf16 inference (msml_conv2d_x3): 64 -> 64 channel 3x3 / stride-1 / pad-1 forward layers; c0p = 3 x 64 as the fast
 // dispatcher sees it.  MSML_NO_S2R_X3=1 leaves them on k_conv_fast.
-bool msml_conv_s2r_x3_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out, int coutp, int N,
-                               int H, int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w, int transposed,
-                               hipStream_t st, const float* scale, const float* alpha, const void* residual, int res_first) {
+bool msml_conv_s2r_x3_dispatch(const ConvCall& c) {
+  const int N = c.N, H = c.H, W = c.W;
   if (msml_opt().no_s2r_conv || msml_opt().no_s2r_x3) return false;
-  if (R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || transposed || c0p != 192 || coutp != 64 || kop < 64) return false;
-  if (P != H || Q != W) return false;
+  if (c.R != 3 || c.S != 3 || c.stride != 1 || c.pad_h != 1 || c.pad_w != 1 || c.transposed || c.c0p != 192 || c.coutp != 64 ||
+      c.kop < 64)
+    return false;
+  if (c.P != H || c.Q != W) return false;
   const long tiles = (long)N * cdiv(H, 14) * cdiv(W, 14);
   if ((long)N * H * W * 10 < tiles * 224 * 7) return false;            // < 70 % real GEMM rows
   if ((long)N * H * W * 192 * 2 >= 0x70000000L) return false;
   ConvS2rX3Args a;
-  a.in = (const unsigned short*)in0; a.in_bytes = (unsigned int)((long)N * H * W * 192 * 2);
+  a.in = (const unsigned short*)c.in0; a.in_bytes = (unsigned int)((long)N * H * W * 192 * 2);
   a.N = N; a.GH = H; a.GW = W;
   a.tpy = cdiv(H, 14); a.tpx = cdiv(W, 14); a.ntiles = N * a.tpy * a.tpx;
-  a.wp = (const unsigned short*)wp;
-  a.out = (unsigned short*)out; a.out_bytes = a.in_bytes;
-  a.scale = scale; a.bias = bias; a.alpha = alpha; a.residual = (const unsigned short*)residual; a.res_first = res_first;
-  a.bias9 = bias ? msml_tl_bias9 : 0;
+  a.wp = (const unsigned short*)c.wp;
+  a.out = (unsigned short*)c.out; a.out_bytes = a.in_bytes;
+  a.scale = c.scale; a.bias = c.bias; a.alpha = c.alpha; a.residual = (const unsigned short*)c.residual; a.res_first = c.res_first;
+  a.bias9 = c.bias ? c.bias9 : 0;
   const size_t lds = (size_t)4 * 256 * 128 + 1024 + 11 * 64 * sizeof(float);
   static std::once_flag attr_once;
   std::call_once(attr_once, [&] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_s2r_x3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
-  const int wgs = a.ntiles < s2r_num_cus() ? a.ntiles : s2r_num_cus();
-  k_conv_s2r_x3<<<dim3(wgs), dim3(512), lds, st>>>(a);
+  const int wgs = a.ntiles < msml_num_cus() ? a.ntiles : msml_num_cus();
+  k_conv_s2r_x3<<<dim3(wgs), dim3(512), lds, c.st>>>(a);
   return true;
 }

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "conv_call.h"
 #include "options.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
@@ -590,9 +591,6 @@ extern "C" int msml_conv_wgrad_group(const void* const* u, const void* const* v,
 
 
 // ---------------------------------------------------------------- split-K GEMM (head dX) -----
-bool msml_conv_fast_splitk(const void* in0, int c0p, const void* wp, int kop, float* ws, int coutp, int N,
-                           int ksplits, hipStream_t st);
-
 // Weight gradient of a conv whose input was X = PReLU(v * x_scale + x_shift) (a training-mode
 // BatchNorm in front of the conv that msml_conv2d_bnin applied on the fly): the strips of v are
 // normalised in LDS, X never exists in HBM.  Only the shapes of the strip / halo kernel

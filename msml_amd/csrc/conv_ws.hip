@@ -17,6 +17,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "conv_call.h"
 #include "options.h"
 
 struct ConvWsArgs {
@@ -458,27 +459,17 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 #endif
 }
 
-static int ws_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
-bool msml_conv_ws_applies(int c0p, int kop, int coutp, int N, int H, int W, int P, int Q, int R, int S,
-                          int stride, int pad_h, int pad_w, bool want_stats) {
+bool msml_conv_ws_applies(const ConvShape& s) {
+  const int N = s.N, H = s.H, W = s.W;
   const bool off = msml_opt().no_ws_conv;
   if (off) return false;
-  if (R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || P != H || Q != W) return false;
-  if (c0p != 64 || coutp != 64 || kop < 64) return false;
+  if (s.R != 3 || s.S != 3 || s.stride != 1 || s.pad_h != 1 || s.pad_w != 1 || s.P != H || s.Q != W) return false;
+  if (s.c0p != 64 || s.coutp != 64 || s.kop < 64) return false;
   const long tiles = (long)N * cdiv(H, 14) * cdiv(W, 14);
   if ((long)N * H * W * 10 < tiles * 224 * 7) return false;       // < 70 % real GEMM rows: im2col kernel wins
-  const int wgs = tiles < ws_num_cus() ? (int)tiles : ws_num_cus();
-  if (want_stats && wgs > cdiv((long)N * P * Q, msml_conv_tile_m(coutp))) return false;
-  return (long)N * H * W * c0p * 2 < 0x70000000L && tiles < (1L << 30);
+  const int wgs = tiles < msml_num_cus() ? (int)tiles : msml_num_cus();
+  if (s.want_stats && wgs > cdiv((long)N * s.P * s.Q, msml_conv_tile_m(s.coutp))) return false;
+  return (long)N * H * W * s.c0p * 2 < 0x70000000L && tiles < (1L << 30);
 }
 
 template <bool FUSE, bool M16 = false>
@@ -489,33 +480,31 @@ static void launch_ws(ConvWsArgs& a, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_ws<FUSE, M16>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
-  const int wgs = a.ntiles < ws_num_cus() ? a.ntiles : ws_num_cus();
+  const int wgs = a.ntiles < msml_num_cus() ? a.ntiles : msml_num_cus();
   k_conv_ws<FUSE, M16><<<dim3(wgs), dim3(512), lds, st>>>(a);
 }
 
 // Tried by msml_conv_fast_dispatch before the im2col kernel; false = shape not covered here.
-bool msml_conv_ws_dispatch(const void* in0, int c0p, const void* wp, int kop, const float* bias, void* out,
-                           int coutp, float* stats, int N, int H, int W, int P, int Q, int R, int S,
-                           int stride, int pad_h, int pad_w, int transposed, hipStream_t st,
-                           const float* scale, const float* alpha, const void* residual, int res_first,
-                           const BnBwdFuse* bnb, int* bnb_rows) {
-  if (!msml_conv_ws_applies(c0p, kop, coutp, N, H, W, P, Q, R, S, stride, pad_h, pad_w, stats != nullptr))
-    return false;
-  if (bnb && (bias || scale || alpha || residual || stats)) return false;
+bool msml_conv_ws_dispatch(const ConvCall& c) {
+  const int N = c.N, H = c.H, W = c.W;
+  const BnBwdFuse* const bnb = c.bnb;
+  hipStream_t st = c.st;
+  if (!msml_conv_ws_applies(c)) return false;
+  if (bnb && (c.bias || c.scale || c.alpha || c.residual || c.stats)) return false;
   ConvWsArgs a;
   a.tpy = cdiv(H, 14); a.tpx = cdiv(W, 14);
   a.ntiles = N * a.tpy * a.tpx;
-  a.in = (const unsigned short*)in0; a.in_bytes = (unsigned int)((long)N * H * W * c0p * 2);
-  a.N = N; a.H = H; a.W = W; a.flip = transposed;
-  a.wp = (const unsigned short*)wp;
-  a.out = (unsigned short*)out;
-  a.bias = bias; a.scale = scale; a.alpha = alpha; a.residual = (const unsigned short*)residual;
-  a.res_first = res_first; a.stats = stats;
-  a.stats_rows = cdiv((long)N * P * Q, msml_conv_tile_m(coutp));
-  a.stats_acc = stats ? msml_tl_stats_acc : 0;
+  a.in = (const unsigned short*)c.in0; a.in_bytes = (unsigned int)((long)N * H * W * c.c0p * 2);
+  a.N = N; a.H = H; a.W = W; a.flip = c.transposed;
+  a.wp = (const unsigned short*)c.wp;
+  a.out = (unsigned short*)c.out;
+  a.bias = c.bias; a.scale = c.scale; a.alpha = c.alpha; a.residual = (const unsigned short*)c.residual;
+  a.res_first = c.res_first; a.stats = c.stats;
+  a.stats_rows = cdiv((long)N * c.P * c.Q, msml_conv_tile_m(c.coutp));
+  a.stats_acc = c.stats ? c.stats_acc : 0;
   a.bnb = BnBwdFuse{};
   if (bnb) a.bnb = *bnb;
-  if (bnb_rows) *bnb_rows = a.ntiles < ws_num_cus() ? a.ntiles : ws_num_cus();
+  if (c.bnb_rows) *c.bnb_rows = a.ntiles < msml_num_cus() ? a.ntiles : msml_num_cus();
   // 16x16x32 variant: measured neutral here (64 -> 64 @ 112x112 forward 426 -> 408 us, backward-data and the 56x56 maps
   // +-1 %: this kernel waits on its image loads and transposes, not on the MFMA clock) -- opt-in, MSML_WS_M16=1
   // Round 5: with the direct stores (no LDS transpose, one barrier per tile) the 16x16x32 variant is the faster one -- 64 -> 64 @

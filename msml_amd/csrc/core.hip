@@ -15,6 +15,16 @@ void msml_set_error(const char* fmt, ...) {
 extern "C" int msml_version(void) { return MSML_ABI_VERSION; }
 extern "C" const char* msml_last_error(void) { return g_err; }
 
+int msml_num_cus() {
+  static const int n = [] {                            // (initialised once, by whichever thread comes first)
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+      v = 256;
+    return v;
+  }();
+  return n;
+}
+
 extern "C" long msml_stream_capture_id(void* stream) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   unsigned long long id = 0;

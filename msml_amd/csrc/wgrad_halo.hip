@@ -351,16 +351,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 #endif
 }
 
-static int wh_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 // splits for a shape (0 = shape not covered by this kernel)
 // 128-row dW tiles halve the operand traffic per FLOP; 64-row tiles halve the split-K slab bytes
 // (measured at 256 -> 256 @ 14x14: 97 us with 128-row tiles, 104 us with 64-row tiles)
@@ -381,7 +371,7 @@ int msml_wgrad_halo_splits(int up, int vp, int A, int Breal, int N, int H, int W
   if ((long)N * H * W * up * 2 >= 0x70000000L || (long)N * H * W * vp * 2 >= 0x70000000L) return 0;
   // (image-pair strips: 64-row tiles only -- the 128-row instantiation of that variant spills)
   const int tiles = ((wh_wide(up) && !pair7) ? up / 128 : up / 64) * (vp / 64);
-  long splits = wh_cus() / tiles;                      // one resident workgroup per CU
+  long splits = msml_num_cus() / tiles;                      // one resident workgroup per CU
   if (splits < 1) splits = 1;
   if (splits > strips) splits = strips;
   if (splits > 512) splits = 512;

@@ -169,16 +169,6 @@ __global__ void __launch_bounds__(512) k_wgrad_n32(const WgradN32Args p) {
 #endif
 }
 
-static int wn_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 // splits for a shape (0 = shape not covered by this kernel)
 int msml_wgrad_n32_splits(int up, int vp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
                           int pad_w) {
@@ -190,8 +180,8 @@ int msml_wgrad_n32_splits(int up, int vp, int N, int H, int W, int P, int Q, int
   if (P < 14 || Q < 14) return 0;                    // tiny maps: the generic kernel is as good
   if ((long)N * H * W * 64 >= 0x70000000L) return 0;
   const long strips = (long)N * cdiv(P, 4) * cdiv(Q, 16);
-  long splits = 2L * wn_cus();                       // two resident workgroups per CU where LDS allows (3x3)
-  if (d4) splits = wn_cus();
+  long splits = 2L * msml_num_cus();                       // two resident workgroups per CU where LDS allows (3x3)
+  if (d4) splits = msml_num_cus();
   if (splits > strips) splits = strips;
   if (splits > 512) splits = 512;
   return (int)splits;
@@ -343,7 +333,7 @@ int msml_wgrad_line_splits(int up, int vp, int N, int H, int W, int P, int Q, in
   if (H != W || P != H || Q != W || !(H == 56 || H == 28)) return 0;
   if ((long)N * H * W * vp * 2 >= 0x70000000L) return 0;
   const long tiles = (long)N * cdiv(H, 224 / H);
-  long splits = (vp == 32 ? 2L : 1L) * wn_cus();
+  long splits = (vp == 32 ? 2L : 1L) * msml_num_cus();
   if (splits > tiles) splits = tiles;
   if (splits > 512) splits = 512;
   return (int)splits;
