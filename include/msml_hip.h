@@ -623,6 +623,21 @@ const char* msml_conv2d_kernel(int c0p, int c1p, int coutp, int N, int H, int W,
 int msml_stem_im2col(const float* x, void* out, int N, int C, int H, int W, int P, int Q, int R,
                      int S, int stride, int pad, int KP, int dtype, void* stream);
 
+/* Backward-data of a stem conv, to the image (the gradient autograd gives iresnet.py:209 `conv1`, unet.py:193 and
+ * lightcnn.py:150 for their input): the adjoint of msml_stem_im2col + the 1x1 conv over the patches in ONE launch,
+ *   dx[n][c][iy][ix] = sum over k, r, s of dy[n][oy][ox][k] * w[k][c][r][s],  iy = oy*stride - pad + r, ix = ox*stride - pad + s.
+ *   dy [N][P][Q][ldy] bf16 or f32 (dtype), the first Cout channels real (the others are never read); w the parameter's
+ *   own f32 OIHW [Cout][C][R][S] (bf16 dy: rounded to bf16 in LDS; f32 dy: used as it is); dx NCHW f32 [N][C][H][W],
+ *   every element stored (no accumulate mode).  f32 accumulation; one writer per element and a fixed summation order:
+ *   two runs give the same bits.
+ *   Serves C in {1, 3}, R = S in {3, 5} with R*S*C <= 32, stride in {1, 2}, pad = R/2, Cout % 32 == 0 and <= 128,
+ *   ldy >= Cout, ldy % 8 == 0, W <= 128, P / Q the conv's output size; anything else, a null pointer or a misaligned
+ *   one (dy 16 bytes) returns MSML_ERR_SHAPE before any launch (another dtype: MSML_ERR_DTYPE).
+ * msml_stem_bwd_data_band: input rows per workgroup of the bf16 kernel for such a shape (0: not served). */
+int msml_stem_bwd_data(const void* dy, const float* w, float* dx, int N, int C, int H, int W, int P, int Q,
+                       int Cout, int ldy, int R, int S, int stride, int pad, int dtype, void* stream);
+int msml_stem_bwd_data_band(int C, int H, int W, int Cout, int R, int stride);
+
 /* msml_bn_act_bwd_apply that also reduces the backward sums of the activation-free BatchNorm whose
  * output gradient the written dx is (chained IBasicBlocks: block i+1's bn1 input gradient is block
  * i's output gradient, i.e. the dy of block i's bn3, iresnet.py:65): next_x = that BatchNorm's

@@ -18,11 +18,14 @@ class _ToNHWC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, dtype):
+        ctx.c, ctx.xdtype = x.shape[1], x.dtype
         return ops.to_nhwc(x.float(), dtype)
 
     @staticmethod
     def backward(ctx, g):
-        return None, None
+        # reached only when the image requires a gradient: the first conv's backward-data then produced g
+        dx = ops.to_nchw(g.contiguous(), ctx.c)
+        return (dx if ctx.xdtype is torch.float32 else dx.to(ctx.xdtype)), None
 
 
 def to_nhwc(x, dtype):
@@ -851,12 +854,14 @@ def _stem_pack(conv_m):
 
 
 class _StemConv(torch.autograd.Function):
-    """3x3 conv on the 3-channel image as im2col + 1x1 conv; only the weight gets a gradient."""
+    """3x3 conv on the 3-channel image as im2col + 1x1 conv.  The weight gradient is the 1x1 conv's; an image that
+    requires a gradient gets it from dy in one launch (msml_stem_bwd_data: no patch gradient in between)."""
 
     @staticmethod
     def forward(ctx, weight, conv_m, raw):
         cout, cin, r, s = weight.shape
         col = ops.stem_im2col(raw, r, s, conv_m.stride[0], conv_m.padding[0])
+        ctx.xshape, ctx.geom = tuple(raw.shape), (conv_m.stride[0], conv_m.padding[0])
         wp = _stem_pack(conv_m)
         y, stats = ops.conv2d(col, None, wp, None, cpad(cout), 1, 1, 1, 0, 0, False, want_stats=True,
                               real=(r * s * cin, cout))
@@ -875,13 +880,18 @@ class _StemConv(torch.autograd.Function):
         cout, cin, r, s = w.shape
         k = r * s * cin
         dw2 = torch.empty(cout, k, 1, 1, dtype=torch.float32, device=dy.device)
-        ops.conv_wgrad(dy.contiguous(), col, dw2, cout, k, k, 0, 1, 1, 1, 0, 0)
+        dy = dy.contiguous()
+        ops.conv_wgrad(dy, col, dw2, cout, k, k, 0, 1, 1, 1, 0, 0)
         dw = dw2.view(cout, r, s, cin).permute(0, 3, 1, 2)          # back to the parameter's OIHW
+        dx = None
+        if ctx.needs_input_grad[2]:
+            n, _, h, wd = ctx.xshape
+            dx = ops.stem_bwd_data(dy, w, n, cin, h, wd, r, s, ctx.geom[0], ctx.geom[1])
         if ops.inplace(w):
             w.grad.view(w.shape).add_(dw)
             ops.grad_ready(w)
-            return None, None, None
-        return dw.contiguous(), None, None
+            return None, None, dx
+        return dw.contiguous(), None, dx
 
 
 def stem_conv_bn(raw, conv_m, bn_m, prelu):
@@ -1379,7 +1389,8 @@ class _MfmConv(torch.autograd.Function):
     then the filter's backward-data, weight- and bias-gradient run as for a plain conv (_Conv._bwd)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, conv_m, c, geom, grad_param):
+    def forward(ctx, x, weight, bias, residual, conv_m, c, geom, grad_param, raw, stem):
+        # raw / stem: the mfm stem (mfm_stem) -- x is the unfolded `raw` image, stem = (r, s, stride, pad) of that unfold
         r, s, stride, pad = geom
         n, h, w, cinp = x.shape
         dtype = DTYPE_OF[x.dtype]
@@ -1404,6 +1415,7 @@ class _MfmConv(torch.autograd.Function):
         ctx.c, ctx.geom, ctx.has_res = c, geom, residual is not None
         ctx.grad_param = weight if grad_param is None else grad_param
         ctx.bias = bias
+        ctx.stem = None if raw is None else (tuple(raw.shape), stem)
         ctx.save_for_backward(x, weight, sel)
         ctx.mark_non_differentiable(sel)
         return out, sel
@@ -1427,7 +1439,12 @@ class _MfmConv(torch.autograd.Function):
         need = (ctx.needs_input_grad[0], False, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
         g = _Conv._bwd(bctx, dz, need)
         dres = dy if ctx.has_res and ctx.needs_input_grad[3] else None
-        return g[0], g[2], g[3], dres, None, None, None, None
+        draw = None
+        if ctx.stem is not None and ctx.needs_input_grad[8]:
+            # the image's gradient straight from dz and the parameter's OIHW filter (no 1x1 backward-data into patches)
+            (n_, cin, h, wd), (sr, ss, sstride, spad) = ctx.stem
+            draw = ops.stem_bwd_data(dz, ctx.grad_param, n_, cin, h, wd, sr, ss, sstride, spad)
+        return g[0], g[2], g[3], dres, None, None, None, None, draw, None
 
 
 def mfm_conv(conv_m, c, x, residual=None):
@@ -1436,21 +1453,23 @@ def mfm_conv(conv_m, c, x, residual=None):
     assert conv_m.padding[0] == conv_m.padding[1] and conv_m.out_channels == 2 * c
     r, s = conv_m.kernel_size
     geom = (r, s, conv_m.stride[0], conv_m.padding[0])
-    y, _ = _MfmConv.apply(x, conv_m.weight, conv_m.bias, residual, conv_m, c, geom, None)
+    y, _ = _MfmConv.apply(x, conv_m.weight, conv_m.bias, residual, conv_m, c, geom, None, None, None)
     return y
 
 
 def mfm_stem(conv_m, c, raw, dtype):
     """mfm stem on the NCHW f32 image (lightcnn.py:150, 5x5 / 1 channel): im2col to K = R*S*Cin -> 32 patches
-    (msml_stem_im2col) and a 1x1 mfm conv over them -- no conv over a channel-padded image.  Only the filter gets
-    gradients (the image is a leaf)."""
+    (msml_stem_im2col) and a 1x1 mfm conv over them -- no conv over a channel-padded image.  The unfold itself is outside
+    autograd; an image that requires a gradient rides along as an input of the mfm node, whose backward feeds its dz to
+    msml_stem_bwd_data."""
     cout, cin, r, s = conv_m.weight.shape
     # (cin == 1: the view below is the parameter's own memory, so an in-place gradient arena receives dW directly)
     assert cout == 2 * c and cin == 1 and r * s <= 32 and conv_m.stride[0] == 1
     col = ops.stem_im2col(raw, r, s, conv_m.stride[0], conv_m.padding[0], dtype=dtype)
     # im2col's k = (r*S + s)*Cin + c, the row-major flatten of the (Cin = 1) filter: a view of the parameter
     wv = conv_m.weight.permute(0, 2, 3, 1).reshape(cout, r * s * cin, 1, 1)
-    y, _ = _MfmConv.apply(col, wv, conv_m.bias, None, conv_m, c, (1, 1, 1, 0), conv_m.weight)
+    y, _ = _MfmConv.apply(col, wv, conv_m.bias, None, conv_m, c, (1, 1, 1, 0), conv_m.weight, raw,
+                          (r, s, conv_m.stride[0], conv_m.padding[0]))
     return y
 
 

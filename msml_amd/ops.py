@@ -240,6 +240,28 @@ def stem_im2col(x, r, s, stride, pad, kp=32, dtype=BF16):
     return out
 
 
+# A/B switch of the input-image gradient (tools/bench_stem_bwd.py, the no-cost-when-unused test): with MSML_NO_STEM_BWD_DATA
+# in the environment (or this flag set) the gradient is refused; there is no second path.
+NO_STEM_BWD_DATA = os.environ.get("MSML_NO_STEM_BWD_DATA") is not None
+
+
+def stem_bwd_data(dy, weight, n, c, h, w, r, s, stride, pad):
+    """Gradient of a stem conv for its NCHW f32 input image: dy [N][P][Q][ldy] (bf16 or f32 storage, weight.shape[0] real
+    channels) and the parameter's own f32 OIHW weight -> dx [n, c, h, w] f32 (msml_stem_bwd_data, one launch)."""
+    if NO_STEM_BWD_DATA:
+        raise RuntimeError("msml_amd: the input image requires a gradient, and MSML_NO_STEM_BWD_DATA switches "
+                           "msml_stem_bwd_data off; there is no other path for it")
+    p = conv_out_size(h, r, stride, pad, False)
+    q = conv_out_size(w, s, stride, pad, False)
+    cout = weight.shape[0]
+    assert dy.is_contiguous() and tuple(dy.shape[:3]) == (n, p, q) and tuple(weight.shape) == (cout, c, r, s)
+    wd = weight.detach().float().contiguous()          # (the parameter itself: f32 and contiguous already, no copy)
+    dx = torch.empty(n, c, h, w, dtype=torch.float32, device=dy.device)
+    with PROFILE.rec("stem_bwd_data", 0.0, dy.numel() * dy.element_size() + dx.numel() * 4):
+        call("msml_stem_bwd_data", dy, wd, dx, n, c, h, w, p, q, cout, dy.shape[3], r, s, stride, pad, DTYPE_OF[dy.dtype])
+    return dx
+
+
 def conv_label(kind, c0p, c1p, coutp, n, h, w, p, q, r, s, stride, pad_h, pad_w, transposed, in_dtype, out_dtype,
                want_stats):
     """Profiling label of one conv launch: shape + the kernel the library picks for it."""

@@ -52,6 +52,28 @@ def extract_embeddings(model, x, normalize=False):
     return out
 
 
+def pair_saliency(model, a, b, flip=False):
+    """Which pixels drive a match: (cos, da, db) for the image batches a, b (B, C, H, W) -- cos (B,) the cosine of the
+    embeddings of a[i] and b[i] (flip=True: of the orig + mirror sums, as extract_embeddings), da / db its gradient for
+    each image batch (the stems' msml_stem_bwd_data in bf16 mode).  Runs the model in eval mode (BatchNorm statistics
+    untouched) and puts every module's mode back; no host synchronisation.  torch.autograd.grad on the images: a
+    parameter's .grad is left alone unless it is a FlatSGD arena view, which the backward kernels add into directly --
+    freeze the parameters (requires_grad_(False)) for a map without that and at less cost."""
+    from . import functional as Fh
+    modes = [(m, m.training) for m in model.modules()]
+    model.eval()
+    try:
+        with torch.enable_grad():
+            xs = [t.detach().requires_grad_(True) for t in (a, b)]
+            emb = [model(x)[0] + model(x.flip(3))[0] if flip else model(x)[0] for x in xs]
+            cos = (Fh.normalize(emb[0].float()) * Fh.normalize(emb[1].float())).sum(1)
+            da, db = torch.autograd.grad(cos.sum(), xs)
+    finally:
+        for m, mode in modes:
+            m.training = mode
+    return cos.detach(), da, db
+
+
 @torch.no_grad()
 def pair_cosine(emb):
     """Cosine of every pair (rows 2i, 2i+1) of summed embeddings: 1 - dist / 2 with the f64 distance of
