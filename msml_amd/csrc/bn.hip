@@ -101,6 +101,15 @@ __global__ void __launch_bounds__(256) k_bn_stats(const T* __restrict__ x, long 
   }, acc_mode);
 }
 
+// the launch of a slab reducer over `rows` workgroups: few workgroups take the pipelined loop (slab_reduce)
+template <typename DT>
+static void launch_bn_stats(const void* x, long M, int C, float* partial, int acc_mode, int rows, hipStream_t st) {
+  if (rows <= RED_PIPE_MAX_ROWS)
+    (k_bn_stats<DT, true>)<<<rows, 256, red_lds(2, C), st>>>((const DT*)x, M, C, partial, acc_mode);
+  else
+    (k_bn_stats<DT, false>)<<<rows, 256, red_lds(2, C), st>>>((const DT*)x, M, C, partial, acc_mode);
+}
+
 extern "C" int msml_bn_stats_rows(long M, int C) { return red_rows(M, C); }
 
 // msml_bn_stats and msml_bn_stats_acc: partial rows or, with acc_mode, an accumulator (common.h)
@@ -108,11 +117,7 @@ static int bn_stats(const void* x, long M, int C, float* partial, int acc_mode, 
   MSML_CHECK(x && partial && M > 0 && C > 0 && C % 8 == 0 && C <= 2048, MSML_ERR_SHAPE,
              "bn_stats: bad shape M=%ld C=%d", M, C);
   int rows = red_rows(M, C);
-  MSML_DISPATCH_DTYPE(dtype, "bn_stats",
-                      if (rows <= RED_PIPE_MAX_ROWS)
-                        (k_bn_stats<DT, true>)<<<rows, 256, red_lds(2, C), (hipStream_t)stream>>>((const DT*)x, M, C, partial, acc_mode);
-                      else
-                        (k_bn_stats<DT, false>)<<<rows, 256, red_lds(2, C), (hipStream_t)stream>>>((const DT*)x, M, C, partial, acc_mode);)
+  MSML_DISPATCH_DTYPE(dtype, "bn_stats", launch_bn_stats<DT>(x, M, C, partial, acc_mode, rows, (hipStream_t)stream);)
   MSML_LAUNCH_OK("bn_stats");
   return MSML_OK;
 }
@@ -196,32 +201,24 @@ __global__ void __launch_bounds__(1024) k_bn_finalize(const float* __restrict__ 
                               float* __restrict__ save_mean, float* __restrict__ save_invstd) {
   const int c = blockIdx.x * FIN_CPB + (threadIdx.x & (FIN_CPB - 1));
   const bool cok = c < C;
-  float mean = 0.f, invstd = 1.f;
+  BnCoef k;
   if (rows > 0) {
     double s[2];
     fin_reduce<2>(partial, rows, C, c, cok, s);
     if (threadIdx.x >= FIN_CPB || !cok) return;
-    double m = s[0] / count;
-    double var = s[1] / count - m * m;
-    if (var < 0.0) var = 0.0;
-    mean = (float)m;
-    invstd = (float)(1.0 / sqrt(var + (double)eps));
-    if (rmean) {
-      double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-      rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-      rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
-    }
+    const double var = bn_moments(s[0], s[1], count, eps, k);
+    if (rmean) bn_running_update(rmean, rvar, c, momentum, k.mean, var, count);
   } else {
     if (threadIdx.x >= FIN_CPB || !cok) return;
-    mean = rmean[c];
-    invstd = 1.0f / sqrtf(rvar[c] + eps);
+    k.mean = rmean[c];
+    k.invstd = 1.0f / sqrtf(rvar[c] + eps);
   }
-  float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-  scale[c] = g * invstd;
-  shift[c] = b - mean * g * invstd;
+  bn_affine(gamma, beta, c, k);
+  scale[c] = k.scale;
+  shift[c] = k.shift;
   if (save_mean) {
-    save_mean[c] = mean;
-    save_invstd[c] = invstd;
+    save_mean[c] = k.mean;
+    save_invstd[c] = k.invstd;
   }
 }
 
@@ -259,23 +256,81 @@ __device__ __forceinline__ Coef8 ldc8(const float* p, int c0, float dflt) {
   }
   return r;
 }
+// ... and a pair from offsets a, b of a table the workgroup derived in LDS (the accumulator protocol); the reads alternate
+// between the two and index the table itself: read row by row, or through two pointers, the f32 k_bn_fin_act_fwd<STATS>
+// takes 66 VGPRs instead of 64 and loses a wave
+__device__ __forceinline__ void ldc8_lds(const float* tab, int a, int b, Coef8& ra, Coef8& rb) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    ra.v[j] = tab[a + j];
+    rb.v[j] = tab[b + j];
+  }
+}
+// what every backward loop keeps per channel chunk: scale, shift, alpha (1 without PReLU), mean (0), invstd (1)
+struct BwdCoef {
+  Coef8 sc, sh, al, mu, is;
+};
+__device__ __forceinline__ BwdCoef bwd_coef(const float* scale, const float* shift, const float* alpha, const float* mean,
+                                            const float* invstd, int c0) {
+  BwdCoef k;
+  k.sc = ldc8(scale, c0, 1.f);
+  k.sh = ldc8(shift, c0, 0.f);
+  k.al = ldc8(alpha, c0, 1.f);
+  k.mu = ldc8(mean, c0, 0.f);
+  k.is = ldc8(invstd, c0, 1.f);
+  return k;
+}
+// a thread's place in a grid-stride element-wise launch: first chunk, stride and its loop-invariant channel chunk.
+// bdim: blockDim.x, read by the kernel itself (only there does the compiler fold it to the uniform-workgroup load)
+struct EwPos {
+  long tid, stride;
+  int c0;
+};
+__device__ __forceinline__ EwPos ew_pos(int C8, unsigned int bdim) {
+  EwPos p;
+  p.tid = blockIdx.x * (long)bdim + threadIdx.x;
+  p.stride = (long)gridDim.x * bdim;
+  p.c0 = (int)(p.tid % C8) * 8;
+  return p;
+}
 
-// STATS: also emit per-channel (sum, sumsq) partial rows of the (storage-rounded) OUTPUT, one row
-// pair per workgroup -- the statistics the next block's leading BatchNorm needs (the block output
-// is otherwise re-read by a k_bn_stats pass).  Needs C8 | 256.
+// threads t, t + C8, ... of the block share a channel chunk: fixed-order sum through LDS, k = cx, cx + C8, ..., of the
+// quantities q... (one float[8] each); emit(a, c, sum) receives NR >= sizeof...(q) rows per channel (the rows past the
+// quantities are zero).  Needs C8 | 256.
+template <int NR, typename E, typename... Q>
+__device__ __forceinline__ void chunk_fold(int C8, E emit, const Q&... q) {
+  constexpr int NQ = sizeof...(Q);
+  __shared__ float red[NQ][256][9];
+  const float* const qs[NQ] = {q...};
+  const int t = threadIdx.x, C = C8 * 8;
+#pragma unroll
+  for (int j = 0; j < 8; j++)
+#pragma unroll
+    for (int a = 0; a < NQ; a++) red[a][t][j] = qs[a][j];
+  __syncthreads();
+  for (int i = t; i < NR * C; i += 256) {
+    const int a = i / C, c = i % C, cx = c >> 3, j = c & 7;
+    float sum = 0.f;
+    if (NR == NQ || a < NQ)
+      for (int k = cx; k < 256; k += C8) sum += red[a][k][j];
+    emit(a, c, sum);
+  }
+}
+
+// The forward streaming loop of thread p, the (scale, shift) of its channel chunk in registers (the pointers carry no
+// __restrict__ here: the kernels' own parameters do).
+// STATS: also emit per-channel (sum, sumsq) of the (storage-rounded) OUTPUT, one row pair per workgroup (acc_mode: into
+// an accumulator, common.h) -- the statistics the next block's leading BatchNorm needs (the block output is otherwise
+// re-read by a k_bn_stats pass).  Needs C8 | 256.
 template <typename T, bool STATS>
-__global__ void __launch_bounds__(256) k_bn_act_fwd(const T* __restrict__ x, const float* __restrict__ scale,
-                                                    const float* __restrict__ shift,
-                                                    const float* __restrict__ alpha,
-                                                    const T* __restrict__ residual, int res_first,
-                                                    T* __restrict__ y, long n8, int C8, float* __restrict__ stats) {
-  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  const int c0 = (int)(tid % C8) * 8;
-  const Coef8 sc = ldc8(scale, c0, 1.f), sh = ldc8(shift, c0, 0.f), al = ldc8(alpha, c0, 1.f);
+__device__ __forceinline__ void bn_fwd_stream(const T* x, const Coef8 sc, const Coef8 sh, const float* alpha,
+                                              const T* residual, int res_first, T* y, long n8, int C8, const EwPos p,
+                                              float* stats, int acc_mode) {
+  const Coef8 al = ldc8(alpha, p.c0, 1.f);
   float q1[8], q2[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) q1[j] = q2[j] = 0.f;
-  for (long i = tid; i < n8; i += (long)gridDim.x * blockDim.x) {
+  for (long i = p.tid; i < n8; i += p.stride) {
     Vec8 v = load8<T>(x + i * 8);
     Vec8 r;
     if (residual) r = load8<T>(residual + i * 8);
@@ -297,23 +352,21 @@ __global__ void __launch_bounds__(256) k_bn_act_fwd(const T* __restrict__ x, con
       }
     }
   }
-  if (STATS) {
-    // threads t, t + C8, ... of the block share a channel chunk: fixed-order sum through LDS
-    __shared__ float red[2][256][9];
-    const int t = threadIdx.x, C = C8 * 8;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      red[0][t][j] = q1[j];
-      red[1][t][j] = q2[j];
-    }
-    __syncthreads();
-    for (int i = t; i < 2 * C; i += 256) {
-      const int which = i / C, c = i % C, cx = c >> 3, j = c & 7;
-      float sum = 0.f;
-      for (int k = cx; k < 256; k += C8) sum += red[which][k][j];
-      stats[((long)blockIdx.x * 2 + which) * C + c] = sum;
-    }
-  }
+  if (STATS)
+    chunk_fold<2>(C8, [&](int which, int c, float sum) {
+      stats_emit(stats, acc_mode, blockIdx.x, which, C8 * 8, c, sum);
+    }, q1, q2);
+}
+
+template <typename T, bool STATS>
+__global__ void __launch_bounds__(256) k_bn_act_fwd(const T* __restrict__ x, const float* __restrict__ scale,
+                                                    const float* __restrict__ shift,
+                                                    const float* __restrict__ alpha,
+                                                    const T* __restrict__ residual, int res_first,
+                                                    T* __restrict__ y, long n8, int C8, float* __restrict__ stats) {
+  const EwPos p = ew_pos(C8, blockDim.x);
+  const Coef8 sc = ldc8(scale, p.c0, 1.f), sh = ldc8(shift, p.c0, 0.f);
+  bn_fwd_stream<T, STATS>(x, sc, sh, alpha, residual, res_first, y, n8, C8, p, stats, 0);
 }
 
 static inline int ew_grid(long n8) {
@@ -393,77 +446,23 @@ __global__ void __launch_bounds__(256) k_bn_fin_act_fwd(const double* __restrict
       s += acc[(r * 2 + 0) * C + c];
       ss += acc[(r * 2 + 1) * C + c];
     }
-    const double m = s / count;
-    double var = ss / count - m * m;
-    if (var < 0.0) var = 0.0;
-    const float mean = (float)m;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-    const float sc = g * invstd, sh = b - mean * g * invstd;
-    cs[c] = sc;
-    cs[C + c] = sh;
+    BnCoef k;
+    const double var = bn_coef(s, ss, count, eps, gamma, beta, c, k);
+    cs[c] = k.scale;
+    cs[C + c] = k.shift;
     if (blockIdx.x == 0) {
-      scale[c] = sc;
-      shift[c] = sh;
-      save_mean[c] = mean;
-      save_invstd[c] = invstd;
-      if (rmean) {
-        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-        rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
-      }
+      scale[c] = k.scale;
+      shift[c] = k.shift;
+      save_mean[c] = k.mean;
+      save_invstd[c] = k.invstd;
+      if (rmean) bn_running_update(rmean, rvar, c, momentum, k.mean, var, count);
     }
   }
   __syncthreads();
-  const long tid = blockIdx.x * (long)blockDim.x + t;
-  const int c0 = (int)(tid % C8) * 8;
+  const EwPos p = ew_pos(C8, blockDim.x);
   Coef8 sc, sh;
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    sc.v[j] = cs[c0 + j];
-    sh.v[j] = cs[C + c0 + j];
-  }
-  const Coef8 al = ldc8(alpha, c0, 1.f);
-  float q1[8], q2[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) q1[j] = q2[j] = 0.f;
-  for (long i = tid; i < n8; i += (long)gridDim.x * blockDim.x) {
-    Vec8 v = load8<T>(x + i * 8);
-    Vec8 r;
-    if (residual) r = load8<T>(residual + i * 8);
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      float z = v.v[j] * sc.v[j] + sh.v[j];
-      if (residual && res_first) z += r.v[j];
-      if (alpha) z = z > 0.f ? z : z * al.v[j];
-      if (residual && !res_first) z += r.v[j];
-      v.v[j] = z;
-    }
-    store8<T>(y + i * 8, v);
-    if (STATS) {
-      const Vec8 vr = round8<T>(v);                    // what the consumer will read back
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        q1[j] += vr.v[j];
-        q2[j] += vr.v[j] * vr.v[j];
-      }
-    }
-  }
-  if (STATS) {
-    __shared__ float red[2][256][9];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      red[0][t][j] = q1[j];
-      red[1][t][j] = q2[j];
-    }
-    __syncthreads();
-    for (int i = t; i < 2 * C; i += 256) {
-      const int which = i / C, c = i % C, cx = c >> 3, j = c & 7;
-      float sum = 0.f;
-      for (int k = cx; k < 256; k += C8) sum += red[which][k][j];
-      stats_emit(reinterpret_cast<float*>(acc_out), 1, blockIdx.x, which, C, c, sum);
-    }
-  }
+  ldc8_lds(cs, p.c0, C + p.c0, sc, sh);
+  bn_fwd_stream<T, STATS>(x, sc, sh, alpha, residual, res_first, y, n8, C8, p, reinterpret_cast<float*>(acc_out), 1);
 }
 
 extern "C" int msml_bn_fin_act_fwd(const double* acc, double count, const float* gamma, const float* beta,
@@ -505,9 +504,7 @@ __global__ void __launch_bounds__(256) k_bn_bwd_reduce(const T* __restrict__ dy,
                                                        const float* __restrict__ invstd,
                                                        const T* __restrict__ res, long M, int C,
                                                        float* __restrict__ partial, int acc_mode) {
-  const int c0h = (threadIdx.x % (C / 8)) * 8;
-  const Coef8 sc = ldc8(scale, c0h, 1.f), sh = ldc8(shift, c0h, 0.f), al = ldc8(alpha, c0h, 1.f);
-  const Coef8 mu = ldc8(mean, c0h, 0.f), is = ldc8(invstd, c0h, 1.f);
+  const BwdCoef k = bwd_coef(scale, shift, alpha, mean, invstd, (threadIdx.x % (C / 8)) * 8);
   struct Px {
     Vec8 g, v, rr;
   };
@@ -523,18 +520,31 @@ __global__ void __launch_bounds__(256) k_bn_bwd_reduce(const T* __restrict__ dy,
     for (int j = 0; j < 8; j++) {
       float gg = g.v[j];
       if (alpha) {
-        float z = v.v[j] * sc.v[j] + sh.v[j];
+        float z = v.v[j] * k.sc.v[j] + k.sh.v[j];
         if (res) z += rr.v[j];
         if (z <= 0.f) {
           q[2][j] += gg * z;
-          gg *= al.v[j];
+          gg *= k.al.v[j];
         }
       }
-      float xh = (v.v[j] - mu.v[j]) * is.v[j];
+      float xh = (v.v[j] - k.mu.v[j]) * k.is.v[j];
       q[0][j] += gg;
       q[1][j] += gg * xh;
     }
   }, acc_mode);
+}
+
+// ... launched like k_bn_stats; acc_mode: partial is an accumulator double[MSML_ACC_ROWS][3][C] (common.h)
+template <typename DT>
+static void launch_bn_bwd_reduce(const void* dy, const void* x, const float* scale, const float* shift, const float* alpha,
+                                 const float* mean, const float* invstd, const void* res, long M, int C, float* partial,
+                                 int acc_mode, int rows, hipStream_t st) {
+  if (rows <= RED_PIPE_MAX_ROWS)
+    (k_bn_bwd_reduce<DT, true>)<<<rows, 256, red_lds(3, C), st>>>((const DT*)dy, (const DT*)x, scale, shift, alpha, mean,
+                                                                  invstd, (const DT*)res, M, C, partial, acc_mode);
+  else
+    (k_bn_bwd_reduce<DT, false>)<<<rows, 256, red_lds(3, C), st>>>((const DT*)dy, (const DT*)x, scale, shift, alpha, mean,
+                                                                   invstd, (const DT*)res, M, C, partial, acc_mode);
 }
 
 // Many partial rows (a fused conv epilogue writes one per workgroup: up to ~50k) are first folded
@@ -559,6 +569,14 @@ __global__ void __launch_bounds__(1024) k_fold_rows(const float* __restrict__ pa
   for (int q = 0; q < NQ; q++) out[((long)blockIdx.y * NQ + q) * C + c] = (float)s[q];
 }
 
+// the parameter gradients of channel c from its three backward sums (accumulate: added to what the buffers hold)
+__device__ __forceinline__ void bn_param_grads(float* dgamma, float* dbeta, float* dalpha, int accumulate, int c,
+                                               const double (&s)[3]) {
+  if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s[0];
+  if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)s[1];
+  if (dalpha) dalpha[c] = (accumulate ? dalpha[c] : 0.f) + (float)s[2];
+}
+
 __global__ void __launch_bounds__(1024) k_bn_bwd_finalize(const float* __restrict__ partial, int rows, int C, double count,
                                   float* __restrict__ dgamma, float* __restrict__ dbeta,
                                   float* __restrict__ dalpha, float* __restrict__ coef, int accumulate) {
@@ -567,46 +585,32 @@ __global__ void __launch_bounds__(1024) k_bn_bwd_finalize(const float* __restric
   double s[3];
   fin_reduce<3>(partial, rows, C, c, cok, s);
   if (threadIdx.x >= FIN_CPB || !cok) return;
-  if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s[0];
-  if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)s[1];
-  if (dalpha) dalpha[c] = (accumulate ? dalpha[c] : 0.f) + (float)s[2];
+  bn_param_grads(dgamma, dbeta, dalpha, accumulate, c, s);
   coef[c] = (float)(s[0] / count);
   coef[C + c] = (float)(s[1] / count);
 }
 
-// NEXT: the dx this kernel writes is the dy of ANOTHER BatchNorm without activation (the previous
+// The backward apply loop of thread p (coefficients k and k1 = s0 / n, k2 = s1 / n of its channel chunk in registers).
+// NEXT: the dx this loop writes is the dy of ANOTHER BatchNorm without activation (the previous
 // IBasicBlock's bn3, whose output was this BatchNorm's input); its backward sums
 // (sum dx, sum dx * xhat_n, 0) are accumulated here from the stored dx and that BatchNorm's saved
-// input nx -- one partial row [3][C] per workgroup, no separate reduce pass over dx.
-template <typename T, bool NEXT, bool ADD_S2 = false>
-__global__ void __launch_bounds__(256) k_bn_bwd_apply(const T* __restrict__ dy, const T* __restrict__ x,
-                                                      const float* __restrict__ scale,
-                                                      const float* __restrict__ shift,
-                                                      const float* __restrict__ alpha,
-                                                      const float* __restrict__ mean,
-                                                      const float* __restrict__ invstd,
-                                                      const float* __restrict__ coef,
-                                                      const T* __restrict__ res, const T* __restrict__ add,
-                                                      T* __restrict__ dx, T* __restrict__ dres, long n8,
-                                                      int C8, const T* __restrict__ nx,
-                                                      const float* __restrict__ nmean,
-                                                      const float* __restrict__ ninvstd,
-                                                      float* __restrict__ npartial, int aH, int aW) {
+// input nx -- no separate reduce pass over dx -- and go to nout: one partial row [3][C] per workgroup, or with ACC the
+// two sums into an accumulator (common.h).
+template <typename T, bool NEXT, bool ADD_S2, bool ACC>
+__device__ __forceinline__ void bn_bwd_stream(const T* dy, const T* x, const float* alpha, const BwdCoef& k, const Coef8& k1,
+                                              const Coef8& k2, const T* res, const T* add, T* dx, T* dres, long n8, int C8,
+                                              const EwPos p, const T* nx, const float* nmean, const float* ninvstd,
+                                              float* nout, int aH, int aW) {
   const int C = C8 * 8;
-  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  const int c0 = (int)(tid % C8) * 8;
-  const Coef8 sc = ldc8(scale, c0, 1.f), sh = ldc8(shift, c0, 0.f), al = ldc8(alpha, c0, 1.f);
-  const Coef8 mu = ldc8(mean, c0, 0.f), is = ldc8(invstd, c0, 1.f);
-  const Coef8 k1 = ldc8(coef, c0, 0.f), k2 = ldc8(coef + C, c0, 0.f);
   // ADD_S2: `add` is the COMPACT input gradient of a 1x1 / stride-2 conv, [N][ceil(H/2)][ceil(W/2)][C]:
   // it lands on the pixels with even y and x, the other three quarters of the dense gradient are zero
   const float rcpW = ADD_S2 ? 1.0f / (float)aW : 0.f, rcpH = ADD_S2 ? 1.0f / (float)aH : 0.f;
   const int aPw = (aW + 1) >> 1, aPh = (aH + 1) >> 1;
-  const Coef8 nmu = ldc8(NEXT ? nmean : nullptr, c0, 0.f), nis = ldc8(NEXT ? ninvstd : nullptr, c0, 1.f);
+  const Coef8 nmu = ldc8(NEXT ? nmean : nullptr, p.c0, 0.f), nis = ldc8(NEXT ? ninvstd : nullptr, p.c0, 1.f);
   float nq0[8], nq1[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) nq0[j] = nq1[j] = 0.f;
-  for (long i = tid; i < n8; i += (long)gridDim.x * blockDim.x) {
+  for (long i = p.tid; i < n8; i += p.stride) {
     Vec8 g = load8<T>(dy + i * 8);
     Vec8 v = load8<T>(x + i * 8);
     Vec8 rr, ad;
@@ -620,7 +624,7 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const T* __restrict__ dy, 
       int nn = (int)((float)row * rcpH), yy = row - nn * aH;
       if (yy < 0) { nn--; yy += aH; } else if (yy >= aH) { nn++; yy -= aH; }
       has_add = !((xx | yy) & 1);
-      if (has_add) ad = load8<T>(add + (((long)nn * aPh + (yy >> 1)) * aPw + (xx >> 1)) * C + c0);
+      if (has_add) ad = load8<T>(add + (((long)nn * aPh + (yy >> 1)) * aPw + (xx >> 1)) * C + p.c0);
     } else if (add) {
       ad = load8<T>(add + i * 8);
     }
@@ -628,13 +632,13 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const T* __restrict__ dy, 
     for (int j = 0; j < 8; j++) {
       float gg = g.v[j];
       if (alpha) {
-        float z = v.v[j] * sc.v[j] + sh.v[j];
+        float z = v.v[j] * k.sc.v[j] + k.sh.v[j];
         if (res) z += rr.v[j];
-        if (z <= 0.f) gg *= al.v[j];
+        if (z <= 0.f) gg *= k.al.v[j];
       }
-      float xh = (v.v[j] - mu.v[j]) * is.v[j];
+      float xh = (v.v[j] - k.mu.v[j]) * k.is.v[j];
       // scale[c] == gamma * invstd
-      v.v[j] = sc.v[j] * (gg - k1.v[j] - xh * k2.v[j]);
+      v.v[j] = k.sc.v[j] * (gg - k1.v[j] - xh * k2.v[j]);
       if (has_add) v.v[j] += ad.v[j];
       g.v[j] = gg;
     }
@@ -649,23 +653,29 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const T* __restrict__ dy, 
       }
     }
   }
-  if (NEXT) {
-    __shared__ float red[2][256][9];
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      red[0][t][j] = nq0[j];
-      red[1][t][j] = nq1[j];
-    }
-    __syncthreads();
-    for (int i = t; i < 3 * C; i += 256) {
-      const int q = i / C, c = i % C, cx = c >> 3, j = c & 7;
-      float sum = 0.f;
-      if (q < 2)
-        for (int k = cx; k < 256; k += C8) sum += red[q][k][j];
-      npartial[((long)blockIdx.x * 3 + q) * C + c] = sum;
-    }
-  }
+  if (NEXT)     // the row protocol's third row (the activation-free BatchNorm has no d alpha) is zero
+    chunk_fold<ACC ? 2 : 3>(C8, [&](int q, int c, float sum) { bnb_emit(nout, ACC, blockIdx.x, q, C, c, sum); }, nq0, nq1);
+}
+
+template <typename T, bool NEXT, bool ADD_S2 = false>
+__global__ void __launch_bounds__(256) k_bn_bwd_apply(const T* __restrict__ dy, const T* __restrict__ x,
+                                                      const float* __restrict__ scale,
+                                                      const float* __restrict__ shift,
+                                                      const float* __restrict__ alpha,
+                                                      const float* __restrict__ mean,
+                                                      const float* __restrict__ invstd,
+                                                      const float* __restrict__ coef,
+                                                      const T* __restrict__ res, const T* __restrict__ add,
+                                                      T* __restrict__ dx, T* __restrict__ dres, long n8,
+                                                      int C8, const T* __restrict__ nx,
+                                                      const float* __restrict__ nmean,
+                                                      const float* __restrict__ ninvstd,
+                                                      float* __restrict__ npartial, int aH, int aW) {
+  const EwPos p = ew_pos(C8, blockDim.x);
+  const BwdCoef k = bwd_coef(scale, shift, alpha, mean, invstd, p.c0);
+  const Coef8 k1 = ldc8(coef, p.c0, 0.f), k2 = ldc8(coef + C8 * 8, p.c0, 0.f);
+  bn_bwd_stream<T, NEXT, ADD_S2, false>(dy, x, alpha, k, k1, k2, res, add, dx, dres, n8, C8, p, nx, nmean, ninvstd, npartial,
+                                        aH, aW);
 }
 
 extern "C" int msml_bn_act_bwd(const void* dy, const void* x, const float* scale, const float* shift,
@@ -687,14 +697,7 @@ extern "C" int msml_bn_act_bwd(const void* dy, const void* x, const float* scale
   long n8 = M * (C / 8);
   MSML_DISPATCH_DTYPE(
       dtype, "bn_act_bwd",
-      if (rows <= RED_PIPE_MAX_ROWS)
-        (k_bn_bwd_reduce<DT, true>)<<<rows, 256, red_lds(3, C), st>>>((const DT*)dy, (const DT*)x, scale, shift, alpha,
-                                                                      save_mean, save_invstd,
-                                                                      (const DT*)residual_first, M, C, partial, 0);
-      else
-        (k_bn_bwd_reduce<DT, false>)<<<rows, 256, red_lds(3, C), st>>>((const DT*)dy, (const DT*)x, scale, shift, alpha,
-                                                                       save_mean, save_invstd,
-                                                                       (const DT*)residual_first, M, C, partial, 0);
+      launch_bn_bwd_reduce<DT>(dy, x, scale, shift, alpha, save_mean, save_invstd, residual_first, M, C, partial, 0, rows, st);
       MSML_LAUNCH_OK("bn_bwd_reduce");
       k_bn_bwd_finalize<<<cdiv(C, FIN_CPB), 1024, 0, st>>>(partial, rows, C, (double)M, dgamma, dbeta, dalpha, coef, accumulate);
       MSML_LAUNCH_OK("bn_bwd_finalize");
@@ -728,95 +731,28 @@ __global__ void __launch_bounds__(256) k_bn_fin_bwd_apply(const T* __restrict__ 
   const int C = C8 * 8, t = threadIdx.x;
   MSML_LDS_REGION(ck, 2 * C * 4);
   for (int c = t; c < C; c += 256) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    double s[3] = {0.0, 0.0, 0.0};
 #pragma unroll
-    for (int r = 0; r < MSML_ACC_ROWS; r++) {
-      s0 += acc[(r * 3 + 0) * C + c];
-      s1 += acc[(r * 3 + 1) * C + c];
-      s2 += acc[(r * 3 + 2) * C + c];
-    }
-    ck[c] = (float)(s0 / count);
-    ck[C + c] = (float)(s1 / count);
-    if (blockIdx.x == 0) {
-      if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s0;
-      if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)s1;
-      if (dalpha) dalpha[c] = (accumulate ? dalpha[c] : 0.f) + (float)s2;
-    }
+    for (int r = 0; r < MSML_ACC_ROWS; r++)
+#pragma unroll
+      for (int q = 0; q < 3; q++) s[q] += acc[(r * 3 + q) * C + c];
+    ck[c] = (float)(s[0] / count);
+    ck[C + c] = (float)(s[1] / count);
+    if (blockIdx.x == 0) bn_param_grads(dgamma, dbeta, dalpha, accumulate, c, s);
   }
   __syncthreads();
-  const long tid = blockIdx.x * (long)blockDim.x + t;
-  const int c0 = (int)(tid % C8) * 8;
-  const Coef8 sc = ldc8(scale, c0, 1.f), sh = ldc8(shift, c0, 0.f), al = ldc8(alpha, c0, 1.f);
-  const Coef8 mu = ldc8(mean, c0, 0.f), is = ldc8(invstd, c0, 1.f);
+  const EwPos p = ew_pos(C8, blockDim.x);
+  const BwdCoef k = bwd_coef(scale, shift, alpha, mean, invstd, p.c0);
   Coef8 k1, k2;
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    k1.v[j] = ck[c0 + j];
-    k2.v[j] = ck[C + c0 + j];
-  }
-  const float rcpW = ADD_S2 ? 1.0f / (float)aW : 0.f, rcpH = ADD_S2 ? 1.0f / (float)aH : 0.f;
-  const int aPw = (aW + 1) >> 1, aPh = (aH + 1) >> 1;
-  const Coef8 nmu = ldc8(NEXT ? nmean : nullptr, c0, 0.f), nis = ldc8(NEXT ? ninvstd : nullptr, c0, 1.f);
-  float nq0[8], nq1[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) nq0[j] = nq1[j] = 0.f;
-  for (long i = tid; i < n8; i += (long)gridDim.x * blockDim.x) {
-    Vec8 g = load8<T>(dy + i * 8);
-    Vec8 v = load8<T>(x + i * 8);
-    Vec8 rr, ad;
-    if (res) rr = load8<T>(res + i * 8);
-    bool has_add = add != nullptr;
-    if (ADD_S2) {
-      const int pix = (int)(i / C8);
-      int row = (int)((float)pix * rcpW), xx = pix - row * aW;
-      if (xx < 0) { row--; xx += aW; } else if (xx >= aW) { row++; xx -= aW; }
-      int nn = (int)((float)row * rcpH), yy = row - nn * aH;
-      if (yy < 0) { nn--; yy += aH; } else if (yy >= aH) { nn++; yy -= aH; }
-      has_add = !((xx | yy) & 1);
-      if (has_add) ad = load8<T>(add + (((long)nn * aPh + (yy >> 1)) * aPw + (xx >> 1)) * C + c0);
-    } else if (add) {
-      ad = load8<T>(add + i * 8);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      float gg = g.v[j];
-      if (alpha) {
-        float z = v.v[j] * sc.v[j] + sh.v[j];
-        if (res) z += rr.v[j];
-        if (z <= 0.f) gg *= al.v[j];
-      }
-      float xh = (v.v[j] - mu.v[j]) * is.v[j];
-      v.v[j] = sc.v[j] * (gg - k1.v[j] - xh * k2.v[j]);
-      if (has_add) v.v[j] += ad.v[j];
-      g.v[j] = gg;
-    }
-    store8<T>(dx + i * 8, v);
-    if (dres) store8<T>(dres + i * 8, g);
-    if (NEXT) {
-      const Vec8 o = round8<T>(v), xn = load8<T>(nx + i * 8);
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        const float gn = o.v[j];
-        nq0[j] += gn;
-        nq1[j] += gn * ((xn.v[j] - nmu.v[j]) * nis.v[j]);
-      }
-    }
-  }
-  if (NEXT) {
-    __shared__ float red[2][256][9];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      red[0][t][j] = nq0[j];
-      red[1][t][j] = nq1[j];
-    }
-    __syncthreads();
-    for (int i = t; i < 2 * C; i += 256) {
-      const int q = i / C, c = i % C, cx = c >> 3, j = c & 7;
-      float sum = 0.f;
-      for (int k = cx; k < 256; k += C8) sum += red[q][k][j];
-      bnb_emit(reinterpret_cast<float*>(nacc), 1, blockIdx.x, q, C, c, sum);
-    }
-  }
+  ldc8_lds(ck, p.c0, C + p.c0, k1, k2);
+  bn_bwd_stream<T, NEXT, ADD_S2, true>(dy, x, alpha, k, k1, k2, res, add, dx, dres, n8, C8, p, nx, nmean, ninvstd,
+                                       reinterpret_cast<float*>(nacc), aH, aW);
+}
+
+// A stride-2 `add` (add_h > 0: the compact gradient of a 1x1 / stride-2 conv over add_h x add_w maps) needs whole maps and
+// M below 2^24: the kernels decode the pixel with float reciprocals.
+static inline bool s2_add_ok(const void* add, int add_h, int add_w, long M) {
+  return add_h <= 0 || (add && add_w > 0 && M % ((long)add_h * add_w) == 0 && M < (1L << 24));
 }
 
 // residual_first / dres: the PReLU-after-the-sum form of msml_bn_act_bwd (res_first blocks); add / add_h / add_w, next_*:
@@ -831,7 +767,7 @@ extern "C" int msml_bn_fin_bwd_apply(const void* dy, const void* x, const float*
              MSML_ERR_SHAPE, "bn_fin_bwd_apply: bad args M=%ld C=%d", M, C);
   MSML_CHECK(256 % (C / 8) == 0, MSML_ERR_UNSUPPORTED, "bn_fin_bwd_apply: C/8 = %d must divide 256", C / 8);
   const bool s2 = add_h > 0;
-  MSML_CHECK(!s2 || (add && add_w > 0 && M % ((long)add_h * add_w) == 0 && M < (1L << 24)), MSML_ERR_SHAPE,
+  MSML_CHECK(s2_add_ok(add, add_h, add_w, M), MSML_ERR_SHAPE,
              "bn_fin_bwd_apply: stride-2 add needs M = N*H*W < 2^24 (M=%ld H=%d W=%d)", M, add_h, add_w);
   MSML_CHECK(!next_acc || (next_x && next_mean && next_invstd), MSML_ERR_SHAPE, "bn_fin_bwd_apply: next_* incomplete");
   hipStream_t st = (hipStream_t)stream;
@@ -863,16 +799,9 @@ extern "C" int msml_bn_act_bwd_acc(const void* dy, const void* x, const float* s
   MSML_CHECK(256 % (C / 8) == 0, MSML_ERR_UNSUPPORTED, "bn_act_bwd_acc: C/8 = %d must divide 256", C / 8);
   const int rows = red_rows(M, C);
   hipStream_t st = (hipStream_t)stream;
-  MSML_DISPATCH_DTYPE(
-      dtype, "bn_act_bwd_acc",
-      if (rows <= RED_PIPE_MAX_ROWS)
-        (k_bn_bwd_reduce<DT, true>)<<<rows, 256, red_lds(3, C), st>>>((const DT*)dy, (const DT*)x, scale, shift, alpha,
-                                                                      save_mean, save_invstd, (const DT*)residual_first,
-                                                                      M, C, reinterpret_cast<float*>(acc), 1);
-      else
-        (k_bn_bwd_reduce<DT, false>)<<<rows, 256, red_lds(3, C), st>>>((const DT*)dy, (const DT*)x, scale, shift, alpha,
-                                                                       save_mean, save_invstd, (const DT*)residual_first,
-                                                                       M, C, reinterpret_cast<float*>(acc), 1);)
+  MSML_DISPATCH_DTYPE(dtype, "bn_act_bwd_acc",
+                      launch_bn_bwd_reduce<DT>(dy, x, scale, shift, alpha, save_mean, save_invstd, residual_first, M, C,
+                                               reinterpret_cast<float*>(acc), 1, rows, st);)
   MSML_LAUNCH_OK("bn_bwd_reduce(acc)");
   return msml_bn_fin_bwd_apply(dy, x, scale, shift, alpha, save_mean, save_invstd, acc, residual_first, add, 0, 0,
                                dx, dres, dgamma, dbeta, dalpha, accumulate, M, C, nullptr, nullptr, nullptr, nullptr,
@@ -893,7 +822,7 @@ static int bn_bwd_apply_impl(const void* dy, const void* x, const float* scale, 
              MSML_ERR_SHAPE, "bn_act_bwd_apply: bad args M=%ld C=%d rows=%d", M, C, rows);
   MSML_CHECK(256 % (C / 8) == 0, MSML_ERR_UNSUPPORTED, "bn_act_bwd_apply: C/8 = %d must divide 256", C / 8);
   const bool s2 = add_h > 0;
-  MSML_CHECK(!s2 || (add && add_w > 0 && M % ((long)add_h * add_w) == 0 && M < (1L << 24)), MSML_ERR_SHAPE,
+  MSML_CHECK(s2_add_ok(add, add_h, add_w, M), MSML_ERR_SHAPE,
              "bn_act_bwd_apply: stride-2 add needs M = N*H*W < 2^24 (M=%ld H=%d W=%d)", M, add_h, add_w);
   hipStream_t st = (hipStream_t)stream;
   long n8 = M * (C / 8);
@@ -1016,11 +945,7 @@ extern "C" int msml_bias_grad(const void* dy, long M, int Cp, int Creal, float* 
   int rows = red_rows(M, Cp);
   MSML_CHECK(ws_floats >= (long)rows * 2 * Cp, MSML_ERR_WORKSPACE, "bias_grad: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  MSML_DISPATCH_DTYPE(dtype, "bias_grad",
-                      if (rows <= RED_PIPE_MAX_ROWS)
-                        (k_bn_stats<DT, true>)<<<rows, 256, red_lds(2, Cp), st>>>((const DT*)dy, M, Cp, workspace, 0);
-                      else
-                        (k_bn_stats<DT, false>)<<<rows, 256, red_lds(2, Cp), st>>>((const DT*)dy, M, Cp, workspace, 0);)
+  MSML_DISPATCH_DTYPE(dtype, "bias_grad", launch_bn_stats<DT>(dy, M, Cp, workspace, 0, rows, st);)
   MSML_LAUNCH_OK("bias_grad");
   k_colsum_finalize<<<cdiv(Creal, 32), 1024, 0, st>>>(workspace, rows, Cp, 2, db, Creal, accumulate);
   MSML_LAUNCH_OK("bias_grad_finalize");
@@ -1069,14 +994,12 @@ __global__ void __launch_bounds__(256) k_bn_eval_bwd(const T* __restrict__ dy, c
                                                      const T* __restrict__ res, T* __restrict__ dx,
                                                      T* __restrict__ dres, long n8, int C8,
                                                      float* __restrict__ partial) {
-  const long tid = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  const int c0 = (int)(tid % C8) * 8;
-  const Coef8 sc = ldc8(scale, c0, 1.f), sh = ldc8(shift, c0, 0.f), al = ldc8(alpha, c0, 1.f);
-  const Coef8 mu = ldc8(SUMS ? mean : nullptr, c0, 0.f), is = ldc8(SUMS ? invstd : nullptr, c0, 1.f);
+  const EwPos p = ew_pos(C8, blockDim.x);
+  const BwdCoef k = bwd_coef(scale, shift, alpha, SUMS ? mean : nullptr, SUMS ? invstd : nullptr, p.c0);
   float q0[8], q1[8], q2[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) q0[j] = q1[j] = q2[j] = 0.f;
-  for (long i = tid; i < n8; i += (long)gridDim.x * blockDim.x) {
+  for (long i = p.tid; i < n8; i += p.stride) {
     Vec8 g = load8<T>(dy + i * 8);
     Vec8 v = load8<T>(x + i * 8);
     Vec8 rr;
@@ -1085,41 +1008,25 @@ __global__ void __launch_bounds__(256) k_bn_eval_bwd(const T* __restrict__ dy, c
     for (int j = 0; j < 8; j++) {
       float gg = g.v[j];
       if (alpha) {
-        float z = v.v[j] * sc.v[j] + sh.v[j];
+        float z = v.v[j] * k.sc.v[j] + k.sh.v[j];
         if (res) z += rr.v[j];
         if (z <= 0.f) {
           if (SUMS) q2[j] += gg * z;
-          gg *= al.v[j];
+          gg *= k.al.v[j];
         }
       }
       if (SUMS) {
         q0[j] += gg;
-        q1[j] += gg * ((v.v[j] - mu.v[j]) * is.v[j]);
+        q1[j] += gg * ((v.v[j] - k.mu.v[j]) * k.is.v[j]);
       }
-      v.v[j] = sc.v[j] * gg;
+      v.v[j] = k.sc.v[j] * gg;
       g.v[j] = gg;
     }
     store8<T>(dx + i * 8, v);
     if (dres) store8<T>(dres + i * 8, g);
   }
-  if (SUMS) {
-    // threads t, t + C8, ... of the block share a channel chunk: fixed-order sum through LDS
-    __shared__ float red[3][256][9];
-    const int t = threadIdx.x, C = C8 * 8;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      red[0][t][j] = q0[j];
-      red[1][t][j] = q1[j];
-      red[2][t][j] = q2[j];
-    }
-    __syncthreads();
-    for (int i = t; i < 3 * C; i += 256) {
-      const int q = i / C, c = i % C, cx = c >> 3, j = c & 7;
-      float sum = 0.f;
-      for (int k = cx; k < 256; k += C8) sum += red[q][k][j];
-      partial[((long)blockIdx.x * 3 + q) * C + c] = sum;
-    }
-  }
+  if (SUMS)
+    chunk_fold<3>(C8, [&](int q, int c, float sum) { bnb_emit(partial, 0, blockIdx.x, q, C8 * 8, c, sum); }, q0, q1, q2);
 }
 
 __global__ void __launch_bounds__(1024) k_bn_eval_bwd_finalize(const float* __restrict__ partial, int rows, int C,
@@ -1130,9 +1037,7 @@ __global__ void __launch_bounds__(1024) k_bn_eval_bwd_finalize(const float* __re
   double s[3];
   fin_reduce<3>(partial, rows, C, c, cok, s);
   if (threadIdx.x >= FIN_CPB || !cok) return;
-  if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s[0];
-  if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)s[1];
-  if (dalpha) dalpha[c] = (accumulate ? dalpha[c] : 0.f) + (float)s[2];
+  bn_param_grads(dgamma, dbeta, dalpha, accumulate, c, s);
 }
 
 extern "C" int msml_bn_eval_act_bwd_rows(long M, int C) {

@@ -237,7 +237,7 @@ struct BnIn {
   const float* shift;
   const float* alpha;      // nullptr: no PReLU
   // Accumulator mode (acc != nullptr, conv_halo.hip only): the coefficients are DERIVED in the kernel's prologue from the
-  // producer's f64 sums double[MSML_ACC_ROWS][2][C] exactly as k_bn_fin_act_fwd derives them (bn.hip), workgroup (0, 0)
+  // producer's f64 sums double[MSML_ACC_ROWS][2][C] by the bn_coef that k_bn_fin_act_fwd calls (bn.hip), workgroup (0, 0)
   // writes coef_out = float[4][C] (scale, shift, mean, invstd) and updates the running statistics, and the normalised
   // image is also WRITTEN OUT (store, same NHWC shape as the input: the weight gradient reads it) -- the BatchNorm apply
   // launch in front of the conv disappears.
@@ -251,6 +251,38 @@ struct BnIn {
   float* coef_out = nullptr;
   unsigned short* store = nullptr;
 };
+// The one training-mode coefficient rule (k_bn_finalize, k_bn_fin_act_fwd in bn.hip, bn_in_fill_acc below).
+// bn_moments: the f64 sums (s, ss) of `count` values of a channel -> mean, invstd; returns the biased variance for
+// bn_running_update.  bn_affine: scale = gamma * invstd, shift = beta - mean * gamma * invstd.  bn_coef: both.
+struct BnCoef {
+  float mean, invstd, scale, shift;
+};
+__device__ __forceinline__ double bn_moments(double s, double ss, double count, float eps, BnCoef& k) {
+  const double m = s / count;
+  double var = ss / count - m * m;
+  if (var < 0.0) var = 0.0;
+  k.mean = (float)m;
+  k.invstd = (float)(1.0 / sqrt(var + (double)eps));
+  return var;
+}
+__device__ __forceinline__ void bn_affine(const float* gamma, const float* beta, int c, BnCoef& k) {
+  const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
+  k.scale = g * k.invstd;
+  k.shift = b - k.mean * g * k.invstd;
+}
+__device__ __forceinline__ double bn_coef(double s, double ss, double count, float eps, const float* gamma,
+                                          const float* beta, int c, BnCoef& k) {
+  const double var = bn_moments(s, ss, count, eps, k);
+  bn_affine(gamma, beta, c, k);
+  return var;
+}
+// running statistics exactly like nn.BatchNorm: momentum, unbiased variance (count == 1 keeps the biased one)
+__device__ __forceinline__ void bn_running_update(float* rmean, float* rvar, int c, float momentum, float mean, double var,
+                                                  double count) {
+  const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+  rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
+  rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
+}
 // tab: LDS table [3][C] (scale, shift, alpha) filled by bn_in_fill
 __device__ __forceinline__ void bn_in_fill(const BnIn& f, float* tab, int c0, int C, int t, int nt) {
   for (int i = t; i < C; i += nt) {
@@ -259,8 +291,9 @@ __device__ __forceinline__ void bn_in_fill(const BnIn& f, float* tab, int c0, in
     tab[2 * C + i] = f.alpha ? f.alpha[c0 + i] : 1.f;
   }
 }
-// Accumulator mode: the table from the producer's f64 sums (the arithmetic of k_bn_fin_act_fwd's prologue, bn.hip --
-// bit-identical coefficients); `writer` (one workgroup of the launch) also stores them and updates the running statistics.
+// Accumulator mode: the table from the producer's f64 sums by the fold and the bn_coef that k_bn_fin_act_fwd's prologue
+// runs (bn.hip): the same coefficients; `writer` (one workgroup of the launch) also stores them and updates the running
+// statistics.
 __device__ __forceinline__ void bn_in_fill_acc(const BnIn& f, float* tab, int C, int t, int nt, bool writer) {
   for (int c = t; c < C; c += nt) {
     double s = 0.0, ss = 0.0;
@@ -269,26 +302,17 @@ __device__ __forceinline__ void bn_in_fill_acc(const BnIn& f, float* tab, int C,
       s += f.acc[(r * 2 + 0) * C + c];
       ss += f.acc[(r * 2 + 1) * C + c];
     }
-    const double m = s / f.count;
-    double var = ss / f.count - m * m;
-    if (var < 0.0) var = 0.0;
-    const float mean = (float)m;
-    const float invstd = (float)(1.0 / sqrt(var + (double)f.eps));
-    const float g = f.gamma ? f.gamma[c] : 1.f, b = f.beta ? f.beta[c] : 0.f;
-    const float sc = g * invstd, sh = b - mean * g * invstd;
-    tab[c] = sc;
-    tab[C + c] = sh;
+    BnCoef k;
+    const double var = bn_coef(s, ss, f.count, f.eps, f.gamma, f.beta, c, k);
+    tab[c] = k.scale;
+    tab[C + c] = k.shift;
     tab[2 * C + c] = f.alpha ? f.alpha[c] : 1.f;
     if (writer) {
-      f.coef_out[c] = sc;
-      f.coef_out[C + c] = sh;
-      f.coef_out[2 * C + c] = mean;
-      f.coef_out[3 * C + c] = invstd;
-      if (f.rmean) {
-        const double unbiased = f.count > 1.0 ? var * f.count / (f.count - 1.0) : var;
-        f.rmean[c] = (1.f - f.momentum) * f.rmean[c] + f.momentum * mean;
-        f.rvar[c] = (1.f - f.momentum) * f.rvar[c] + f.momentum * (float)unbiased;
-      }
+      f.coef_out[c] = k.scale;
+      f.coef_out[C + c] = k.shift;
+      f.coef_out[2 * C + c] = k.mean;
+      f.coef_out[3 * C + c] = k.invstd;
+      if (f.rmean) bn_running_update(f.rmean, f.rvar, c, f.momentum, k.mean, var, f.count);
     }
   }
 }

@@ -251,11 +251,7 @@ class _BnAct(torch.autograd.Function):
             with ops.PROFILE.rec("bn_act_fwd", 0.0, x.numel() * x.element_size() * (3 if residual is not None else 2)):
                 call("msml_bn_fin_act_fwd", stats, float(m), gamma, beta, rmean, rvar, momentum, eps, coef[0], coef[1],
                      coef[2], coef[3], x, alpha, residual, int(res_first), y, m, c, yacc, dtype)
-            ctx.training = training
-            ctx.has = (gamma is not None, beta is not None, alpha is not None, residual is not None)
-            ctx.res_first = bool(res_first) and residual is not None and alpha is not None
-            ctx.params = (gamma, beta, alpha)
-            ctx.save_for_backward(x, coef, alpha, residual if ctx.res_first else None)
+            _BnAct._save(ctx, training, x, coef, gamma, beta, alpha, residual, res_first)
             if emit:
                 ctx.mark_non_differentiable(yacc)
                 return y, yacc
@@ -274,12 +270,39 @@ class _BnAct(torch.autograd.Function):
         y = torch.empty_like(x)
         with ops.PROFILE.rec("bn_act_fwd", 0.0, x.numel() * x.element_size() * (3 if residual is not None else 2)):
             call("msml_bn_act_fwd", x, coef[0], coef[1], alpha, residual, int(res_first), y, m, c, dtype)
+        _BnAct._save(ctx, training, x, coef, gamma, beta, alpha, residual, res_first)
+        return y
+
+    @staticmethod
+    def _save(ctx, training, x, coef, gamma, beta, alpha, residual, res_first):
         ctx.training = training
         ctx.has = (gamma is not None, beta is not None, alpha is not None, residual is not None)
         ctx.res_first = bool(res_first) and residual is not None and alpha is not None
         ctx.params = (gamma, beta, alpha)
         ctx.save_for_backward(x, coef, alpha, residual if ctx.res_first else None)
-        return y
+
+    @staticmethod
+    def _wanted(ctx):
+        """(want, inplace, tg): which of (dgamma, dbeta, dalpha) the graph asks for; inplace: every wanted one goes straight
+        into the flat arena (FlatSGD owns the .grad views), and tg holds those views (None otherwise)."""
+        has_g, has_b, has_a, _ = ctx.has
+        want = (has_g and ctx.needs_input_grad[2], has_b and ctx.needs_input_grad[3],
+                has_a and ctx.needs_input_grad[4])
+        inplace = all((not w) or ops.inplace(prm) for w, prm in zip(want, ctx.params))
+        return want, inplace, [prm.grad if w else None for w, prm in zip(want, ctx.params)] if inplace else None
+
+    @staticmethod
+    def _grads(ctx, want, inplace, pg, dx, dy, dres):
+        """The 13 gradients of forward()'s arguments; pg: the [3][c] buffer of the gradients that did not go in place."""
+        if ctx.res_first:
+            dy = dres
+        if inplace:
+            ops.grad_ready(*[prm for w, prm in zip(want, ctx.params) if w])
+        return (dx, None,
+                pg[0] if want[0] and not inplace else None,
+                pg[1] if want[1] and not inplace else None,
+                pg[2] if want[2] and not inplace else None,
+                dy if ctx.has[3] else None, None, None, None, None, None, None, None)
 
     @staticmethod
     def backward(ctx, dy, *_dacc):
@@ -296,15 +319,8 @@ class _BnAct(torch.autograd.Function):
         need = (rows * 3 * c + 2 * c) * 4
         ws = ops.workspace(need, x.device)
         dres = torch.empty_like(x) if ctx.res_first else None
-        has_g, has_b, has_a, has_r = ctx.has
-        gamma, beta, alpha_p = ctx.params
-        want = (has_g and ctx.needs_input_grad[2], has_b and ctx.needs_input_grad[3],
-                has_a and ctx.needs_input_grad[4])
-        # parameter gradients go straight into the flat arena when FlatSGD owns the .grad views
-        inplace = all((not w) or ops.inplace(prm) for w, prm in zip(want, (gamma, beta, alpha_p)))
-        if inplace:
-            tg = [prm.grad if w else None for w, prm in zip(want, (gamma, beta, alpha_p))]
-        else:
+        want, inplace, tg = _BnAct._wanted(ctx)
+        if not inplace:
             tg = [pg[0], pg[1], pg[2] if alpha is not None else None]
         with ops.PROFILE.rec("bn_act_bwd", 0.0, x.numel() * x.element_size() * (5 + (3 if ctx.res_first else 0))):
             if ops.acc_applies(c, dtype):
@@ -313,15 +329,7 @@ class _BnAct(torch.autograd.Function):
             else:
                 call("msml_bn_act_bwd", dy, x, coef[0], coef[1], alpha, coef[2], coef[3], res, dx, dres,
                      tg[0], tg[1], tg[2], int(inplace), m, c, ws, ws.numel() // 4, dtype)
-        if ctx.res_first:
-            dy = dres
-        if inplace:
-            ops.grad_ready(*[prm for w, prm in zip(want, (gamma, beta, alpha_p)) if w])
-        return (dx, None,
-                pg[0] if want[0] and not inplace else None,
-                pg[1] if want[1] and not inplace else None,
-                pg[2] if want[2] and not inplace else None,
-                dy if has_r else None, None, None, None, None, None, None, None)
+        return _BnAct._grads(ctx, want, inplace, pg, dx, dy, dres)
 
     @staticmethod
     def _backward_eval(ctx, dy, x, coef, alpha, res):
@@ -334,34 +342,18 @@ class _BnAct(torch.autograd.Function):
         dy = dy.contiguous()
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if ctx.res_first else None
-        has_g, has_b, has_a, has_r = ctx.has
-        params = ctx.params
-        want = (has_g and ctx.needs_input_grad[2], has_b and ctx.needs_input_grad[3],
-                has_a and ctx.needs_input_grad[4])
-        # parameter gradients go straight into the flat arena when FlatSGD owns the .grad views
-        inplace = any(want) and all((not w) or ops.inplace(prm) for w, prm in zip(want, params))
+        want, inplace, tg = _BnAct._wanted(ctx)
+        inplace = any(want) and inplace          # nothing wanted: tg is three Nones, nothing accumulates
         pg, ws = None, None
-        if inplace:
-            tg = [prm.grad if w else None for w, prm in zip(want, params)]
-        elif any(want):
+        if any(want) and not inplace:
             pg = torch.empty(3, c, dtype=torch.float32, device=x.device)
             tg = [pg[i] if w else None for i, w in enumerate(want)]
-        else:
-            tg = [None, None, None]
         if any(want):
             ws = ops.workspace(_lib.value("msml_bn_eval_act_bwd_rows", m, c) * 3 * c * 4, x.device)
         with ops.PROFILE.rec("bn_eval_act_bwd", 0.0, x.numel() * x.element_size() * (3 + (2 if ctx.res_first else 0))):
             call("msml_bn_eval_act_bwd", dy, x, coef[0], coef[1], alpha, coef[2], coef[3], res, dx, dres,
                  tg[0], tg[1], tg[2], int(inplace), m, c, ws, ws.numel() // 4 if ws is not None else 0, dtype)
-        if ctx.res_first:
-            dy = dres
-        if inplace:
-            ops.grad_ready(*[prm for w, prm in zip(want, params) if w])
-        return (dx, None,
-                pg[0] if want[0] and not inplace else None,
-                pg[1] if want[1] and not inplace else None,
-                pg[2] if want[2] and not inplace else None,
-                dy if has_r else None, None, None, None, None, None, None, None)
+        return _BnAct._grads(ctx, want, inplace, pg, dx, dy, dres)
 
 
 def bn_act(x, stats, bn, prelu=None, residual=None, res_first=False, emit_stats=False):

@@ -257,7 +257,9 @@ def test_add():
 
 def test_two_runs_bit_identical_and_protocols_agree():
     """Row-protocol entry points are deterministic; the accumulator protocol's f64 totals equal the fixed-order f64 total
-    of the row protocol exactly (docs/KERNELS.md: an f64 sum of f32 partials is exact, hence order-free)."""
+    of the row protocol exactly (docs/KERNELS.md: an f64 sum of f32 partials is exact, hence order-free).  From equal
+    totals the two protocols run the same device functions (bn_coef, bn_fwd_stream, bn_bwd_stream: csrc/bn.hip,
+    csrc/common.h), so coefficients, running statistics, y, dx and dres are the same bits too."""
     for c in [c for c in B.case_table("apply") if c.tag in ("row+1", "rows512", "rows513", "capped", "offset30")] + \
             B.case_table("big")[:2]:
         d = B.draw(c, "cuda")
@@ -268,18 +270,27 @@ def test_two_runs_bit_identical_and_protocols_agree():
         acc = be.stat_acc(x)
         assert torch.equal(acc.sum(0), p1.double().sum(0)), "bn_stats_acc total != row total: %s" % c.name
         eps, mom = B.f32(B.EPS), B.f32(0.1)
-        sc, sh, mean, inv = be.bn_train(x, d["gamma"], d["beta"], d["rmean0"].clone(), d["rvar0"].clone(), mom, eps)
+        rm1, rv1 = d["rmean0"].clone(), d["rvar0"].clone()
+        sc, sh, mean, inv = be.bn_train(x, d["gamma"], d["beta"], rm1, rv1, mom, eps)
         rf = int(c.res_first and c.residual)
         (y1, e1), (y2, e2) = (be.act_fwd(x, sc, sh, d["alpha"], d["res"], rf, emit=True) for _ in range(2))
         assert torch.equal(y1.view(torch.uint8), y2.view(torch.uint8)) and torch.equal(e1[0], e2[0]) and torch.equal(e1[1], e2[1])
-        _, _, ea = be.fin_act_fwd(x, d["gamma"], d["beta"], d["rmean0"].clone(), d["rvar0"].clone(), mom, eps, d["alpha"],
-                                  d["res"], rf, True)
+        rm2, rv2 = d["rmean0"].clone(), d["rvar0"].clone()
+        coef2, ya, ea = be.fin_act_fwd(x, d["gamma"], d["beta"], rm2, rv2, mom, eps, d["alpha"], d["res"], rf, True)
+        # one coefficient rule (bn_coef / bn_running_update, common.h) on the same exact f64 totals, one forward loop
+        for nm, a, b in zip(("scale", "shift", "mean", "invstd", "running_mean", "running_var"),
+                            (sc, sh, mean, inv, rm1, rv1), tuple(coef2) + (rm2, rv2)):
+            assert _same(a, b), "msml_bn_finalize and msml_bn_fin_act_fwd differ in %s: %s" % (nm, c.name)
+        assert _same(y1, ya), "msml_bn_act_fwd and msml_bn_fin_act_fwd differ in y: %s" % c.name
         outs = []
         for proto in ("rows", "rows", "acc"):
             grads = [torch.zeros(C, device="cuda") for _ in range(3)]
             dx, dres = be.act_bwd(d["dy"], x, sc, sh, d["alpha"], mean, inv, d["res"] if rf else None, grads, 0, proto=proto)
-            outs.append((dx, grads))
+            outs.append((dx, grads, dres))
         assert torch.equal(outs[0][0].view(torch.uint8), outs[1][0].view(torch.uint8))
+        # one backward apply loop, k1 / k2 from the same exact totals
+        assert _same(outs[0][0], outs[2][0]), "msml_bn_act_bwd and msml_bn_act_bwd_acc differ in dx: %s" % c.name
+        assert _same(outs[0][2], outs[2][2]), "msml_bn_act_bwd and msml_bn_act_bwd_acc differ in dres: %s" % c.name
         for a, b in zip(outs[0][1], outs[1][1]):
             assert torch.equal(a, b)
         # same reduce kernel, exact f64 totals: the parameter gradients of the two protocols are the same f32 numbers
