@@ -191,6 +191,17 @@ int msml_conv_wgrad_group(const void* const* u, const void* const* v, float* con
 int msml_conv_wgrad_kernel_is_n32(int up, int vp, int N, int H, int W, int P, int Q, int R, int S, int stride,
                                   int pad_h, int pad_w);
 
+/* How a weight-gradient call of this shape would run (tests, profiling labels): the decision of msml_conv_wgrad
+ * (group 1), msml_conv_wgrad_group (group > 1: the consecutive IBasicBlocks of backbones/frb/iresnet.py:40-67) or
+ * msml_conv_wgrad_bnin (bnin != 0), and the status that entry point returns before it launches, given valid pointers, a
+ * 16-byte aligned dw and enough workspace.  plan[8] = family (0 none, 1 fc, 2 narrow-operand, 3 line, 4 strip / halo,
+ * 5 im2col, 6 generic), variant (strip / halo: 64- or 128-row tiles, 7 = image-pair strips), tile rows, tile columns,
+ * taps per workgroup (im2col / generic), split-K slabs per layer, pixels per split (im2col / generic), 1 when the tiles go
+ * straight into dw.  *slab_bytes: what the launch writes into the workspace (0: nothing).  A pure shape query: no GPU. */
+int msml_conv_wgrad_plan(int up, int vp, int A, int Breal, int Btot, int boff, int N, int H, int W, int P, int Q, int R,
+                         int S, int stride, int pad_h, int pad_w, int dtype, int group, int bnin, int* plan,
+                         long* slab_bytes);
+
 /* ---------------------------------------------------------------- BatchNorm / PReLU --------
  * nn.BatchNorm2d(eps=1e-5, momentum=0.1) + nn.PReLU + residual of IBasicBlock
  * (backbones/frb/iresnet.py:56-67, backbones/osb/unet.py:80-91), resblock_bottle

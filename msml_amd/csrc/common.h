@@ -40,14 +40,16 @@ void msml_set_error(const char* fmt, ...);
   } while (0)
 
 // call after every launch: reports launch-configuration errors without synchronising
-#define MSML_LAUNCH_OK(name)                                                     \
-  do {                                                                           \
-    hipError_t e_ = hipGetLastError();                                           \
-    if (e_ != hipSuccess) {                                                      \
-      msml_set_error("%s: launch failed: %s", name, hipGetErrorString(e_));      \
-      return MSML_ERR_LAUNCH;                                                    \
-    }                                                                            \
+// (MSML_LAUNCH_OK2: the label in two parts, put together only when the launch failed)
+#define MSML_LAUNCH_OK2(who, what)                                                         \
+  do {                                                                                     \
+    hipError_t e_ = hipGetLastError();                                                     \
+    if (e_ != hipSuccess) {                                                                \
+      msml_set_error("%s%s: launch failed: %s", who, what, hipGetErrorString(e_));         \
+      return MSML_ERR_LAUNCH;                                                              \
+    }                                                                                      \
   } while (0)
+#define MSML_LAUNCH_OK(name) MSML_LAUNCH_OK2(name, "")
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 

@@ -18,11 +18,19 @@
 // from LDS with the gfx950 transposing read ds_read_b64_tr_b16 (rows = pixels, 16-channel
 // blocks); LDS rows are padded to a pitch == 64 (mod 256) bytes so the four pixel rows of a
 // block fall in disjoint bank windows.  f32 fragments are plain ds_read_b32 (one k per lane).
+//
+// This file also holds the host side of EVERY weight gradient (wgrad_call.h): the entry points msml_conv_wgrad, _group
+// and _bnin check their arguments and fill one WgradCall; wgrad_plan takes the whole decision (family, variant, splits,
+// chunk, slab bytes) by asking the families' predicates in one order (fc_wgrad.hip, wgrad_n32.hip, wgrad_halo.hip,
+// wgrad_fast.hip, then the generic kernel above); wgrad_run calls the family's launcher and, when the plan has slabs, the
+// fixed-order reduce.  The shape queries (msml_conv_wgrad_workspace, _group_max, _kernel_is_n32, _bnin_applies, _plan)
+// read the same plan.
 #include <stdlib.h>
 
 #include "common.h"
 #include "conv_call.h"
 #include "options.h"
+#include "wgrad_call.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -226,8 +234,7 @@ __global__ void __launch_bounds__(256) k_conv_wgrad(const WgradArgs p) {
 // not by bandwidth), the four lanes are combined through LDS.  Every addition has a fixed place in
 // the tree: deterministic.
 // (blockIdx.y = layer of a grouped launch: its slabs start at ws + layer * splits * slab, its gradient is dsts.p[layer])
-#define WR_MAXGROUP 8
-struct DwPtrs { float* p[WR_MAXGROUP]; };
+struct DwPtrs { float* p[WGRAD_MAXGROUP]; };
 __global__ void __launch_bounds__(256) k_wgrad_reduce(const float* __restrict__ ws, const DwPtrs dsts,
                                                       int splits, int arows, int taps, int vp, int A,
                                                       int Breal, int Btot, int boff, int accumulate) {
@@ -316,7 +323,7 @@ __global__ void __launch_bounds__(256) k_wgrad_reduce_rows(const float* __restri
 static void wgrad_reduce_launch_group(const float* ws, float* const* dw, int group, int splits, int up, int taps, int vp,
                                       int A, int Breal, int Btot, int boff, int accumulate, hipStream_t st) {
   DwPtrs d;
-  for (int i = 0; i < WR_MAXGROUP; i++) d.p[i] = dw[i < group ? i : 0];
+  for (int i = 0; i < WGRAD_MAXGROUP; i++) d.p[i] = dw[i < group ? i : 0];
   const int rowblocks = A * ((vp + 63) / 64);
   if (rowblocks >= 512 && taps > 1 && taps <= WR_MAXTAPS)
     k_wgrad_reduce_rows<<<dim3(rowblocks, group), 256, 0, st>>>(ws, d, splits, up, taps, vp, A, Breal, Btot, boff, accumulate);
@@ -325,42 +332,7 @@ static void wgrad_reduce_launch_group(const float* ws, float* const* dw, int gro
                                                                  accumulate);
 }
 
-static void wgrad_reduce_launch(const float* ws, float* dw, int splits, int up, int taps, int vp, int A, int Breal,
-                                int Btot, int boff, int accumulate, hipStream_t st) {
-  wgrad_reduce_launch_group(ws, &dw, 1, splits, up, taps, vp, A, Breal, Btot, boff, accumulate, st);
-}
-
-bool msml_wgrad_fast_launch(const void* u, int up, const void* v, int vp, float* ws, int N, int H, int W,
-                            int P, int Q, int R, int S, int stride, int pad_h, int pad_w, int ba, int bb,
-                            int ntw, int splits, int chunk, hipStream_t st, float* dw_direct, int A, int Breal,
-                            int Btot, int boff, int accumulate);
-
-bool msml_wgrad_fast_launch_group(const void* const* u, int up, const void* const* v, int vp, float* ws, int N, int H,
-                                  int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w, int ba, int bb,
-                                  int ntw, int group, int splits, int chunk, hipStream_t st, float* const* dw_direct,
-                                  int A, int Breal, int Btot, int boff, int accumulate);
-
-int msml_wgrad_halo_splits(int up, int vp, int A, int Breal, int N, int H, int W, int P, int Q, int R, int S,
-                           int stride, int pad_h, int pad_w);
-bool msml_wgrad_halo_launch(const void* u, int up, const void* v, int vp, float* ws, int N, int H, int W,
-                            int splits, hipStream_t st, const BnIn* xin = nullptr);
-int msml_wgrad_halo_group_splits(int up, int vp, int A, int Breal, int N, int H, int W, int P, int Q, int R, int S,
-                                 int stride, int pad_h, int pad_w, int group);
-bool msml_wgrad_halo_launch_group(const void* const* u, int up, const void* const* v, int vp, float* ws, int N, int H,
-                                  int W, int group, int splits, hipStream_t st, const BnIn* xin);
-
-int msml_fc_wgrad_launch(const void* u, int up, const void* v, int vp, float* dw, int A, int Breal, int Btot, int boff,
-                         int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w,
-                         int accumulate, hipStream_t st);      // fc_wgrad.hip
-int msml_wgrad_n32_splits(int up, int vp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
-                          int pad_w);
-bool msml_wgrad_n32_launch(const void* u, const void* v, float* ws, int N, int H, int W, int P, int Q, int R,
-                           int stride, int splits, hipStream_t st);
-int msml_wgrad_line_splits(int up, int vp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
-                           int pad_w);
-bool msml_wgrad_line_launch(const void* u, const void* v, int vp, float* ws, int N, int H, int R, int splits,
-                            hipStream_t st);
-
+// ---------------------------------------------------------------- the plan -------------------
 // taps handled by one workgroup of the bf16 fast kernel (narrow V operands share the U tile)
 static int wgrad_ntw(int vp, int taps) {
   const bool off = msml_opt().wgrad_no_multitap;
@@ -390,35 +362,206 @@ static int pick_splits(long mpix, int out_tiles) {
   long max_by_chunk = (mpix + minchunk - 1) / minchunk;
   long s = want < max_by_chunk ? want : max_by_chunk;
   if (s < 1) s = 1;
-  if (s > 512) s = 512;
+  if (s > WGRAD_MAXSPLITS) s = WGRAD_MAXSPLITS;
   return (int)s;
 }
 
+// The tiling of the im2col ("fast") and the generic kernel: tile sizes, taps per workgroup, splits per layer, pixels per
+// split.  bf16 counts its output tiles as the fast kernel cuts them (the generic bf16 launch keeps that split count), f32
+// as the generic kernel does.  Layers that share a launch spread the workgroup budget of ONE layer's launch over the
+// group (>= 1 split each; 1 = every layer's tile goes straight into its dW).
+static void wgrad_tile_plan(const WgradShape& s, WgradPlan& p) {
+  const int taps = s.R * s.S;
+  const long mpix = (long)s.N * s.P * s.Q;
+  p.ba = pick_tile(s.up);
+  p.bb = pick_tile(s.vp);
+  p.ntw = s.dtype == MSML_BF16 ? wgrad_ntw(s.vp, taps) : 1;
+  const int tiles = p.ntw > 1 ? cdiv(s.up, p.ba) * cdiv(taps, p.ntw) * cdiv(s.vp, 64) : cdiv(s.up, p.ba) * cdiv(s.vp, p.bb) * taps;
+  p.splits = pick_splits(mpix, tiles) / s.group;
+  if (p.splits < 1) p.splits = 1;
+  p.chunk = (int)(((mpix + p.splits - 1) / p.splits + 63) / 64 * 64);
+}
+
+// What a grouped launch of the im2col kernel asks of the shape (the strip / halo kernel has its own predicate).
+static bool wgrad_fast_groupable(const WgradShape& s) { return s.R == 3 && s.S == 3 && s.stride == 1; }
+
+// The whole decision.  One layer: fc, narrow-operand, line, strip / halo, im2col (unless MSML_NO_FAST_WGRAD, or when the
+// tensors are beyond its 32-bit offsets), generic; f32 is always generic.  Several layers, or the BatchNorm applied in
+// LDS: strip / halo; several layers of a shape it leaves go to the im2col kernel when they are 3x3 / stride 1 (tensors
+// too large for it are refused at the launch, wgrad_launch_refusal: the parent's order).  Everything else is refused:
+// p.refused says why, the family stays WGRAD_NONE.
+static WgradPlan wgrad_plan(const WgradShape& s) {
+  WgradPlan p;
+  const bool bf16 = s.dtype == MSML_BF16, one = s.group == 1 && !s.bnin;
+  if (bf16 && one && msml_wgrad_fc_applies(s)) {
+    p.family = WGRAD_FC;
+    p.splits = p.direct = 1;
+  } else if (bf16 && one && (p.splits = msml_wgrad_n32_applies(s)) > 0) {
+    p.family = WGRAD_N32;
+  } else if (bf16 && one && (p.splits = msml_wgrad_line_applies(s)) > 0) {
+    p.family = WGRAD_LINE;
+  } else if (bf16 && (p.splits = msml_wgrad_halo_applies(s)) > 0) {
+    p.family = WGRAD_HALO;
+    p.variant = msml_wgrad_halo_variant(s);
+  } else if (s.bnin) {
+    p.refused = "shape not covered by the strip kernel";
+  } else if (s.group > 1 && (!wgrad_fast_groupable(s) || (long)s.N * s.P * s.Q >= (1L << 24))) {
+    p.refused = "3x3 / stride-1 layers only";
+  } else {
+    wgrad_tile_plan(s, p);
+    const bool fast = bf16 && (s.group > 1 || (!msml_opt().no_fast_wgrad && msml_wgrad_fast_applies(s)));
+    p.family = fast ? WGRAD_FAST : WGRAD_GENERIC;
+    p.direct = fast && p.splits == 1;
+  }
+  if (p.family != WGRAD_NONE && !p.direct)
+    p.slab_bytes = (long)s.group * p.splits * s.up * s.R * s.S * s.vp * (long)sizeof(float);
+  return p;
+}
+
+// Why a planned call cannot launch after all (nullptr: it can): only a group sized for the im2col kernel knows this late.
+static const char* wgrad_launch_refusal(const WgradShape& s, const WgradPlan& p) {
+  return p.family == WGRAD_FAST && !msml_wgrad_fast_applies(s) ? "tensors too large for 32-bit offsets" : nullptr;
+}
+
+// Slabs of the largest split count any family can choose for a one-layer call of these channels, taps and pixels (a
+// group never gets more slabs than one layer, the fc kernel and the direct tiles none).  H, W, stride, padding and dtype
+// are not known here: both dtypes' tilings are asked, and every strip family for its largest answer (*_max_splits).
 extern "C" long msml_conv_wgrad_workspace(int up, int vp, int N, int P, int Q, int R, int S) {
-  int ba = pick_tile(up), bb = pick_tile(vp);
-  int tiles = cdiv(up, ba) * cdiv(vp, bb) * R * S;
-  int splits = pick_splits((long)N * P * Q, tiles);      // upper bound over both dtypes' tilings
-  int nt = wgrad_ntw(vp, R * S);
-  if (nt > 1) {
-    int s2 = pick_splits((long)N * P * Q, cdiv(up, ba) * cdiv(R * S, nt) * cdiv(vp, 64));
-    if (s2 > splits) splits = s2;
+  WgradShape s{up, vp, up, vp, vp, 0, N, P, Q, P, Q, R, S, 1, 0, 0};
+  int splits = 0;
+  for (int dtype : {MSML_F32, MSML_BF16}) {
+    WgradPlan t;
+    s.dtype = dtype;
+    wgrad_tile_plan(s, t);
+    if (t.splits > splits) splits = t.splits;
   }
-  // the halo kernel (wgrad_halo.hip) may use up to one split per CU-resident workgroup
-  if (R == 3 && S == 3 && splits < 512) {
-    int hs = msml_wgrad_halo_splits(up, vp, up, vp, N, P, Q, P, Q, 3, 3, 1, 1, 1);
-    if (hs > splits) splits = hs;
-  }
-  // narrow-operand kernel (wgrad_n32.hip): H / W are not known here, assume its largest split count
-  if (up == 32 && vp == 32 && (R * S == 16 || R * S == 9) && splits < 512) splits = 512;
-  if (up == 32 && (vp == 32 || vp == 64) && R * S == 7 && splits < 512) splits = 512;          // line kernel
+  for (int m : {msml_wgrad_halo_max_splits(s), msml_wgrad_n32_max_splits(s), msml_wgrad_line_max_splits(s)})
+    if (m > splits) splits = m;
   return (long)splits * up * R * S * vp * (long)sizeof(float);
 }
 
 // 1 when the bf16 weight gradient of this shape runs on the narrow-operand kernel (tests, profiling labels)
 extern "C" int msml_conv_wgrad_kernel_is_n32(int up, int vp, int N, int H, int W, int P, int Q, int R, int S, int stride,
                                              int pad_h, int pad_w) {
-  return (msml_wgrad_n32_splits(up, vp, N, H, W, P, Q, R, S, stride, pad_h, pad_w) > 0 ||
-          msml_wgrad_line_splits(up, vp, N, H, W, P, Q, R, S, stride, pad_h, pad_w) > 0) ? 1 : 0;
+  const int f = wgrad_plan(WgradShape{up, vp, up, vp, vp, 0, N, H, W, P, Q, R, S, stride, pad_h, pad_w}).family;
+  return f == WGRAD_N32 || f == WGRAD_LINE;
+}
+
+extern "C" int msml_conv_wgrad_bnin_applies(int up, int vp, int A, int Breal, int N, int H, int W, int P, int Q,
+                                            int R, int S, int stride, int pad_h, int pad_w) {
+  return wgrad_plan(WgradShape{up, vp, A, Breal, Breal, 0, N, H, W, P, Q, R, S, stride, pad_h, pad_w, MSML_BF16, 1, 1}).refused ? 0 : 1;
+}
+
+// Largest number of same-shape layers msml_conv_wgrad_group accepts for this shape (1: no grouping).  Strip / halo kernel:
+// while a layer keeps two splits.  Im2col kernel (small maps, the shapes the strip / halo kernel leaves): grouping pays
+// while a layer still has split-K slabs to shed, i.e. up to the split count of the one-layer launch.
+extern "C" int msml_conv_wgrad_group_max(int up, int vp, int A, int Breal, int N, int H, int W, int P, int Q, int R,
+                                         int S, int stride, int pad_h, int pad_w) {
+  const WgradShape s{up, vp, A, Breal, Breal, 0, N, H, W, P, Q, R, S, stride, pad_h, pad_w};
+  const int hs = msml_wgrad_halo_applies(s);
+  int most = hs / 2;
+  if (hs == 0) {
+    const bool off = msml_opt().no_fast_wgrad_group;
+    if (off || !wgrad_fast_groupable(s) || up % 8 || vp % 8 || msml_wgrad_n32_applies(s) > 0) return 1;
+    WgradPlan t;
+    wgrad_tile_plan(s, t);
+    most = t.splits;
+  }
+  int g = 1;
+  while (g * 2 <= WGRAD_MAXGROUP && g * 2 <= most) g *= 2;
+  return g;
+}
+
+// ---------------------------------------------------------------- the runner -----------------
+// The generic kernel's launcher: either dtype, any shape.
+static int wgrad_generic_launch(const WgradCall& c, const WgradPlan& p) {
+  const WgradArgs a{c.u[0], c.up, c.v[0], c.vp, c.N, c.H, c.W, c.P, c.Q, c.R, c.S, c.stride, c.pad_h, c.pad_w, c.ws, c.up,
+                    (long)c.N * c.P * c.Q, p.chunk, 1.0f / (float)(c.P * c.Q), 1.0f / (float)c.Q};
+  const int ba = p.ba, bb = p.bb;
+  const dim3 grid(cdiv(c.up, ba), cdiv(c.vp, bb) * c.R * c.S, p.splits);
+#define WG_LAUNCH(T, BA_, BB_)                                                    \
+  {                                                                               \
+    typedef WTile<T, BA_, BB_> WT_;                                               \
+    k_conv_wgrad<T, BA_, BB_><<<grid, dim3(256), 2 * WT_::STAGE, c.st>>>(a);      \
+  }
+#define WG_CASE(T)                                            \
+  if (ba == 128 && bb == 128) WG_LAUNCH(T, 128, 128)          \
+  else if (ba == 128) WG_LAUNCH(T, 128, 64)                   \
+  else if (bb == 128) WG_LAUNCH(T, 64, 128)                   \
+  else WG_LAUNCH(T, 64, 64)
+  if (c.dtype == MSML_F32) { WG_CASE(float) }
+  else if (c.dtype == MSML_BF16) { WG_CASE(unsigned short) }
+  else {
+    msml_set_error("conv_wgrad: unsupported dtype %d", c.dtype);
+    return MSML_ERR_DTYPE;
+  }
+#undef WG_CASE
+#undef WG_LAUNCH
+  return MSML_OK;
+}
+
+// Launch what the plan names; when it left slabs, sum them into the dW of every layer.
+static int wgrad_run(const WgradCall& c, const WgradPlan& p, const char* who) {
+  static const char* const family[] = {"", "(fc)", "(n32)", "(line)", "(halo)", "(fast)", ""};
+  const char* late = wgrad_launch_refusal(c, p);
+  MSML_CHECK(!late, MSML_ERR_UNSUPPORTED, "%s: %s", who, late);
+  int rc = MSML_OK;
+  switch (p.family) {
+    case WGRAD_FC: msml_wgrad_fc_launch(c, p); break;
+    case WGRAD_N32: msml_wgrad_n32_launch(c, p); break;
+    case WGRAD_LINE: msml_wgrad_line_launch(c, p); break;
+    case WGRAD_HALO: msml_wgrad_halo_launch(c, p); break;
+    case WGRAD_FAST: msml_wgrad_fast_launch(c, p); break;
+    default: rc = wgrad_generic_launch(c, p);
+  }
+  if (rc != MSML_OK) return rc;
+  MSML_LAUNCH_OK2(who, family[p.family]);
+  if (p.direct) return MSML_OK;
+  wgrad_reduce_launch_group(c.ws, c.dw, c.group, p.splits, c.up, c.R * c.S, c.vp, c.A, c.Breal, c.Btot, c.boff,
+                            c.accumulate, c.st);
+  MSML_LAUNCH_OK2(who, "_reduce");
+  return MSML_OK;
+}
+
+// ---------------------------------------------------------------- entry points ---------------
+static const char* wgrad_who(const WgradShape& s, bool grouped) {
+  return grouped ? "conv_wgrad_group" : s.bnin ? "conv_wgrad_bnin" : "conv_wgrad";
+}
+
+// The refusals that depend on the shape alone, in the order and the words of each entry point.  grouped: through
+// msml_conv_wgrad_group, which has two checks of its own; a group of one shares the plan of msml_conv_wgrad, so it
+// passes that entry point's checks too.
+static int wgrad_check_shape(const WgradShape& s, bool grouped) {
+  const char* who = wgrad_who(s, grouped);
+  if (grouped) {
+    MSML_CHECK(s.dtype == MSML_BF16, MSML_ERR_UNSUPPORTED, "%s: bf16 only", who);
+    MSML_CHECK(s.boff >= 0 && s.boff + s.Breal <= s.Btot && s.A <= s.up && s.Breal <= s.vp, MSML_ERR_SHAPE,
+               "%s: bad channel range", who);
+    if (s.group > 1) return MSML_OK;
+  }
+  MSML_CHECK(s.up > 0 && s.up % 8 == 0 && s.vp > 0 && s.vp % 8 == 0 && s.A > 0 && s.A <= s.up && s.Breal > 0 &&
+                 s.Breal <= s.vp && s.boff >= 0 && s.boff + s.Breal <= s.Btot,
+             MSML_ERR_SHAPE, "%s: bad channels up=%d vp=%d A=%d Breal=%d Btot=%d boff=%d", who, s.up, s.vp, s.A, s.Breal,
+             s.Btot, s.boff);
+  MSML_CHECK(s.N > 0 && s.H > 0 && s.W > 0 && s.P > 0 && s.Q > 0, MSML_ERR_SHAPE, "%s: bad dims", who);
+  if (s.bnin) return MSML_OK;        // (the strip predicate looks at the filter; its kernel has no reciprocal pixel decode)
+  MSML_CHECK(s.R > 0 && s.S > 0 && s.stride >= 1, MSML_ERR_SHAPE, "%s: bad dims", who);
+  MSML_CHECK((long)s.N * s.P * s.Q < (1L << 24), MSML_ERR_UNSUPPORTED,
+             "%s: N*P*Q = %ld exceeds 2^24 (float-reciprocal pixel decode)", who, (long)s.N * s.P * s.Q);
+  return MSML_OK;
+}
+
+// Check, plan, size, run.  The one-layer entry points owe msml_conv_wgrad_workspace bytes whatever the plan writes
+// (ops.py sizes its arenas from that query), the group entry point the slabs of its plan.
+static int wgrad_enter(const WgradCall& c, bool grouped) {
+  const char* who = wgrad_who(c, grouped);
+  const int rc = wgrad_check_shape(c, grouped);
+  if (rc != MSML_OK) return rc;
+  const WgradPlan p = wgrad_plan(c);
+  MSML_CHECK(!p.refused, MSML_ERR_UNSUPPORTED, "%s: %s", who, p.refused);
+  const long need = grouped ? p.slab_bytes : msml_conv_wgrad_workspace(c.up, c.vp, c.N, c.P, c.Q, c.R, c.S);
+  MSML_CHECK(c.ws_bytes >= need, MSML_ERR_WORKSPACE, "%s: workspace %ld < %ld bytes", who, c.ws_bytes, need);
+  return wgrad_run(c, p, who);
 }
 
 extern "C" int msml_conv_wgrad(const void* u, int up, const void* v, int vp, float* dw, int A,
@@ -426,207 +569,70 @@ extern "C" int msml_conv_wgrad(const void* u, int up, const void* v, int vp, flo
                                int R, int S, int stride, int pad_h, int pad_w, int accumulate,
                                void* workspace, long ws_bytes, int dtype, void* stream) {
   MSML_CHECK(u && v && dw && workspace, MSML_ERR_SHAPE, "conv_wgrad: null pointer");
-  MSML_CHECK(up > 0 && up % 8 == 0 && vp > 0 && vp % 8 == 0 && A > 0 && A <= up && Breal > 0 &&
-                 Breal <= vp && boff >= 0 && boff + Breal <= Btot,
-             MSML_ERR_SHAPE, "conv_wgrad: bad channels up=%d vp=%d A=%d Breal=%d Btot=%d boff=%d", up,
-             vp, A, Breal, Btot, boff);
-  MSML_CHECK(N > 0 && H > 0 && W > 0 && P > 0 && Q > 0 && R > 0 && S > 0 && stride >= 1,
-             MSML_ERR_SHAPE, "conv_wgrad: bad dims");
-  MSML_CHECK((long)N * P * Q < (1L << 24), MSML_ERR_UNSUPPORTED,
-             "conv_wgrad: N*P*Q = %ld exceeds 2^24 (float-reciprocal pixel decode)", (long)N * P * Q);
-  long need = msml_conv_wgrad_workspace(up, vp, N, P, Q, R, S);
-  MSML_CHECK(ws_bytes >= need, MSML_ERR_WORKSPACE, "conv_wgrad: workspace %ld < %ld bytes", ws_bytes, need);
-  WgradArgs a;
-  a.u = u; a.up = up; a.v = v; a.vp = vp;
-  a.N = N; a.H = H; a.W = W; a.P = P; a.Q = Q; a.R = R; a.S = S;
-  a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
-  a.ws = (float*)workspace;
-  a.arows = up;
-  a.Mpix = (long)N * P * Q;
-  a.rcp_pq = 1.0f / (float)(P * Q);
-  a.rcp_q = 1.0f / (float)Q;
-  const int ba = pick_tile(up), bb = pick_tile(vp);
-  const int atiles = cdiv(up, ba), btiles = cdiv(vp, bb), taps = R * S;
-  const int ntw = dtype == MSML_BF16 ? wgrad_ntw(vp, taps) : 1;
-  const int splits = pick_splits(a.Mpix, ntw > 1 ? atiles * cdiv(taps, ntw) * cdiv(vp, 64) : atiles * btiles * taps);
-  a.chunk = (int)(((a.Mpix + splits - 1) / splits + 63) / 64 * 64);
-  dim3 grid(atiles, btiles * taps, splits);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MSML_BF16) {
-    if (msml_fc_wgrad_launch(u, up, v, vp, dw, A, Breal, Btot, boff, N, H, W, P, Q, R, S, stride, pad_h, pad_w,
-                             accumulate, st)) {
-      MSML_LAUNCH_OK("conv_wgrad(fc)");
-      return MSML_OK;
-    }
-    const int ns = msml_wgrad_n32_splits(up, vp, N, H, W, P, Q, R, S, stride, pad_h, pad_w);
-    if (ns > 0 && msml_wgrad_n32_launch(u, v, a.ws, N, H, W, P, Q, R, stride, ns, st)) {
-      MSML_LAUNCH_OK("conv_wgrad(n32)");
-      wgrad_reduce_launch(a.ws, dw, ns, up, taps, vp, A, Breal, Btot, boff, accumulate, st);
-      MSML_LAUNCH_OK("conv_wgrad_reduce");
-      return MSML_OK;
-    }
-    const int ls = msml_wgrad_line_splits(up, vp, N, H, W, P, Q, R, S, stride, pad_h, pad_w);
-    if (ls > 0 && msml_wgrad_line_launch(u, v, vp, a.ws, N, H, R, ls, st)) {
-      MSML_LAUNCH_OK("conv_wgrad(line)");
-      wgrad_reduce_launch(a.ws, dw, ls, up, taps, vp, A, Breal, Btot, boff, accumulate, st);
-      MSML_LAUNCH_OK("conv_wgrad_reduce");
-      return MSML_OK;
-    }
-    const int hs = msml_wgrad_halo_splits(up, vp, A, Breal, N, H, W, P, Q, R, S, stride, pad_h, pad_w);
-    if (hs > 0 && msml_wgrad_halo_launch(u, up, v, vp, a.ws, N, H, W, hs, st)) {
-      MSML_LAUNCH_OK("conv_wgrad(halo)");
-      wgrad_reduce_launch(a.ws, dw, hs, up, taps, vp, A, Breal, Btot, boff, accumulate, st);
-      MSML_LAUNCH_OK("conv_wgrad_reduce");
-      return MSML_OK;
-    }
-  }
-  if (dtype == MSML_BF16 && !msml_opt().no_fast_wgrad &&
-      msml_wgrad_fast_launch(u, up, v, vp, a.ws, N, H, W, P, Q, R, S, stride, pad_h, pad_w, ba, bb, ntw,
-                             splits, a.chunk, st, dw, A, Breal, Btot, boff, accumulate)) {
-    MSML_LAUNCH_OK("conv_wgrad(fast)");
-    if (splits == 1) return MSML_OK;                   // written straight into dw
-    wgrad_reduce_launch(a.ws, dw, splits, up, taps, vp, A, Breal, Btot, boff, accumulate, st);
-    MSML_LAUNCH_OK("conv_wgrad_reduce");
-    return MSML_OK;
-  }
-
-#define WG_LAUNCH(T, BA_, BB_)                                                    \
-  {                                                                               \
-    typedef WTile<T, BA_, BB_> WT_;                                               \
-    k_conv_wgrad<T, BA_, BB_><<<grid, dim3(256), 2 * WT_::STAGE, st>>>(a);        \
-  }
-#define WG_CASE(T)                                            \
-  if (ba == 128 && bb == 128) WG_LAUNCH(T, 128, 128)          \
-  else if (ba == 128) WG_LAUNCH(T, 128, 64)                   \
-  else if (bb == 128) WG_LAUNCH(T, 64, 128)                   \
-  else WG_LAUNCH(T, 64, 64)
-  if (dtype == MSML_F32) { WG_CASE(float) }
-  else if (dtype == MSML_BF16) { WG_CASE(unsigned short) }
-  else {
-    msml_set_error("conv_wgrad: unsupported dtype %d", dtype);
-    return MSML_ERR_DTYPE;
-  }
-  MSML_LAUNCH_OK("conv_wgrad");
-  wgrad_reduce_launch(a.ws, dw, splits, up, taps, vp, A, Breal, Btot, boff, accumulate, st);
-  MSML_LAUNCH_OK("conv_wgrad_reduce");
-  return MSML_OK;
-}
-
-// Splits per layer of the im2col kernel when `group` layers share a launch: the workgroup budget of ONE layer's launch
-// spread over the group (>= 1; 1 = every layer's tile goes straight into its dW, no slabs, no reduce).
-static int fast_group_splits(long mpix, int out_tiles, int group) {
-  const int one = pick_splits(mpix, out_tiles);
-  int per = one / group;
-  return per < 1 ? 1 : per;
-}
-
-// Largest number of same-shape layers msml_conv_wgrad_group accepts for this shape (1: no grouping).
-extern "C" int msml_conv_wgrad_group_max(int up, int vp, int A, int Breal, int N, int H, int W, int P, int Q, int R,
-                                         int S, int stride, int pad_h, int pad_w) {
-  if (msml_wgrad_halo_splits(up, vp, A, Breal, N, H, W, P, Q, R, S, stride, pad_h, pad_w) > 0) {
-    int g = 1;
-    while (g * 2 <= WR_MAXGROUP &&
-           msml_wgrad_halo_group_splits(up, vp, A, Breal, N, H, W, P, Q, R, S, stride, pad_h, pad_w, g * 2) >= 2)
-      g *= 2;
-    return g;
-  }
-  // im2col kernel (small maps, the shapes the strip / halo kernel leaves): grouping pays while a layer still has
-  // split-K slabs to shed, i.e. up to the split count of the one-layer launch
-  const bool off = msml_opt().no_fast_wgrad_group;
-  if (off || R != 3 || S != 3 || stride != 1 || up % 8 || vp % 8) return 1;
-  if (msml_wgrad_n32_splits(up, vp, N, H, W, P, Q, R, S, stride, pad_h, pad_w) > 0) return 1;
-  const int ba = pick_tile(up), bb = pick_tile(vp), taps = R * S, ntw = wgrad_ntw(vp, taps);
-  const int tiles = ntw > 1 ? cdiv(up, ba) * cdiv(taps, ntw) * cdiv(vp, 64) : cdiv(up, ba) * cdiv(vp, bb) * taps;
-  const int one = pick_splits((long)N * P * Q, tiles);
-  int g = 1;
-  while (g * 2 <= WR_MAXGROUP && g * 2 <= one) g *= 2;
-  return g;
+  return wgrad_enter(WgradCall{{up, vp, A, Breal, Btot, boff, N, H, W, P, Q, R, S, stride, pad_h, pad_w, dtype, 1, 0,
+                                (size_t)dw % 16 == 0},
+                               &u, &v, &dw, accumulate, (float*)workspace, ws_bytes, (hipStream_t)stream}, false);
 }
 
 // Weight gradients of `group` layers of ONE shape in one launch pair (strip / halo kernel, or the im2col kernel for
 // the shapes it serves, + fixed-order reduce): every layer gets 1 / group of the workgroups, so the split-K slab bytes
 // written and re-read PER LAYER fall by the same factor (256 -> 256 @ 14x14: 75 MB of slabs for a 2.4 MB gradient at
 // group 1; 512 -> 512 @ 7x7 at group 4: no slabs at all, the tiles go straight into dW).  u / v / dw: host arrays of
-// `group` device pointers.  Results depend on `group` only through the split partition (fixed for a given group).
+// `group` device pointers.  Results depend on `group` only through the split partition (fixed for a given group); a
+// group of one takes the plan of msml_conv_wgrad.
 extern "C" int msml_conv_wgrad_group(const void* const* u, const void* const* v, float* const* dw, int group, int up,
                                      int vp, int A, int Breal, int Btot, int boff, int N, int H, int W, int P, int Q,
                                      int R, int S, int stride, int pad_h, int pad_w, int accumulate, void* workspace,
                                      long ws_bytes, int dtype, void* stream) {
-  MSML_CHECK(u && v && dw && workspace && group >= 1 && group <= WR_MAXGROUP, MSML_ERR_SHAPE,
+  MSML_CHECK(u && v && dw && workspace && group >= 1 && group <= WGRAD_MAXGROUP, MSML_ERR_SHAPE,
              "conv_wgrad_group: bad arguments (group %d)", group);
   for (int i = 0; i < group; i++)
     MSML_CHECK(u[i] && v[i] && dw[i], MSML_ERR_SHAPE, "conv_wgrad_group: null pointer in layer %d", i);
-  MSML_CHECK(dtype == MSML_BF16, MSML_ERR_UNSUPPORTED, "conv_wgrad_group: bf16 only");
-  MSML_CHECK(boff >= 0 && boff + Breal <= Btot && A <= up && Breal <= vp, MSML_ERR_SHAPE, "conv_wgrad_group: bad channel range");
-  hipStream_t st = (hipStream_t)stream;
-  const int per = msml_wgrad_halo_group_splits(up, vp, A, Breal, N, H, W, P, Q, R, S, stride, pad_h, pad_w, group);
-  if (per > 0) {
-    const long need = (long)group * per * up * 9 * vp * (long)sizeof(float);
-    MSML_CHECK(ws_bytes >= need, MSML_ERR_WORKSPACE, "conv_wgrad_group: workspace %ld < %ld bytes", ws_bytes, need);
-    msml_wgrad_halo_launch_group(u, up, v, vp, (float*)workspace, N, H, W, group, per, st, nullptr);
-    MSML_LAUNCH_OK("conv_wgrad_group(halo)");
-    wgrad_reduce_launch_group((const float*)workspace, dw, group, per, up, 9, vp, A, Breal, Btot, boff, accumulate, st);
-    MSML_LAUNCH_OK("conv_wgrad_group_reduce");
-    return MSML_OK;
-  }
-  MSML_CHECK(R == 3 && S == 3 && stride == 1 && (long)N * P * Q < (1L << 24), MSML_ERR_UNSUPPORTED,
-             "conv_wgrad_group: 3x3 / stride-1 layers only");
-  const int ba = pick_tile(up), bb = pick_tile(vp), taps = R * S, ntw = wgrad_ntw(vp, taps);
-  const int tiles = ntw > 1 ? cdiv(up, ba) * cdiv(taps, ntw) * cdiv(vp, 64) : cdiv(up, ba) * cdiv(vp, bb) * taps;
-  const long mpix = (long)N * P * Q;
-  const int splits = fast_group_splits(mpix, tiles, group);
-  const int chunk = (int)(((mpix + splits - 1) / splits + 63) / 64 * 64);
-  const long need = splits == 1 ? 0 : (long)group * splits * up * taps * vp * (long)sizeof(float);
-  MSML_CHECK(ws_bytes >= need, MSML_ERR_WORKSPACE, "conv_wgrad_group: workspace %ld < %ld bytes", ws_bytes, need);
-  MSML_CHECK(msml_wgrad_fast_launch_group(u, up, v, vp, (float*)workspace, N, H, W, P, Q, R, S, stride, pad_h, pad_w, ba,
-                                          bb, ntw, group, splits, chunk, st, dw, A, Breal, Btot, boff, accumulate),
-             MSML_ERR_UNSUPPORTED, "conv_wgrad_group: tensors too large for 32-bit offsets");
-  MSML_LAUNCH_OK("conv_wgrad_group(fast)");
-  if (splits > 1) {
-    wgrad_reduce_launch_group((const float*)workspace, dw, group, splits, up, taps, vp, A, Breal, Btot, boff, accumulate, st);
-    MSML_LAUNCH_OK("conv_wgrad_group_reduce");
-  }
-  return MSML_OK;
+  return wgrad_enter(WgradCall{{up, vp, A, Breal, Btot, boff, N, H, W, P, Q, R, S, stride, pad_h, pad_w, dtype, group, 0,
+                                (size_t)dw[0] % 16 == 0},
+                               u, v, dw, accumulate, (float*)workspace, ws_bytes, (hipStream_t)stream}, true);
 }
 
-
-// ---------------------------------------------------------------- split-K GEMM (head dX) -----
 // Weight gradient of a conv whose input was X = PReLU(v * x_scale + x_shift) (a training-mode
 // BatchNorm in front of the conv that msml_conv2d_bnin applied on the fly): the strips of v are
 // normalised in LDS, X never exists in HBM.  Only the shapes of the strip / halo kernel
 // (msml_conv_wgrad_bnin_applies); MSML_ERR_UNSUPPORTED otherwise.
-extern "C" int msml_conv_wgrad_bnin_applies(int up, int vp, int A, int Breal, int N, int H, int W, int P, int Q,
-                                            int R, int S, int stride, int pad_h, int pad_w) {
-  if (H == 7 && W == 7) return 0;      // (the image-pair strips of the 7 x 7 maps have no in-LDS BatchNorm variant)
-  return msml_wgrad_halo_splits(up, vp, A, Breal, N, H, W, P, Q, R, S, stride, pad_h, pad_w) > 0 ? 1 : 0;
-}
-
 extern "C" int msml_conv_wgrad_bnin(const void* u, int up, const void* v, int vp, const float* x_scale,
                                     const float* x_shift, const float* x_alpha, float* dw, int A, int Breal,
                                     int Btot, int boff, int N, int H, int W, int P, int Q, int R, int S,
                                     int stride, int pad_h, int pad_w, int accumulate, void* workspace,
                                     long ws_bytes, void* stream) {
   MSML_CHECK(u && v && dw && workspace && x_scale && x_shift, MSML_ERR_SHAPE, "conv_wgrad_bnin: null pointer");
-  MSML_CHECK(up > 0 && up % 8 == 0 && vp > 0 && vp % 8 == 0 && A > 0 && A <= up && Breal > 0 &&
-                 Breal <= vp && boff >= 0 && boff + Breal <= Btot,
-             MSML_ERR_SHAPE, "conv_wgrad_bnin: bad channels up=%d vp=%d A=%d Breal=%d Btot=%d boff=%d", up,
-             vp, A, Breal, Btot, boff);
-  MSML_CHECK(N > 0 && H > 0 && W > 0 && P > 0 && Q > 0, MSML_ERR_SHAPE, "conv_wgrad_bnin: bad dims");
-  const int hs = msml_wgrad_halo_splits(up, vp, A, Breal, N, H, W, P, Q, R, S, stride, pad_h, pad_w);
-  MSML_CHECK(hs > 0 && !(H == 7 && W == 7), MSML_ERR_UNSUPPORTED, "conv_wgrad_bnin: shape not covered by the strip kernel");
-  long need = msml_conv_wgrad_workspace(up, vp, N, P, Q, R, S);
-  MSML_CHECK(ws_bytes >= need, MSML_ERR_WORKSPACE, "conv_wgrad_bnin: workspace %ld < %ld bytes", ws_bytes, need);
-  hipStream_t st = (hipStream_t)stream;
   const BnIn xin{x_scale, x_shift, x_alpha};
-  MSML_CHECK(msml_wgrad_halo_launch(u, up, v, vp, (float*)workspace, N, H, W, hs, st, &xin), MSML_ERR_UNSUPPORTED,
-             "conv_wgrad_bnin: launch refused");
-  MSML_LAUNCH_OK("conv_wgrad_bnin(halo)");
-  const int taps = R * S;
-  wgrad_reduce_launch((const float*)workspace, dw, hs, up, taps, vp, A, Breal, Btot, boff, accumulate, st);
-  MSML_LAUNCH_OK("conv_wgrad_reduce");
+  return wgrad_enter(WgradCall{{up, vp, A, Breal, Btot, boff, N, H, W, P, Q, R, S, stride, pad_h, pad_w, MSML_BF16, 1, 1},
+                               &u, &v, &dw, accumulate, (float*)workspace, ws_bytes, (hipStream_t)stream, &xin}, false);
+}
+
+// The decision msml_conv_wgrad (group 1), msml_conv_wgrad_group (group > 1) or msml_conv_wgrad_bnin (bnin) takes for a
+// shape, and the status it would return before launching (valid pointers, 16-byte aligned dw and enough workspace
+// assumed).  plan: family (WgradFamily), variant, ba, bb, ntw, splits per layer, chunk, direct.  A pure shape query.
+extern "C" int msml_conv_wgrad_plan(int up, int vp, int A, int Breal, int Btot, int boff, int N, int H, int W, int P, int Q,
+                                    int R, int S, int stride, int pad_h, int pad_w, int dtype, int group, int bnin,
+                                    int* plan, long* slab_bytes) {
+  MSML_CHECK(plan && slab_bytes && group >= 1 && group <= WGRAD_MAXGROUP && !(bnin && group > 1), MSML_ERR_SHAPE,
+             "conv_wgrad_plan: bad arguments (group %d)", group);
+  const WgradShape s{up, vp, A, Breal, Btot, boff, N, H, W, P, Q, R, S, stride, pad_h, pad_w, bnin ? MSML_BF16 : dtype,
+                     group, bnin != 0};
+  const int rc = wgrad_check_shape(s, group > 1);
+  const WgradPlan p = rc == MSML_OK ? wgrad_plan(s) : WgradPlan{};
+  const int words[8] = {p.family, p.variant, p.ba, p.bb, p.ntw, p.splits, p.chunk, p.direct};
+  for (int i = 0; i < 8; i++) plan[i] = words[i];
+  *slab_bytes = p.slab_bytes;
+  if (rc != MSML_OK) return rc;
+  const char* no = p.refused ? p.refused : wgrad_launch_refusal(s, p);
+  MSML_CHECK(!no, MSML_ERR_UNSUPPORTED, "%s: %s", wgrad_who(s, group > 1), no);
+  MSML_CHECK(p.family != WGRAD_GENERIC || dtype == MSML_F32 || dtype == MSML_BF16, MSML_ERR_DTYPE,
+             "conv_wgrad: unsupported dtype %d", dtype);
   return MSML_OK;
 }
 
+
+// ---------------------------------------------------------------- split-K GEMM (head dX) -----
 extern "C" long msml_gemm_splitk_workspace(int M, int coutp, int K) {
   int stages = (K / 32 + 1) / 2;
   int ks = stages / 16 > 0 ? stages / 16 : 1;          // >= 16 stages (1024 k) per slice
@@ -648,7 +654,7 @@ extern "C" int msml_gemm_splitk(const void* a, int M, int K, const void* wp, int
   MSML_CHECK(msml_conv_fast_splitk(a, K, wp, kop, (float*)workspace, coutp, M, ks, st), MSML_ERR_UNSUPPORTED,
              "gemm_splitk: shape not supported by the fast kernel");
   MSML_LAUNCH_OK("gemm_splitk");
-  wgrad_reduce_launch((const float*)workspace, out, ks, M, 1, coutp, M, coutp, coutp, 0, 0, st);
+  wgrad_reduce_launch_group((const float*)workspace, &out, 1, ks, M, 1, coutp, M, coutp, coutp, 0, 0, st);
   MSML_LAUNCH_OK("gemm_splitk_reduce");
   return MSML_OK;
 }

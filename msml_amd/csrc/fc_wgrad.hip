@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "options.h"
+#include "wgrad_call.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -148,27 +149,28 @@ __global__ void __launch_bounds__(512) k_fc_wgrad(const FcWgradArgs p) {
 #endif
 }
 
-// 1 if the launch was taken (the caller falls back to the generic path otherwise)
-int msml_fc_wgrad_launch(const void* u, int up, const void* v, int vp, float* dw, int A, int Breal, int Btot, int boff,
-                         int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w,
-                         int accumulate, hipStream_t st) {
+bool msml_wgrad_fc_applies(const WgradShape& s) {
   const bool off = msml_opt().no_fc_wgrad;
-  const int T = R * S;
-  if (off || P != 1 || Q != 1 || R != H || S != W || pad_h != 0 || pad_w != 0 || stride != 1) return 0;
-  if (T < 2 || T > FCW_MAX_TAPS || up % 32 || vp % 32 || A != up || Breal != vp || N < 16) return 0;
-  if (boff % 4 || ((long)Btot * T) % 4 || ((size_t)dw % 16)) return 0;
-  if ((long)N * T * vp * 2 >= 0x70000000L || (long)N * up * 2 >= 0x70000000L) return 0;
+  const int T = s.R * s.S;
+  if (off || s.P != 1 || s.Q != 1 || s.R != s.H || s.S != s.W || s.pad_h != 0 || s.pad_w != 0 || s.stride != 1) return false;
+  if (T < 2 || T > FCW_MAX_TAPS || s.up % 32 || s.vp % 32 || s.A != s.up || s.Breal != s.vp || s.N < 16) return false;
+  if (s.boff % 4 || ((long)s.Btot * T) % 4 || !s.dw_aligned) return false;
+  if ((long)s.N * T * s.vp * 2 >= 0x70000000L || (long)s.N * s.up * 2 >= 0x70000000L) return false;
+  return true;
+}
+
+void msml_wgrad_fc_launch(const WgradCall& c, const WgradPlan&) {
+  const int T = c.R * c.S;
   FcWgradArgs a;
-  a.u = (const unsigned short*)u; a.u_bytes = (unsigned int)((long)N * up * 2);
-  a.v = (const unsigned short*)v; a.v_bytes = (unsigned int)((long)N * T * vp * 2);
-  a.N = N; a.T = T; a.up = up; a.vp = vp;
-  a.dw = dw; a.row_stride = (long)Btot * T; a.boff = boff; a.accumulate = accumulate;
+  a.u = (const unsigned short*)c.u[0]; a.u_bytes = (unsigned int)((long)c.N * c.up * 2);
+  a.v = (const unsigned short*)c.v[0]; a.v_bytes = (unsigned int)((long)c.N * T * c.vp * 2);
+  a.N = c.N; a.T = T; a.up = c.up; a.vp = c.vp;
+  a.dw = c.dw[0]; a.row_stride = (long)c.Btot * T; a.boff = c.boff; a.accumulate = c.accumulate;
   const int lds = 3 * (T + 2) * 1024;                // >= the 16 x 32 T x 4 B epilogue tile for T >= 2
   static std::once_flag once;
   std::call_once(once, [] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fc_wgrad), hipFuncAttributeMaxDynamicSharedMemorySize,
                               3 * (FCW_MAX_TAPS + 2) * 1024);
   });
-  k_fc_wgrad<<<dim3(vp / 32, up / 32), 512, lds, st>>>(a);
-  return 1;
+  k_fc_wgrad<<<dim3(c.vp / 32, c.up / 32), 512, lds, c.st>>>(a);
 }

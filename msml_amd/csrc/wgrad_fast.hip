@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "wgrad_call.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -21,10 +22,9 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 
 #define OOB_OFFSET 0x7ffffff0u
 
-#define WF_MAXGROUP 8
 struct WgradFastArgs {
-  const unsigned short* u[WF_MAXGROUP]; int up; unsigned int u_bytes;     // one (dY, X, dW) per grouped layer
-  const unsigned short* v[WF_MAXGROUP]; int vp; unsigned int v_bytes;
+  const unsigned short* u[WGRAD_MAXGROUP]; int up; unsigned int u_bytes;     // one (dY, X, dW) per grouped layer
+  const unsigned short* v[WGRAD_MAXGROUP]; int vp; unsigned int v_bytes;
   int zper;                   // splits per layer: grid.z = layers x zper
   int N, H, W, P, Q, R, S, stride, pad_h, pad_w;
   float* ws;
@@ -34,7 +34,7 @@ struct WgradFastArgs {
   float rcp_pq, rcp_q;
   // splits == 1 (many output tiles, short K: the PartialFC / fc weight gradients): no slab, the
   // tile goes straight into dW[a][boff + b][tap] (saves writing and re-reading |dW| floats)
-  float* dw[WF_MAXGROUP];
+  float* dw[WGRAD_MAXGROUP];
   int direct;
   int A, Breal, Btot, boff, accumulate;
 };
@@ -213,40 +213,41 @@ __global__ void __launch_bounds__(256) k_wgrad_fast(const WgradFastArgs p) {
 
 
 
-// Called from msml_conv_wgrad[_group] (conv_wgrad.hip) for bf16; chunk is a multiple of 64.  group layers of one shape
-// share the launch (grid.z = group x splits; slabs at ws[layer * splits + split], or, with splits == 1, every layer's
-// tile straight into its dW).  Returns false when the tensors are too large for 32-bit buffer offsets.
-bool msml_wgrad_fast_launch_group(const void* const* u, int up, const void* const* v, int vp, float* ws, int N, int H,
-                                  int W, int P, int Q, int R, int S, int stride, int pad_h, int pad_w, int ba, int bb,
-                                  int ntw, int group, int splits, int chunk, hipStream_t st, float* const* dw_direct,
-                                  int A, int Breal, int Btot, int boff, int accumulate) {
-  const long ub = (long)N * P * Q * up * 2, vb = (long)N * H * W * vp * 2;
-  if (ub >= 0x7fffff00L || vb >= 0x7fffff00L || group < 1 || group > WF_MAXGROUP) return false;
+// false when the tensors are too large for 32-bit buffer offsets
+bool msml_wgrad_fast_applies(const WgradShape& s) {
+  const long ub = (long)s.N * s.P * s.Q * s.up * 2, vb = (long)s.N * s.H * s.W * s.vp * 2;
+  return ub < 0x7fffff00L && vb < 0x7fffff00L && s.group >= 1 && s.group <= WGRAD_MAXGROUP;
+}
+
+// bf16; p.chunk is a multiple of 64.  The layers of the group share the launch (grid.z = group x splits; slabs at
+// ws[layer * splits + split], or, with p.direct, every layer's tile straight into its dW).
+void msml_wgrad_fast_launch(const WgradCall& c, const WgradPlan& p) {
+  const int up = c.up, vp = c.vp, R = c.R, S = c.S;
   WgradFastArgs a;
-  for (int i = 0; i < WF_MAXGROUP; i++) {
-    a.u[i] = (const unsigned short*)u[i < group ? i : 0];
-    a.v[i] = (const unsigned short*)v[i < group ? i : 0];
-    a.dw[i] = dw_direct ? dw_direct[i < group ? i : 0] : nullptr;
+  for (int i = 0; i < WGRAD_MAXGROUP; i++) {
+    a.u[i] = (const unsigned short*)c.u[i < c.group ? i : 0];
+    a.v[i] = (const unsigned short*)c.v[i < c.group ? i : 0];
+    a.dw[i] = c.dw[i < c.group ? i : 0];
   }
-  a.up = up; a.u_bytes = (unsigned int)ub;
-  a.vp = vp; a.v_bytes = (unsigned int)vb;
-  a.zper = splits;
-  a.N = N; a.H = H; a.W = W; a.P = P; a.Q = Q; a.R = R; a.S = S;
-  a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
-  a.ws = ws; a.arows = up;
-  a.Mpix = (long)N * P * Q;
-  a.chunk = chunk;
-  a.rcp_pq = 1.0f / (float)(P * Q);
-  a.rcp_q = 1.0f / (float)Q;
-  a.direct = (splits == 1 && dw_direct) ? 1 : 0;
-  a.A = A; a.Breal = Breal; a.Btot = Btot; a.boff = boff; a.accumulate = accumulate;
-  const int gz = group * splits;
-#define WF(BA_, BB_, NTW_) k_wgrad_fast<BA_, BB_, NTW_><<<grid, dim3(256), 2 * 64 * (BA_ + BB_) * 2, st>>>(a)
-  if (ntw == 3) {                                       // narrow V: 3 taps per workgroup
+  a.up = up; a.u_bytes = (unsigned int)((long)c.N * c.P * c.Q * up * 2);
+  a.vp = vp; a.v_bytes = (unsigned int)((long)c.N * c.H * c.W * vp * 2);
+  a.zper = p.splits;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.P = c.P; a.Q = c.Q; a.R = R; a.S = S;
+  a.stride = c.stride; a.pad_h = c.pad_h; a.pad_w = c.pad_w;
+  a.ws = c.ws; a.arows = up;
+  a.Mpix = (long)c.N * c.P * c.Q;
+  a.chunk = p.chunk;
+  a.rcp_pq = 1.0f / (float)(c.P * c.Q);
+  a.rcp_q = 1.0f / (float)c.Q;
+  a.direct = p.direct;
+  a.A = c.A; a.Breal = c.Breal; a.Btot = c.Btot; a.boff = c.boff; a.accumulate = c.accumulate;
+  const int gz = c.group * p.splits, ba = p.ba, bb = p.bb;
+#define WF(BA_, BB_, NTW_) k_wgrad_fast<BA_, BB_, NTW_><<<grid, dim3(256), 2 * 64 * (BA_ + BB_) * 2, c.st>>>(a)
+  if (p.ntw == 3) {                                     // narrow V: 3 taps per workgroup
     dim3 grid(cdiv(up, ba), cdiv(R * S, 3) * cdiv(vp, 64), gz);
     if (ba == 128) WF(128, 192, 3);
     else WF(64, 192, 3);
-    return true;
+    return;
   }
   dim3 grid(cdiv(up, ba), cdiv(vp, bb) * R * S, gz);
   if (ba == 128 && bb == 128) WF(128, 128, 1);
@@ -254,14 +255,4 @@ bool msml_wgrad_fast_launch_group(const void* const* u, int up, const void* cons
   else if (bb == 128) WF(64, 128, 1);
   else WF(64, 64, 1);
 #undef WF
-  return true;
-}
-
-bool msml_wgrad_fast_launch(const void* u, int up, const void* v, int vp, float* ws, int N, int H, int W,
-                            int P, int Q, int R, int S, int stride, int pad_h, int pad_w, int ba, int bb,
-                            int ntw, int splits, int chunk, hipStream_t st, float* dw_direct, int A, int Breal,
-                            int Btot, int boff, int accumulate) {
-  return msml_wgrad_fast_launch_group(&u, up, &v, vp, ws, N, H, W, P, Q, R, S, stride, pad_h, pad_w, ba, bb, ntw, 1,
-                                      splits, chunk, st, dw_direct ? &dw_direct : nullptr, A, Breal, Btot, boff,
-                                      accumulate);
 }

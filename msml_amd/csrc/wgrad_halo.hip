@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "options.h"
+#include "wgrad_call.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -54,10 +55,9 @@ __device__ __forceinline__ void wh_dma_wait() {
 #endif
 }
 
-#define WH_MAXGROUP 8
 struct WgradHaloArgs {
-  const unsigned short* u[WH_MAXGROUP]; int up; unsigned int u_bytes;     // dY [N][H][W][up], one per grouped layer
-  const unsigned short* v[WH_MAXGROUP]; int vp; unsigned int v_bytes;     // X  [N][H][W][vp]
+  const unsigned short* u[WGRAD_MAXGROUP]; int up; unsigned int u_bytes;     // dY [N][H][W][up], one per grouped layer
+  const unsigned short* v[WGRAD_MAXGROUP]; int vp; unsigned int v_bytes;     // X  [N][H][W][vp]
   int N, H, W, spy, spx;      // dY map; strips per image column / row (7 rows x 14 columns each)
   int XH, XW;                 // unused (the removed stride-2 variant's input map): keeps the offsets of the fields below
   int nstrips, chunk;         // total strips, strips per split
@@ -359,23 +359,38 @@ static bool wh_wide(int up) {
   return up % 128 == 0 && up >= lim;
 }
 
-int msml_wgrad_halo_splits(int up, int vp, int A, int Breal, int N, int H, int W, int P, int Q, int R, int S,
-                           int stride, int pad_h, int pad_w) {
+static bool wh_pair7(const WgradShape& s) { return s.H == 7 && s.W == 7; }    // two 7 x 7 images per strip
+
+// (image-pair strips: 64-row tiles only -- the 128-row instantiation of that variant spills)
+int msml_wgrad_halo_variant(const WgradShape& s) {
+  return wh_pair7(s) ? WGRAD_HALO_PAIR7 : wh_wide(s.up) ? WGRAD_HALO_128 : WGRAD_HALO_64;
+}
+
+// `group` layers of this shape share one launch: every layer gets 1 / group of the splits of a one-layer launch
+int msml_wgrad_halo_applies(const WgradShape& s) {
   const bool off = msml_opt().no_halo_wgrad;
   if (off) return 0;
-  if (R != 3 || S != 3 || stride != 1 || pad_h != 1 || pad_w != 1 || P != H || Q != W) return 0;
-  if (up % 64 != 0 || vp % 64 != 0 || A != up || Breal != vp) return 0;
-  const bool pair7 = H == 7 && W == 7 && !msml_opt().wgrad_halo_no_pair7;   // two 7 x 7 images per strip
-  const long strips = pair7 ? (N + 1) / 2 : (long)N * cdiv(H, 7) * cdiv(W, 14);
-  if ((long)N * H * W * 10 < strips * 112 * 7) return 0;           // < 70 % real k-values
-  if ((long)N * H * W * up * 2 >= 0x70000000L || (long)N * H * W * vp * 2 >= 0x70000000L) return 0;
-  // (image-pair strips: 64-row tiles only -- the 128-row instantiation of that variant spills)
-  const int tiles = ((wh_wide(up) && !pair7) ? up / 128 : up / 64) * (vp / 64);
+  if (s.R != 3 || s.S != 3 || s.stride != 1 || s.pad_h != 1 || s.pad_w != 1 || s.P != s.H || s.Q != s.W) return 0;
+  if (s.up % 64 != 0 || s.vp % 64 != 0 || s.A != s.up || s.Breal != s.vp) return 0;
+  if (wh_pair7(s) && s.bnin) return 0;               // (no in-LDS BatchNorm variant of the image-pair strips)
+  const bool pair7 = wh_pair7(s) && !msml_opt().wgrad_halo_no_pair7;
+  const long strips = pair7 ? (s.N + 1) / 2 : (long)s.N * cdiv(s.H, 7) * cdiv(s.W, 14);
+  if ((long)s.N * s.H * s.W * 10 < strips * 112 * 7) return 0;     // < 70 % real k-values
+  if ((long)s.N * s.H * s.W * s.up * 2 >= 0x70000000L || (long)s.N * s.H * s.W * s.vp * 2 >= 0x70000000L) return 0;
+  const int tiles = s.up / (msml_wgrad_halo_variant(s) == WGRAD_HALO_128 ? 128 : 64) * (s.vp / 64);
   long splits = msml_num_cus() / tiles;                      // one resident workgroup per CU
   if (splits < 1) splits = 1;
   if (splits > strips) splits = strips;
-  if (splits > 512) splits = 512;
-  return (int)splits;
+  if (splits > WGRAD_MAXSPLITS) splits = WGRAD_MAXSPLITS;
+  if (s.group < 1 || s.group > WGRAD_MAXGROUP) return 0;
+  return (int)splits / s.group;
+}
+
+// (this family takes one completion only: V on the grid of U, stride 1, pad 1, every stored channel real)
+int msml_wgrad_halo_max_splits(const WgradShape& s) {
+  WgradShape h = s;
+  h.H = s.P; h.W = s.Q; h.stride = h.pad_h = h.pad_w = 1; h.A = s.up; h.Breal = s.vp; h.group = 1; h.bnin = 0;
+  return msml_wgrad_halo_applies(h);
 }
 
 template <int CO, bool XF, bool P7 = false>
@@ -390,54 +405,32 @@ static void wh_launch(const WgradHaloArgs& a, dim3 grid, hipStream_t st) {
   k_wgrad_halo<CO, XF, P7><<<grid, dim3(512), lds, st>>>(a);
 }
 
-// splits per layer when `group` layers of this shape share one launch (0: not covered)
-int msml_wgrad_halo_group_splits(int up, int vp, int A, int Breal, int N, int H, int W, int P, int Q, int R, int S,
-                                 int stride, int pad_h, int pad_w, int group) {
-  const int hs = msml_wgrad_halo_splits(up, vp, A, Breal, N, H, W, P, Q, R, S, stride, pad_h, pad_w);
-  if (hs <= 0 || group < 1 || group > WH_MAXGROUP) return 0;
-  const int per = hs / group;
-  return per < 1 ? 0 : per;
-}
-
-// group: number of layers (u[i], v[i]), i < group, of ONE shape; splits = splits per layer; slabs land in
-// ws[(layer * splits + split)][up][9][vp]
-bool msml_wgrad_halo_launch_group(const void* const* u, int up, const void* const* v, int vp, float* ws, int N, int H,
-                                  int W, int group, int splits, hipStream_t st, const BnIn* xin) {
+// slabs land in ws[(layer * splits + split)][up][9][vp]
+void msml_wgrad_halo_launch(const WgradCall& c, const WgradPlan& p) {
   const bool no_remap = msml_opt().wgrad_halo_no_remap;
+  const int up = c.up, vp = c.vp, N = c.N, H = c.H, W = c.W;
   WgradHaloArgs a;
-  for (int i = 0; i < WH_MAXGROUP; i++) {
-    a.u[i] = (const unsigned short*)u[i < group ? i : 0];
-    a.v[i] = (const unsigned short*)v[i < group ? i : 0];
+  for (int i = 0; i < WGRAD_MAXGROUP; i++) {
+    a.u[i] = (const unsigned short*)c.u[i < c.group ? i : 0];
+    a.v[i] = (const unsigned short*)c.v[i < c.group ? i : 0];
   }
   a.up = up; a.u_bytes = (unsigned int)((long)N * H * W * up * 2);
   a.vp = vp; a.v_bytes = (unsigned int)((long)N * H * W * vp * 2);
   a.N = N; a.H = H; a.W = W; a.spy = cdiv(H, 7); a.spx = cdiv(W, 14);
-  a.pair7 = (H == 7 && W == 7) ? 1 : 0;
+  a.pair7 = p.variant == WGRAD_HALO_PAIR7 ? 1 : 0;
   a.nstrips = a.pair7 ? (N + 1) / 2 : N * a.spy * a.spx;
-  a.chunk = cdiv(a.nstrips, splits);
-  a.zper = splits;
-  a.ws = ws;
+  a.chunk = cdiv(a.nstrips, p.splits);
+  a.zper = p.splits;
+  a.ws = c.ws;
   a.xin = BnIn{nullptr, nullptr, nullptr};
-  if (xin) a.xin = *xin;
-  const int gz = group * splits;
-  const int tiles = ((wh_wide(up) && !a.pair7) ? up / 128 : up / 64) * (vp / 64);
-  a.remap = (!no_remap && tiles >= 4 && gz % 8 == 0) ? 1 : 0;
-  if (a.pair7) {
-    if (xin) return false;                             // (no in-LDS BatchNorm variant of the image-pair strips)
-    wh_launch<64, false, true>(a, dim3(up / 64, vp / 64, gz), st);
-    return true;
-  }
-  if (wh_wide(up)) {
-    if (xin) wh_launch<128, true>(a, dim3(up / 128, vp / 64, gz), st);
-    else wh_launch<128, false>(a, dim3(up / 128, vp / 64, gz), st);
-  } else {
-    if (xin) wh_launch<64, true>(a, dim3(up / 64, vp / 64, gz), st);
-    else wh_launch<64, false>(a, dim3(up / 64, vp / 64, gz), st);
-  }
-  return true;
-}
-
-bool msml_wgrad_halo_launch(const void* u, int up, const void* v, int vp, float* ws, int N, int H, int W,
-                            int splits, hipStream_t st, const BnIn* xin) {
-  return msml_wgrad_halo_launch_group(&u, up, &v, vp, ws, N, H, W, 1, splits, st, xin);
+  if (c.xin) a.xin = *c.xin;
+  const int gz = c.group * p.splits;
+  const int co = p.variant == WGRAD_HALO_128 ? 128 : 64;
+  a.remap = (!no_remap && (up / co) * (vp / 64) >= 4 && gz % 8 == 0) ? 1 : 0;
+  const dim3 grid(up / co, vp / 64, gz);
+  if (a.pair7) wh_launch<64, false, true>(a, grid, c.st);
+  else if (co == 128 && c.xin) wh_launch<128, true>(a, grid, c.st);
+  else if (co == 128) wh_launch<128, false>(a, grid, c.st);
+  else if (c.xin) wh_launch<64, true>(a, grid, c.st);
+  else wh_launch<64, false>(a, grid, c.st);
 }

@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "options.h"
+#include "wgrad_call.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -170,21 +171,26 @@ __global__ void __launch_bounds__(512) k_wgrad_n32(const WgradN32Args p) {
 }
 
 // splits for a shape (0 = shape not covered by this kernel)
-int msml_wgrad_n32_splits(int up, int vp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
-                          int pad_w) {
+int msml_wgrad_n32_applies(const WgradShape& s) {
   const bool off = msml_opt().no_n32_wgrad;
-  if (off || up != 32 || vp != 32 || R != S || pad_h != 1 || pad_w != 1) return 0;
-  const bool d4 = R == 4 && stride == 2 && H == 2 * P && W == 2 * Q;
-  const bool c3 = R == 3 && stride == 1 && H == P && W == Q;
+  if (off || msml_wgrad_n32_max_splits(s) == 0 || s.R != s.S || s.pad_h != 1 || s.pad_w != 1) return 0;
+  const bool d4 = s.R == 4 && s.stride == 2 && s.H == 2 * s.P && s.W == 2 * s.Q;
+  const bool c3 = s.R == 3 && s.stride == 1 && s.H == s.P && s.W == s.Q;
   if (!d4 && !c3) return 0;
-  if (P < 14 || Q < 14) return 0;                    // tiny maps: the generic kernel is as good
-  if ((long)N * H * W * 64 >= 0x70000000L) return 0;
-  const long strips = (long)N * cdiv(P, 4) * cdiv(Q, 16);
+  if (s.P < 14 || s.Q < 14) return 0;                // tiny maps: the generic kernel is as good
+  if ((long)s.N * s.H * s.W * 64 >= 0x70000000L) return 0;
+  const long strips = (long)s.N * cdiv(s.P, 4) * cdiv(s.Q, 16);
   long splits = 2L * msml_num_cus();                       // two resident workgroups per CU where LDS allows (3x3)
   if (d4) splits = msml_num_cus();
   if (splits > strips) splits = strips;
-  if (splits > 512) splits = 512;
+  if (splits > WGRAD_MAXSPLITS) splits = WGRAD_MAXSPLITS;
   return (int)splits;
+}
+
+// (the cap: with a large batch on a large map every workgroup the rule above asks for gets a strip; by tap count, as the
+// workspace query has always granted it)
+int msml_wgrad_n32_max_splits(const WgradShape& s) {
+  return (s.up == 32 && s.vp == 32 && (s.R * s.S == 9 || s.R * s.S == 16)) ? WGRAD_MAXSPLITS : 0;
 }
 
 template <int R, int STRIDE>
@@ -199,20 +205,17 @@ static void wn_launch(const WgradN32Args& a, int splits, hipStream_t st) {
   k_wgrad_n32<R, STRIDE><<<dim3(splits), dim3(512), lds, st>>>(a);
 }
 
-bool msml_wgrad_n32_launch(const void* u, const void* v, float* ws, int N, int H, int W, int P, int Q, int R,
-                           int stride, int splits, hipStream_t st) {
+void msml_wgrad_n32_launch(const WgradCall& c, const WgradPlan& p) {
   WgradN32Args a;
-  a.u = (const unsigned short*)u; a.u_bytes = (unsigned int)((long)N * P * Q * 64);
-  a.v = (const unsigned short*)v; a.v_bytes = (unsigned int)((long)N * H * W * 64);
-  a.N = N; a.P = P; a.Q = Q; a.H = H; a.W = W;
-  a.spy = cdiv(P, 4); a.spx = cdiv(Q, 16);
-  a.nstrips = N * a.spy * a.spx;
-  a.chunk = cdiv(a.nstrips, splits);
-  a.ws = ws;
-  if (R == 4 && stride == 2) wn_launch<4, 2>(a, splits, st);
-  else if (R == 3 && stride == 1) wn_launch<3, 1>(a, splits, st);
-  else return false;
-  return true;
+  a.u = (const unsigned short*)c.u[0]; a.u_bytes = (unsigned int)((long)c.N * c.P * c.Q * 64);
+  a.v = (const unsigned short*)c.v[0]; a.v_bytes = (unsigned int)((long)c.N * c.H * c.W * 64);
+  a.N = c.N; a.P = c.P; a.Q = c.Q; a.H = c.H; a.W = c.W;
+  a.spy = cdiv(c.P, 4); a.spx = cdiv(c.Q, 16);
+  a.nstrips = c.N * a.spy * a.spx;
+  a.chunk = cdiv(a.nstrips, p.splits);
+  a.ws = c.ws;
+  if (c.R == 4) wn_launch<4, 2>(a, p.splits, c.st);
+  else wn_launch<3, 1>(a, p.splits, c.st);
 }
 
 
@@ -325,18 +328,23 @@ __global__ void __launch_bounds__(512) k_wgrad_line(const WgradLineArgs p) {
 #endif
 }
 
-int msml_wgrad_line_splits(int up, int vp, int N, int H, int W, int P, int Q, int R, int S, int stride, int pad_h,
-                           int pad_w) {
+int msml_wgrad_line_applies(const WgradShape& s) {
   const bool off = msml_opt().no_n32_wgrad;
-  if (off || up != 32 || (vp != 32 && vp != 64) || stride != 1) return 0;
-  if (!((R == 7 && S == 1 && pad_h == 3 && pad_w == 0) || (R == 1 && S == 7 && pad_h == 0 && pad_w == 3))) return 0;
-  if (H != W || P != H || Q != W || !(H == 56 || H == 28)) return 0;
-  if ((long)N * H * W * vp * 2 >= 0x70000000L) return 0;
-  const long tiles = (long)N * cdiv(H, 224 / H);
-  long splits = (vp == 32 ? 2L : 1L) * msml_num_cus();
+  if (off || msml_wgrad_line_max_splits(s) == 0 || s.stride != 1) return 0;
+  if (!((s.R == 7 && s.pad_h == 3 && s.pad_w == 0) || (s.S == 7 && s.pad_h == 0 && s.pad_w == 3))) return 0;
+  if (s.H != s.W || s.P != s.H || s.Q != s.W || !(s.H == 56 || s.H == 28)) return 0;
+  if ((long)s.N * s.H * s.W * s.vp * 2 >= 0x70000000L) return 0;
+  const long tiles = (long)s.N * cdiv(s.H, 224 / s.H);
+  long splits = (s.vp == 32 ? 2L : 1L) * msml_num_cus();
   if (splits > tiles) splits = tiles;
-  if (splits > 512) splits = 512;
+  if (splits > WGRAD_MAXSPLITS) splits = WGRAD_MAXSPLITS;
   return (int)splits;
+}
+
+// (the cap, as for the narrow-operand kernel)
+int msml_wgrad_line_max_splits(const WgradShape& s) {
+  const bool line = (s.R == 7 && s.S == 1) || (s.R == 1 && s.S == 7);
+  return (s.up == 32 && (s.vp == 32 || s.vp == 64) && line) ? WGRAD_MAXSPLITS : 0;
 }
 
 template <int VP>
@@ -350,18 +358,16 @@ static void wl_launch(const WgradLineArgs& a, int splits, hipStream_t st) {
   k_wgrad_line<VP><<<dim3(splits), dim3(512), lds, st>>>(a);
 }
 
-bool msml_wgrad_line_launch(const void* u, const void* v, int vp, float* ws, int N, int H, int R, int splits,
-                            hipStream_t st) {
+void msml_wgrad_line_launch(const WgradCall& c, const WgradPlan& p) {
   WgradLineArgs a;
-  a.u = (const unsigned short*)u; a.u_bytes = (unsigned int)((long)N * H * H * 64);
-  a.v = (const unsigned short*)v; a.v_bytes = (unsigned int)((long)N * H * H * vp * 2);
-  a.N = N; a.L = H; a.B = 224 / H;
-  a.tiles_per_img = cdiv(H, a.B);
-  a.ntiles = N * a.tiles_per_img;
-  a.chunk = cdiv(a.ntiles, splits);
-  a.vertical = R == 7 ? 1 : 0;
-  a.ws = ws;
-  if (vp == 64) wl_launch<64>(a, splits, st);
-  else wl_launch<32>(a, splits, st);
-  return true;
+  a.u = (const unsigned short*)c.u[0]; a.u_bytes = (unsigned int)((long)c.N * c.H * c.H * 64);
+  a.v = (const unsigned short*)c.v[0]; a.v_bytes = (unsigned int)((long)c.N * c.H * c.H * c.vp * 2);
+  a.N = c.N; a.L = c.H; a.B = 224 / c.H;
+  a.tiles_per_img = cdiv(c.H, a.B);
+  a.ntiles = c.N * a.tiles_per_img;
+  a.chunk = cdiv(a.ntiles, p.splits);
+  a.vertical = c.R == 7 ? 1 : 0;
+  a.ws = c.ws;
+  if (c.vp == 64) wl_launch<64>(a, p.splits, c.st);
+  else wl_launch<32>(a, p.splits, c.st);
 }

@@ -391,10 +391,7 @@ def conv_wgrad_bnin(u, v, coef, alpha, dw, a, breal, btot, boff, accumulate=Fals
     (msml_conv_wgrad_bnin); same conventions as conv_wgrad."""
     n, p, q, up = u.shape
     _, h, w, vp = v.shape
-    key = (up, vp, n, p, q, 3, 3)
-    need = _WGRAD_WS_NEED.get(key)
-    if need is None:
-        need = _WGRAD_WS_NEED[key] = _lib.value("msml_conv_wgrad_workspace", *key)
+    need = wgrad_ws_need(up, vp, n, p, q, 3, 3)
     raw = stream.cuda_stream if stream is not None else _lib.raw_stream()
     ws = workspace(need, u.device, "wgrad", stream)
     coef = rows4(coef)
@@ -548,16 +545,21 @@ def wgrad_stream_join():
 _WGRAD_WS_NEED = {}
 
 
+def wgrad_ws_need(*key):
+    """msml_conv_wgrad_workspace(up, vp, n, p, q, r, s), asked once per shape."""
+    need = _WGRAD_WS_NEED.get(key)
+    if need is None:
+        need = _WGRAD_WS_NEED[key] = _lib.value("msml_conv_wgrad_workspace", *key)
+    return need
+
+
 def conv_wgrad(u, v, dw, a, breal, btot, boff, r, s, stride, pad_h, pad_w, accumulate=False, stream=None):
     """dw[a][boff+b][r][s] = sum_pix u[pix][a] * v[shift(pix, r, s)][b] (see msml_conv_wgrad).
     stream: enqueue on this torch stream instead of the current one (the weight-gradient stream,
     without the Python cost of a stream context per launch)."""
     n, p, q, up = u.shape
     _, h, w, vp = v.shape
-    key = (up, vp, n, p, q, r, s)
-    need = _WGRAD_WS_NEED.get(key)
-    if need is None:
-        need = _WGRAD_WS_NEED[key] = _lib.value("msml_conv_wgrad_workspace", *key)
+    need = wgrad_ws_need(up, vp, n, p, q, r, s)
     raw = stream.cuda_stream if stream is not None else _lib.raw_stream()
     ws = workspace(need, u.device, "wgrad", stream)
     name = "conv_wgrad"
@@ -614,9 +616,7 @@ def wgrad_flush():
         # a node of another stream): launch on THAT stream with ITS scratch buffer, not the caller's
         stream = torch.cuda.ExternalStream(raw)
     g = len(items)
-    need = _WGRAD_WS_NEED.get((up, vp, n, h, w, 3, 3))
-    if need is None:
-        need = _WGRAD_WS_NEED[(up, vp, n, h, w, 3, 3)] = _lib.value("msml_conv_wgrad_workspace", up, vp, n, h, w, 3, 3)
+    need = wgrad_ws_need(up, vp, n, h, w, 3, 3)
     ws = workspace(need, items[0][0].device, "wgrad", stream)
     arr = ctypes.c_void_p * g
     us, vs, dws = arr(*[it[0].data_ptr() for it in items]), arr(*[it[1].data_ptr() for it in items]), \

@@ -8,7 +8,8 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "msml_amd", "csrc")
 HEADER = "conv_call.h"
-# the host functions that choose a conv kernel (the weight-gradient dispatch keeps its own, extern "C", queries)
+# the host functions that choose a conv kernel (the weight-gradient dispatch has its own header, wgrad_call.h, and its own
+# test of the same kind, test_wgrad_call_cpu.py)
 CONV_NAME = re.compile(r"msml_(?:conv_(?!wgrad)\w+|deconv4)_(?:dispatch|applies|tiling|persist_shape)|msml_conv_fast_splitk")
 # a prototype (ends in ';') or a definition (ends in '{'), at file scope or re-declared inside a function
 FUNCTION = re.compile(r"^[ \t]*(?:extern\s+)?(?:static\s+)?(?:bool|int)\s+(msml_\w+)\(([^;{]*)\)\s*([;{])", re.M)
