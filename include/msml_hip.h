@@ -1146,6 +1146,47 @@ int msml_png_encode(const unsigned char* src, long src_bytes, const long* meta, 
                     const int* desc, const int* desc_host, unsigned char* dst, long dst_bytes, const long* out_meta,
                     int* length, int* status, unsigned char* ws, long ws_bytes, int N, void* stream);
 
+/* ---------------------------------------------------------------- segmentation-branch evaluation -------------
+ * Scores of the occlusion segmentation branch, which the reference only looks at by eye (train.py:357-364 saves
+ * _seg.jpg beside _gt_occ.jpg, eval/qeval_mxnet.py:350-363 _learned.jpg beside _truth.jpg).  Integers only: no
+ * floating-point sum anywhere, every run gives the same bits.
+ *
+ * A MASK argument is a pointer with a `kind`, one image size (H, W in 1..256) per call:
+ *   MSML_SEG_LOGITS_F32 / MSML_SEG_LOGITS_BF16   logits [N][2][H][W], contiguous NCHW (final_seg).  A pixel is CLEAN
+ *       iff channel 1 > channel 0, compared after widening to f32; ties and NaN are OCCLUDED -- train.py:357's
+ *       final_seg.max(0)[1] (functional.mask_index);
+ *   MSML_SEG_INDEX_U8 / MSML_SEG_INDEX_I64       an index mask [N][H][W]: 0 occluded, anything else clean.
+ *   Another kind returns MSML_ERR_DTYPE, a null pointer MSML_ERR_SHAPE, N < 1 or a side outside 1..256
+ *   MSML_ERR_UNSUPPORTED; every refusal of the three entry points comes before any launch.
+ *
+ * msml_seg_counts: the confusion counts the picture pairs of train.py:357 / eval/qeval_mxnet.py:350-363 would be
+ *   compared by, in one launch.  pred: any mask kind; gt: an index mask.  counts int64 [N][4] = (tp, fp, fn, tn) per
+ *   image, positive = OCCLUDED (tp: predicted occluded and truly occluded); total int64 [4] or NULL: the launch ADDS the
+ *   sums over its N images to it (integer atomics: the order does not matter).  One workgroup per image; 16-byte loads
+ *   for an image whose planes start on 16 bytes, with a scalar tail for H W % 8 != 0, and a scalar path for the others.
+ *   MSML_ERR_SHAPE for counts / total not 8-byte aligned, MSML_ERR_DTYPE for a gt of logits.
+ *
+ * msml_seg_label: connected components of the OCCLUDED pixels of a mask -- the `blobs` the consensus loss is written
+ *   over (tricks/consensus_loss.py:83).  connectivity 4 or 8.  labels int32 [N][H][W] or NULL: 0 on clean pixels, 1..K on
+ *   the components, NUMBERED IN RASTER ORDER OF EACH COMPONENT'S FIRST PIXEL (scipy.ndimage.label's numbering);
+ *   count int32 [N] = K; status int32 [N]: 0, or 2 for an image on which a loop reached its bound (count 0, labels 0:
+ *   no input is known to reach it; the kernel never spins).  One workgroup per image, the parent plane of a union-find in
+ *   LDS: rows seed their runs, atomicMin on the parent merges vertically adjacent runs, the roots are ranked by a
+ *   prefix sum (docs/KERNELS.md).  MSML_ERR_UNSUPPORTED for H W > 16384 (64 KiB of LDS) and another connectivity.
+ *
+ * msml_seg_blob_table: per-component statistics of mask A against mask B.  labels / count: msml_seg_label's outputs for
+ *   A; b: any mask kind.  table int32 [N][cap][6]: row k - 1 of image n = (area, hit, x0, y0, x1, y1) of A's component
+ *   k: its pixel count, how many of those pixels are occluded in B, and its inclusive bounding box.  Rows from
+ *   min(count, cap) on are zeros; count > cap is how a caller sees the overflow.  cap in 1..1024
+ *   (MSML_ERR_UNSUPPORTED otherwise); labels outside 1..min(count, cap) are not counted. */
+enum { MSML_SEG_LOGITS_F32 = 0, MSML_SEG_LOGITS_BF16 = 1, MSML_SEG_INDEX_U8 = 2, MSML_SEG_INDEX_I64 = 3 };
+int msml_seg_counts(const void* pred, int pred_kind, const void* gt, int gt_kind, long* counts, long* total, int N, int H,
+                    int W, void* stream);
+int msml_seg_label(const void* mask, int kind, int* labels, int* count, int* status, int N, int H, int W,
+                   int connectivity, void* stream);
+int msml_seg_blob_table(const int* labels, const int* count, const void* b, int b_kind, int* table, int N, int H, int W,
+                        int cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ eval/qeval_mxnet.py:326-390 uses the same orig + flip sum).
 * `eval_pairs` / `extract_sum` / `occlusion_sweep`: test.py itself (eval/qeval_mxnet.py:486-600) -- the model inputs
   of one extraction in one launch (msml_eval_pairs), the orig + mirror feature sum, and the loop over occlusion
   levels and repeats that prints the paper's table.
+* `eval_pair_masks` / `segmentation_sweep`: the same loop for the segmentation branch -- the ground-truth masks of
+  eval_pairs' rows and the pixel / blob scores of `final_seg` against them (msml_amd/segeval.py).
 """
 import numpy as np
 import torch
@@ -463,3 +465,109 @@ def load_bin(path, image_size, device="cuda"):
                               device=device)
     data = faces.permute(0, 3, 1, 2).float().contiguous()
     return [data, data.flip(3).contiguous()], issame
+
+
+# ---------------------------------------------------------------------------------------------- the mask branch
+@torch.no_grad()
+def eval_pair_masks(n, h, w, seed=1, index0=0, lo=0, hi=1, protocol="BB", out_size=None, device="cuda"):
+    """The ground-truth masks of the 2n rows eval_pairs builds from n source images of h x w with the same arguments:
+    uint8 [2n][oh][ow] on the device, 0 inside the row's block and 1 elsewhere (the `msk` convention of data.augment).
+    The same data.draw(2n, seed, 2 * index0, mode="block", ..., size=ow) descriptors and the same rectangle words (kind,
+    x0, y0, w, h; cropped at the border) as msml_eval_pairs reads, the same NB rule (images with an odd global index
+    index0 + i stay clean) and the same refusals.  lo = hi = None, or (0, 1), gives all ones.  A few torch operations on
+    the descriptors, no synchronisation."""
+    if protocol not in PROTOCOLS:
+        raise ValueError("eval_pair_masks: protocol %r is not one of %s" % (protocol, sorted(PROTOCOLS)))
+    if (lo is None) != (hi is None):
+        raise ValueError("eval_pair_masks: lo and hi are both None or both integers")
+    if not _no_block(lo, hi) and not 0 <= int(lo) < int(hi) <= 101:
+        raise ValueError("eval_pair_masks: block range [%r, %r) outside 0..101" % (lo, hi))
+    if int(index0) < 0:
+        raise ValueError("eval_pair_masks: index0 = %r" % (index0,))
+    if int(n) < 1:
+        raise ValueError("eval_pair_masks: n = %r" % (n,))
+    from . import data
+    n, h, w = int(n), int(h), int(w)
+    oh, ow = data._out_hw(out_size, h, w)
+    if ow % 4 or not (4 <= h <= 256 and 4 <= w <= 256 and 4 <= oh <= 256 and 4 <= ow <= 256):
+        raise ValueError("eval_pair_masks: source %d x %d -> output %d x %d: sizes 4..256, output width a multiple of 4"
+                         % (h, w, oh, ow))
+    if _no_block(lo, hi):
+        return torch.ones(2 * n, oh, ow, dtype=torch.uint8, device=device)
+    desc = data.draw(2 * n, seed, 2 * int(index0), mode="block", lo=int(lo), hi=int(hi), flip=False, size=ow,
+                     device=device)
+    kind, bx, by, bw, bh = (desc[:, k].view(-1, 1, 1) for k in range(5))
+    ys = torch.arange(oh, dtype=torch.int32, device=desc.device).view(1, oh, 1)
+    xs = torch.arange(ow, dtype=torch.int32, device=desc.device).view(1, 1, ow)
+    inside = (kind == 3) & (ys >= by) & (ys < by + bh) & (xs >= bx) & (xs < bx + bw)
+    if protocol == "NB":
+        g = int(index0) + torch.arange(2 * n, device=desc.device) // 2
+        inside &= (g % 2 == 0).view(-1, 1, 1)
+    return (~inside).to(torch.uint8)
+
+
+@torch.no_grad()
+def segmentation_sweep(model, src, levels=LEVELS, repeats=10, seed=1, batch=256, fill="black", protocol="BB",
+                       out_size=None, gray=False, use_norm=True, tau=0.5, min_area=1, connectivity=8, cap=1024):
+    """occlusion_sweep's loop for the OTHER output of the model: did the segmentation branch find the block?  The same
+    levels, the same repeat rule (one extraction for (0, 1) and (100, 101)) and the same sweep_seed(seed, k, r) seeds, so the
+    two tables line up row for row.  Every eval_pairs batch goes through the model; its `final_seg` (the second output)
+    is scored against eval_pair_masks of the same arguments: segeval.mask_counts (pixels) and segeval.blob_totals (blobs
+    of `connectivity`, at most `cap` per mask, found / false alarm at `tau`).  src: uint8 [N][H][W][3] on the device.
+
+    Returns {"levels", "metrics": per level segeval.metrics_from_counts of the counts pooled over its repeats, "blobs": per
+    level the blob_detection dict of the totals pooled over its repeats, "counts": per level int64 [repeats][4],
+    "metrics_runs" / "blobs_runs": per level the lists of per-repeat dicts}.  A row with more than `cap` components in
+    either mask (the salt-and-pepper output of an untrained branch) is left out of the blob totals and counted in the
+    dict's "n_overflow" instead of ending the sweep; a labelling status other than 0 raises RuntimeError as in
+    blob_detection.  ValueError for a model without a second output (use_osb=False) or whose final_seg is not
+    [rows][2][oh][ow] of the input's size.
+    The host waits for the device once per level, after its last launch."""
+    from . import segeval
+    levels = [(int(lo), int(hi)) for lo, hi in levels]
+    res = {"levels": levels, "metrics": [], "blobs": [], "counts": [], "metrics_runs": [], "blobs_runs": []}
+    n, h, w = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    batch = max(1, int(batch))
+    for k, (lo, hi) in enumerate(levels):
+        reps = 1 if (lo, hi) in ((0, 1), (100, 101)) else int(repeats)
+        pix = torch.zeros(reps, 4, dtype=torch.int64, device=src.device)
+        blob = torch.zeros(reps, 5, dtype=torch.int64, device=src.device)
+        bad = []
+        for r in range(reps):
+            s = sweep_seed(seed, k, r)
+            for i0 in range(0, n, batch):
+                i1 = min(n, i0 + batch)
+                x = eval_pairs(src[i0:i1], seed=s, index0=i0, lo=lo, hi=hi, fill=fill, protocol=protocol,
+                               out_size=out_size, gray=gray, use_norm=use_norm)
+                out = model(x)
+                if not isinstance(out, (tuple, list)) or len(out) < 2 or out[1] is None:
+                    raise ValueError("segmentation_sweep: the model returns no final_seg (use_osb=False?)")
+                seg = out[1]
+                if seg.dim() != 4 or seg.shape[0] != x.shape[0] or seg.shape[1] != 2 or seg.shape[2:] != x.shape[2:]:
+                    raise ValueError("segmentation_sweep: final_seg is %s for inputs %s" % (tuple(seg.shape), tuple(x.shape)))
+                if seg.dtype not in (torch.float32, torch.bfloat16):
+                    seg = seg.float()
+                seg = seg.contiguous()
+                gt = eval_pair_masks(i1 - i0, h, w, seed=s, index0=i0, lo=lo, hi=hi, protocol=protocol, out_size=out_size,
+                                     device=src.device)
+                segeval.mask_counts(seg, gt, total=pix[r])
+                totals, over, failed = segeval.blob_totals(seg, gt, tau, min_area, connectivity, cap)
+                blob[r, :4] += (totals * (~over).view(-1, 1)).sum(0)
+                blob[r, 4] += over.sum()
+                bad.append((2 * i0, failed))
+        for row0, failed in bad:                                # the level's first wait for the device
+            segeval.raise_if_failed(failed, row0)
+        pix_h, blob_h = pix.cpu().numpy(), blob.cpu().numpy()
+        res["counts"].append(pix_h)
+        res["metrics"].append(segeval.metrics_from_counts(pix_h.sum(0)))
+        res["blobs"].append(_blob_dict(blob_h.sum(0)))
+        res["metrics_runs"].append([segeval.metrics_from_counts(c) for c in pix_h])
+        res["blobs_runs"].append([_blob_dict(t) for t in blob_h])
+    return res
+
+
+def _blob_dict(t):
+    from . import segeval
+    d = segeval.detection_from_totals(t[:4])
+    d["n_overflow"] = int(t[4])
+    return d
