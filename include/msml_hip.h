@@ -150,8 +150,10 @@ int msml_conv2d(const void* in0, int c0p, const void* in1, int c1p, const void* 
                 int in_dtype, int out_dtype, void* stream);
 
 /* msml_conv2d whose BatchNorm statistics go to an ACCUMULATOR instead of partial rows: `acc` is a zero-initialised
- * double[8][2][coutp]; every workgroup adds its per-channel (sum, sumsq) of the stored output with f64 atomics into
- * row (workgroup index % 8).  f64 sums of f32 partials are exact unless two partials differ by more than 2^29, so the
+ * double[8][2][coutp]; every workgroup adds its per-channel (sum, sumsq) with f64 atomics into row (workgroup index % 8).
+ * The sums are those of row mode: of the f32 results (acc + bias) BEFORE they are rounded to the storage type, in every
+ * kernel family (tests/conv_cases.py, STATDEF) -- not of the stored bf16 output, which differs from them by up to half a
+ * bf16 ulp per element.  f64 sums of f32 partials are exact unless two partials differ by more than 2^29, so the
  * totals do not depend on the order of the adds.  Consumed by msml_bn_fin_act_fwd (no finalize launch in between:
  * the nn.BatchNorm2d that follows a conv in IBasicBlock, backbones/frb/iresnet.py:56-67). */
 int msml_conv2d_acc(const void* in0, int c0p, const void* in1, int c1p, const void* wp, int kop,
@@ -395,7 +397,9 @@ int msml_transpose(const void* src, int R, int C, int ld_s, void* dst, int ld_d,
 /* Inference conv with the eval-mode BatchNorm folded into the epilogue (bf16 tensors only):
  *   res_first == 0: out = prelu(acc*scale[c] + shift[c], alpha[c]) + residual   (IBasicBlock)
  *   res_first == 1: out = prelu(acc*scale[c] + shift[c] + residual, alpha[c])   (resblock_bottle)
- * scale/shift from msml_bn_finalize(rows = 0); alpha, residual optional.  Replaces the
+ * scale/shift from msml_bn_finalize(rows = 0); alpha, residual optional.  The residual joins the value AS STORED: every
+ * kernel rounds prelu(acc*scale + shift) (res_first: acc*scale + shift) to bf16 in its copy-out layout, adds the bf16
+ * residual to that in f32 and rounds once more -- the rounding points of the chain the call replaces.  Replaces the
  * conv -> BatchNorm(eval) -> PReLU -> (+identity) chains of backbones/frb/iresnet.py:59-66,
  * backbones/fm/fmoperator.py:55-67 in eval mode (eval/verification.py:271). */
 int msml_conv2d_fused(const void* in0, int c0p, const void* in1, int c1p, const void* wp, int kop,
